@@ -26,9 +26,75 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 ALG_BYTES = {(5, 6): 1320, (5, 12): 2184, (6, 6): 1528}       # algorithmic bytes per instance-step
-HBM_PEAK_GBPS = 8000.0                                          # /opt/skills/guides/MI355X_MICROARCH.md:35 (spec)
+HBM_PEAK_GBPS = 8000.0                                          # MI355X HBM3E peak (spec)
+DUMP_BYTES_MAX = 64 << 20                                       # --dump-outputs: at most this much in all
 
 
+def host_cpus():
+    """CPUs this process may use: its affinity mask, capped by OMP_NUM_THREADS where the environment sets it (a shared host
+    sets it to one job's share; os.cpu_count() counts the whole machine, and pools sized by it only oversubscribe)"""
+    try:
+        n = len(os.sched_getaffinity(0))
+    except AttributeError:
+        n = os.cpu_count() or 1
+    v = os.environ.get("OMP_NUM_THREADS", "")
+    if v.isdigit() and int(v) > 0:
+        n = min(n, int(v))
+    return max(1, n)
+
+
+class HostJobs:
+    """Functions of tests/independent.py (SLSQP classification) run in worker processes started from scratch, at most `procs`
+    at a time, in the background while the GPU legs go on.  A job still running at `deadline` (time.time(); None = no limit)
+    is stopped and its result is None: the caller reports it as not classified within the budget."""
+
+    def __init__(self, procs, deadline):
+        from concurrent.futures import ThreadPoolExecutor
+        self.ex = ThreadPoolExecutor(max_workers=max(1, procs))
+        self.deadline = deadline
+
+    def submit(self, fn, jobs):
+        return [self.ex.submit(self._run, fn.__name__, j) for j in jobs]
+
+    def _run(self, name, job):
+        import pickle
+        import subprocess
+        import tempfile
+        left = None if self.deadline is None else self.deadline - time.time()
+        if left is not None and left <= 0:
+            return None
+        with tempfile.TemporaryDirectory() as tmp:
+            fin, fout = os.path.join(tmp, "in.pkl"), os.path.join(tmp, "out.pkl")
+            with open(fin, "wb") as fh:
+                pickle.dump([job], fh)
+            try:
+                r = subprocess.run([sys.executable, "-m", "tests.independent", name, fin, fout], cwd=ROOT, timeout=left,
+                                   env=dict(os.environ, OMP_NUM_THREADS="1", OPENBLAS_NUM_THREADS="1"))
+            except subprocess.TimeoutExpired:
+                return None
+            if r.returncode != 0:
+                raise RuntimeError("independent-solver worker failed")
+            with open(fout, "rb") as fh:
+                return pickle.load(fh)[0]
+
+    def close(self):
+        self.ex.shutdown(wait=True)
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: the arrays of the last timed step as d/<name>.npy (float64).  Over DUMP_BYTES_MAX in all, a fixed seeded
+    sample of instances (rows) is written instead, with its row indices as sample_index.npy."""
+    os.makedirs(d, exist_ok=True)
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    n = next(iter(arrays.values())).shape[0]
+    per_row = sum(a.nbytes for a in arrays.values()) / max(n, 1)
+    if per_row * n > DUMP_BYTES_MAX:
+        keep = int(DUMP_BYTES_MAX // (per_row + 8))                 # + 8: the row index written beside the sample
+        idx = np.sort(np.random.default_rng(20260928).choice(n, size=keep, replace=False))
+        arrays = {k: a[idx] for k, a in arrays.items()}
+        arrays["sample_index"] = idx.astype(np.float64)
+    for k, a in arrays.items():
+        np.save(os.path.join(d, k + ".npy"), a)
 
 
 def _pmc_summary_file():
@@ -104,7 +170,7 @@ def cpu_oracle(batch, N, seconds=10.0):
     """The dense oracle (plain-C restatement, oracle/obca_oracle.c: dense Bunch-Kaufman KKT solves) timed on the host cores of
     this box on a bounded sample of the same workload -- context: it is the CHECKER's speed, not a same-algorithm baseline."""
     from oracle import c_oracle
-    cores = os.cpu_count() or 1
+    cores = host_cpus()
     n, solved = 0, 0
     chunk = max(cores, 8)
     t0 = time.time()
@@ -131,7 +197,7 @@ def independent_leg(solver, batch, dv, N, prm, n=64):
     z, y = solver.cert_z[:n].cpu().numpy(), solver.cert_y[:n].cpu().numpy()
     ok = [i for i in range(n) if st[i] in (0, 1)]
     ps = {i: kkt_check.problem_of(batch, i, N) for i in ok}
-    procs = max(1, min(128, os.cpu_count() or 1))
+    procs = max(1, min(128, host_cpus()))
     t0 = time.time()
     pol = ind.pool_map(ind.polish, [(ps[i], z[i], y[i]) for i in ok], procs)
     sta = ind.pool_map(ind.from_starts, [(ps[i], z[i], i) for i in ok], procs)
@@ -149,7 +215,7 @@ def cpu_baseline(batch, N):
         native_build.load()
     except Exception as e:          # no g++ / build failed: the figure is optional
         return {"value": None, "note": "host build of the structured core unavailable: %r" % (e,)}
-    cores = os.cpu_count() or 1
+    cores = host_cpus()
     n = min(batch["x0"].shape[0], max(64 * cores, 1024))           # one call: the thread pool is started once
     sl = slice(0, n)
     native_build.lpi_solve(4, N, batch["m"], batch["x0"][:cores], batch["u0"][:cores], batch["xref"][:cores],
@@ -164,9 +230,28 @@ def cpu_baseline(batch, N):
 
 
 _C3_BATCHES = {}          # generated once per run (the start-order legs solve the same instances)
+_PENDING = []             # (dict, key, futures, fill): background classifications, filled in before the line is printed
 
 
-def config_c3(B, N=20, start_order=0, classify=False):
+def _classify(host, fn, jobs, procs, into, key, fill):
+    """into[key] = fill(fn over jobs): at once in `procs` worker processes without a background pool, else when the run ends"""
+    if host is None:
+        from tests import independent as ind
+        into[key] = fill(ind.pool_map(fn, jobs, procs))
+    else:
+        _PENDING.append((into, key, host.submit(fn, jobs), fill))
+
+
+def finish_pending():
+    while _PENDING:
+        into, key, futs, fill = _PENDING.pop(0)
+        try:
+            into[key] = fill([f.result() for f in futs])
+        except Exception as e:          # noqa: BLE001
+            into[key] = {"error": repr(e)}
+
+
+def config_c3(B, N=20, start_order=0, classify=False, host=None):
     """Config C3: N=20, walls + box + two moving boxes, lidar-gated: the free-time sub-batch (obca_mpc4, three
     static obstacles) and the gated sub-batch (obca_mpc6, five obstacles, time-varying rows), B UNIQUE seeded instances
     each; both run on the four-wavefront LDS kernel."""
@@ -174,7 +259,7 @@ def config_c3(B, N=20, start_order=0, classify=False):
     from vehicle_motion_planning_with_obstacles_avoidance_using_mpc_amd.solver import BatchSolver, SolverParams
     res = {"workload": "C3 (SURVEY 8d): N=%d, B=%d unique seeded instances per sub-batch" % (N, B),
            "kernel": "free-time half (three obstacles): one wavefront per instance, row state in an HBM workspace (obca_ipm_kernel_gm1); gated half (five obstacles): four wavefronts per instance, LDS resident, two-sided Riccati sweep"}
-    procs = max(1, min(48, (os.cpu_count() or 1) // 2))
+    procs = max(1, min(48, host_cpus()))
     for name, gated in (("free_time_obca_mpc4", False), ("gated_obca_mpc6", True)):
         if (B, N, gated) not in _C3_BATCHES:
             _C3_BATCHES[(B, N, gated)] = sc.make_batch_c3(B, N, gated=gated, procs=procs)
@@ -199,14 +284,20 @@ def config_c3(B, N=20, start_order=0, classify=False):
         bad = np.flatnonzero(~np.isin(st, (0, 1)))
         if classify and len(bad) and len(bad) <= 64:
             # every instance the ladder gave up on: SciPy SLSQP on the pinned model from seven starts (tests/independent.py:classify)
+            def fill(rows, bad=bad):
+                done = [r for r in rows if r is not None]
+                d = {"instances": [int(i) for i in bad],
+                     "feasible_point_exists_solver_failure": [int(r["tag"]) for r in done if r["feasible_point_found"]],
+                     "no_feasible_point_found": int(sum(not r["feasible_point_found"] for r in done)),
+                     "method": "SciPy SLSQP on the pinned model, seven starts each (window, straight line, window moved 1.5 / 3 m to either side)"}
+                if len(done) < len(rows):
+                    d["not_classified_within_budget"] = [int(i) for i, r in zip(bad, rows) if r is None]
+                return d
             try:
                 from tests import independent as ind, kkt_check
                 probs = [kkt_check.problem_of(b, int(i), N) for i in bad]
-                rows = ind.pool_map(ind.classify, [(q, ind.trajectory_start(q, q.xref), int(i)) for q, i in zip(probs, bad)], min(len(bad), os.cpu_count() or 1))
-                res[name]["failures_classified"] = {"instances": [int(i) for i in bad],
-                                                    "feasible_point_exists_solver_failure": [int(r["tag"]) for r in rows if r["feasible_point_found"]],
-                                                    "no_feasible_point_found": int(sum(not r["feasible_point_found"] for r in rows)),
-                                                    "method": "SciPy SLSQP on the pinned model, seven starts each (window, straight line, window moved 1.5 / 3 m to either side)"}
+                _classify(host, ind.classify, [(q, ind.trajectory_start(q, q.xref), int(i)) for q, i in zip(probs, bad)],
+                          min(len(bad), host_cpus()), res[name], "failures_classified", fill)
             except Exception as e:          # noqa: BLE001
                 res[name]["failures_classified"] = {"error": repr(e)}
     return res
@@ -355,7 +446,7 @@ def start_order_leg(solver, dv, out0, B, order, steps=3):
             "same_optimum_as_the_default_order": int(same.sum().item()), "of_instances_both_solved": int(both.sum().item())}
 
 
-def closed_loop_c5(B, n_dyn=2, warm_start=None, first=0, dist=None, classify=False, classify_max=None, start_order=0, dodge=True):
+def closed_loop_c5(B, n_dyn=2, warm_start=None, first=0, dist=None, classify=False, classify_max=None, start_order=0, dodge=True, host=None):
     """Config C5: B Monte-Carlo rollouts of the receding-horizon loop per GPU, harness and solves on the device
     (obca_rollouts_run: one persistent kernel, one wavefront per rollout); worlds first .. first+B-1, resident in HBM
     before the clock starts.  With a process group every rank runs the whole loop for its own worlds (no collective on
@@ -412,16 +503,21 @@ def closed_loop_c5(B, n_dyn=2, warm_start=None, first=0, dist=None, classify=Fal
                 if classify_max is not None and n_stopped > classify_max:      # bounded sample: one job per process, one wave
                     stopped = stopped[:classify_max]
                 t1 = time.time()
-                rows = ind.pool_map(ind.classify_stopped_world, [(first + int(i), n_dyn, int(o["steps"][i])) for i in stopped],
-                                    max(1, min(192, os.cpu_count() or 1)))
-                same = [r for r in rows if not r["replay_differs"]]
-                res["stopped_infeasible_split"] = {
-                    "sample": "%d of the %d stopped rollouts (lowest world indices%s)" % (len(stopped), n_stopped, "" if len(stopped) == n_stopped else "; --classify-all for every one"),
-                    "classified": len(same), "feasible_point_exists_solver_failure": int(sum(r["feasible_point_found"] for r in same)),
-                    "no_feasible_point_found": int(sum(not r["feasible_point_found"] for r in same)),
-                    "host_replay_stops_elsewhere": len(rows) - len(same),
-                    "solver_failures_world_step_variant_status": [list(r["tag"]) for r in same if r["feasible_point_found"]],
-                    "method": "host replay of each stopped rollout (structured core), last solve to SciPy SLSQP from seven starts on the pinned model (window, straight line, last iterate, window moved 1.5 / 3 m to either side), %.1f s" % (time.time() - t1)}
+
+                def fill(rows):
+                    done = [r for r in rows if r is not None]
+                    same = [r for r in done if not r["replay_differs"]]
+                    d = {"sample": "%d of the %d stopped rollouts (lowest world indices%s)" % (len(stopped), n_stopped, "" if len(stopped) == n_stopped else "; --classify-all for every one"),
+                         "classified": len(same), "feasible_point_exists_solver_failure": int(sum(r["feasible_point_found"] for r in same)),
+                         "no_feasible_point_found": int(sum(not r["feasible_point_found"] for r in same)),
+                         "host_replay_stops_elsewhere": len(done) - len(same),
+                         "solver_failures_world_step_variant_status": [list(r["tag"]) for r in same if r["feasible_point_found"]],
+                         "method": "host replay of each stopped rollout (structured core), last solve to SciPy SLSQP from seven starts on the pinned model (window, straight line, last iterate, window moved 1.5 / 3 m to either side), %.1f s" % (time.time() - t1)}
+                    if len(done) < len(rows):
+                        d["not_classified_within_budget"] = len(rows) - len(done)
+                    return d
+                _classify(host, ind.classify_stopped_world, [(first + int(i), n_dyn, int(o["steps"][i])) for i in stopped],
+                          max(1, min(192, host_cpus())), res, "stopped_infeasible_split", fill)
             except Exception as e:          # noqa: BLE001
                 res["stopped_infeasible_split"] = {"error": repr(e)}
     return res
@@ -455,20 +551,24 @@ def main():
     ap.add_argument("--batch", type=int, default=8192, help="instances per GPU")
     ap.add_argument("--horizon", type=int, default=5)
     ap.add_argument("--three-boxes", action="store_true", help="M=12 sub-config (3 boxes) instead of walls+box (M=6)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one returned (xopt, uopt, ts_opt, status, iters, info; float64) "
+                         "as DIR/<name>.npy -- at most 64 MB in all, a fixed seeded sample of instances beyond that")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: batch_1024, cpu_baseline, the dense-oracle timing, SLSQP cross-checks, config_c3, "
+                         "closed_loop (C5, 48 stopped rollouts classified), the start-order legs (with the x0-first re-runs of C3 / open loop / "
+                         "C5), open_loop, the reference-picture replays and the static closed loops; under a launcher the sharded closed loop.  "
+                         "Without it a run times the headline only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: leave out the host legs (CPU timings, SLSQP)")
     ap.add_argument("--cpu-seconds", type=float, default=20.0)
     ap.add_argument("--classify-all", action="store_true",
-                    help="classify EVERY stopped C5 rollout on the host (about three minutes on 256 cores) instead of the first 48")
+                    help="--full: classify EVERY stopped C5 rollout on the host (about three minutes on 256 cores) instead of the first 48, "
+                         "and every classification to its end, however long it takes")
     ap.add_argument("--closed-loop-rollouts", type=int, default=4096,
-                    help="config C5 reported beside the headline number at N=1 (0 = skip)")
-    ap.add_argument("--full", action="store_true",
-                    help="every secondary leg (dense-oracle timing, SLSQP cross-checks, the reference-picture replays, the x0-first re-runs of "
-                         "C3 / open loop / C5, failure classification): about ten minutes.  The default run (about 100 s) keeps the headline, batch_1024, "
-                         "cpu_baseline, roofline, config_c3, closed_loop (C5, 16 stopped rollouts classified), the start-order legs on the headline "
-                         "batch, open_loop, the reference-picture replays and the static closed loops, and stops adding legs once "
-                         "--budget-seconds of wall time are spent")
-    ap.add_argument("--budget-seconds", type=float, default=150.0,
-                    help="default run only: secondary legs that would start after this much wall time are skipped (and say so)")
+                    help="--full: rollouts of config C5 (0 = skip the closed-loop legs)")
+    ap.add_argument("--budget-seconds", type=float, default=420.0,
+                    help="--full without --classify-all: host-side SLSQP classifications run in the background beside the GPU legs; "
+                         "one still running this long after the start is stopped and reported as not classified within the budget")
     args = ap.parse_args()
     t_start = time.time()
 
@@ -501,7 +601,7 @@ def main():
 
     B, N = args.batch, args.horizon
     batch = sc.make_batch(B, N, three_boxes=args.three_boxes, first=rank * B,             # shard: instances rank*B ..
-                          procs=max(1, min(16, (os.cpu_count() or 1) // max(world, 1))))
+                          procs=max(1, min(16, host_cpus() // max(world, 1))))
     M = sum(batch["m"])
     solver = BatchSolver(N, batch["m"], max_batch=B, device=dev)
     solver_rows = 3 + 3 * N + 3 + 2 * (N + 1) + 4 * N + 2 + (N + 1) * (2 * len(batch["m"]) + M + 4 * len(batch["m"]))
@@ -536,7 +636,7 @@ def main():
     # configs[1] of BASELINE.json names the same workload at batch 1024: one wave per SIMD slot, so a launch lasts as
     # long as its slowest instance -- reported beside the headline (batch 8192, the north-star's size)
     small = None
-    if world == 1 and B >= 1024:
+    if args.full and world == 1 and B >= 1024:
         dv_s = {k: v[:1024].contiguous() for k, v in dv.items()}
         s_small = BatchSolver(N, batch["m"], max_batch=1024, device=dev)
         o_small = None
@@ -558,20 +658,23 @@ def main():
     ok = ((out.status == 0) | (out.status == 1)).sum().to(torch.float64)
     stats = torch.stack([torch.tensor(elapsed, dtype=torch.float64, device=dev), ok,
                          out.iters.to(torch.float64).sum(), out.info[:, 3].sum()])
+    names = ("xopt", "uopt", "ts_opt", "status") + (("iters", "info") if args.dump_outputs else ())
+    outputs = {k: getattr(out, k) for k in names}
     if dist:
         tmax = stats[:1].clone()
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dist.all_reduce(stats, op=dist.ReduceOp.SUM)
         elapsed = float(tmax.item())
         from vehicle_motion_planning_with_obstacles_avoidance_using_mpc_amd.sharding import gather_outputs
-        full = gather_outputs(dist, {"xopt": out.xopt, "uopt": out.uopt, "ts_opt": out.ts_opt, "status": out.status},
-                              B * world, world)                            # the one data collective: outputs
-        assert full["xopt"].shape[0] == B * world
+        outputs = gather_outputs(dist, outputs, B * world, world)           # the one data collective: outputs
+        assert outputs["xopt"].shape[0] == B * world
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {k: v.cpu().numpy() for k, v in outputs.items()})
     n_ok, it_sum, nf_sum = float(stats[1]), float(stats[2]), float(stats[3])
     total = B * world
     # the closed loop (config C5) sharded the same way: every rank runs the whole loop for its own rollouts
     c5_multi = None
-    if dist is not None and args.closed_loop_rollouts > 0:
+    if args.full and dist is not None and args.closed_loop_rollouts > 0:
         try:
             c5_multi = closed_loop_c5(args.closed_loop_rollouts, first=rank * args.closed_loop_rollouts, dist=dist)
         except Exception as e:          # noqa: BLE001
@@ -622,76 +725,79 @@ def main():
             line["closed_loop"] = c5_multi
         if small is not None:
             line["batch_1024"] = small
-        # ---- secondary legs.  (name, function, part of the default run).  A failure in one of them must not cost the headline line;
-        # a default run skips the `--full` legs and whatever would start after the wall budget, and says so under the leg's key.
-        legs = []
-        cpu = dist is None and not args.no_cpu_baseline
-        if cpu:
-            legs.append(("cpu_baseline", lambda: cpu_baseline(batch, N), True))
-            legs.append(("ipopt", lambda: ipopt_leg(batch, N), True))             # the reference's own solver, where it exists (not in this image)
-            legs.append(("cpu_oracle", lambda: cpu_oracle(batch, N, min(args.cpu_seconds, 10.0)), False))
-            legs.append(("independent_solver", lambda: independent_leg(solver, batch, dv, N, prm), False))   # SLSQP on the pinned model (tests/independent.py)
-        if dist is None and args.closed_loop_rollouts > 0:
-            def x0_first_all():
-                r = start_order_leg(solver, dv, out, B, "x0")
-                r["note"] = "obca_params.start_order = OBCA_START_X0_FIRST: x0 first for every variant -- for obca_mpc4 the default until obca_mpc 0.4, i.e. the configuration BENCH_r01 ... BENCH_r04 were measured in (NOT the default)"
-                if args.full:
-                    r["config_c3"] = config_c3(B, start_order="x0")
-                    ol = open_loop(start_order="x0")
-                    r["open_loop"] = {k: v for k, v in ol.items() if isinstance(v, dict) and "seconds" in v}
-                    c5 = closed_loop_c5(args.closed_loop_rollouts, start_order="x0")
-                    r["closed_loop"] = {k: c5[k] for k in ("value", "unit", "seconds", "converged_steps", "attempted_steps", "rollouts_to_step_cap", "rollouts_stopped_infeasible", "mean_ipm_iters") if k in c5}
-                else:
-                    r["config_c3"] = r["open_loop"] = r["closed_loop"] = {"skipped": "--full"}
-                return r
-
-            def zeros_first():
-                r = start_order_leg(solver, dv, out, B, "zeros")
-                r["note"] = "obca_params.start_order = OBCA_START_ZEROS_FIRST: the reference's literal all-zero start first (src/obca.py:856) -- the default of rounds 1-3, kept for comparison"
-                return r
-            def c5_dodge_off():
-                c5 = closed_loop_c5(args.closed_loop_rollouts, dodge=False)
-                r = {k: c5[k] for k in ("value", "unit", "seconds", "converged_steps", "attempted_steps", "rollouts_to_step_cap", "rollouts_stopped_infeasible", "mean_ipm_iters") if k in c5}
-                r["note"] = ("obca_params.dodge = off (NOT the default): the ladder's last rung costs C5 a third of its launch and rescues ~20 of 4096 rollouts -- the launch lasts as long "
-                             "as its longest ROLLOUT (a serial chain of <= 30 steps), and the rescued rollouts, which need the rung again at every later step, are the longest "
-                             "(profiles/r06_c5_dodge.txt); the rung stays on because the reference's own demo11 run needs it (DESIGN.md section 2)")
-                return r
-            classify = cpu and args.full
-            legs += [("config_c3", lambda: config_c3(B, classify=classify), True),
-                     ("closed_loop", lambda: closed_loop_c5(args.closed_loop_rollouts, classify=cpu,
-                                                            classify_max=None if args.classify_all else (48 if args.full else 16)), True),
-                     ("x0_first", x0_first_all, True),
-                     ("closed_loop_dodge_off", c5_dodge_off, True),
-                     ("open_loop", lambda: open_loop(classify=classify), True),
-                     ("reference_gif", reference_gif_leg, True),
-                     ("zeros_first", zeros_first, True),
-                     ("reference_report_figures", report_figures_leg, True),
-                     # the same loop with the three static obstacles only, at the batch size BASELINE.json quotes
-                     ("closed_loop_static", lambda: closed_loop_c5(B, n_dyn=0), True),
-                     # optional extension, NOT reference behaviour (the reference cold-starts): shifted previous plan
-                     ("closed_loop_static_warm_start", lambda: closed_loop_c5(B, n_dyn=0, warm_start=0.1), True)]
-        leg_s = {}
-        for name, fn, in_default in legs:
-            if not args.full and not in_default:
-                line[name] = {"skipped": "--full"}
-                continue
-            if not args.full and time.time() - t_start > args.budget_seconds:
-                line[name] = {"skipped": "wall budget of the default run (%.0f s) spent; --full runs it" % args.budget_seconds}
-                continue
-            t_leg = time.time()
-            try:
-                line[name] = fn()
-            except Exception as e:          # noqa: BLE001
-                line[name] = {"value": None, "error": repr(e)} if name.startswith("cpu_") else {"error": repr(e)}
-            leg_s[name] = round(time.time() - t_leg, 1)
-        if cpu and line.get("ipopt") == "unavailable" and isinstance(line.get("cpu_baseline"), dict):
-            line["cpu_baseline"]["note"] = "IPOPT unavailable (`import casadi` fails on this box); the reference publishes 3.7 s per solve at N=10 (src/simulation.py:231)"
-        line["leg_seconds"] = leg_s
+        if args.full:
+            full_legs(args, line, solver, batch, dv, out, prm, B, N, dist, t_start)
         line["wall_seconds"] = round(time.time() - t_start, 1)
-        line["run"] = "full" if args.full else "default (secondary legs under a %.0f s wall budget; --full runs all of them)" % args.budget_seconds
+        line["run"] = "full" if args.full else "headline only (--full runs the secondary legs)"
         print(json.dumps(line))
     if dist:
         dist.destroy_process_group()
+
+
+def full_legs(args, line, solver, batch, dv, out, prm, B, N, dist, t_start):
+    """--full: the secondary legs, one key of the line each.  A failure in one of them must not cost the headline line.  The
+    host-side classifications run in the background beside the GPU legs and are filled in before the line is printed."""
+    host = HostJobs(host_cpus(), None if args.classify_all else t_start + args.budget_seconds)
+    legs = []
+    cpu = dist is None and not args.no_cpu_baseline
+    if cpu:
+        legs.append(("cpu_baseline", lambda: cpu_baseline(batch, N)))
+        legs.append(("ipopt", lambda: ipopt_leg(batch, N)))             # the reference's own solver, where it exists (not in this image)
+        legs.append(("cpu_oracle", lambda: cpu_oracle(batch, N, min(args.cpu_seconds, 10.0))))
+        legs.append(("independent_solver", lambda: independent_leg(solver, batch, dv, N, prm)))   # SLSQP on the pinned model (tests/independent.py)
+    if dist is None and args.closed_loop_rollouts > 0:
+        def x0_first_all():
+            r = start_order_leg(solver, dv, out, B, "x0")
+            r["note"] = "obca_params.start_order = OBCA_START_X0_FIRST: x0 first for every variant -- for obca_mpc4 the default until obca_mpc 0.4, i.e. the configuration BENCH_r01 ... BENCH_r04 were measured in (NOT the default)"
+            r["config_c3"] = config_c3(B, start_order="x0")
+            ol = open_loop(start_order="x0")
+            r["open_loop"] = {k: v for k, v in ol.items() if isinstance(v, dict) and "seconds" in v}
+            c5 = closed_loop_c5(args.closed_loop_rollouts, start_order="x0")
+            r["closed_loop"] = {k: c5[k] for k in ("value", "unit", "seconds", "converged_steps", "attempted_steps", "rollouts_to_step_cap", "rollouts_stopped_infeasible", "mean_ipm_iters") if k in c5}
+            return r
+
+        def zeros_first():
+            r = start_order_leg(solver, dv, out, B, "zeros")
+            r["note"] = "obca_params.start_order = OBCA_START_ZEROS_FIRST: the reference's literal all-zero start first (src/obca.py:856) -- the default of rounds 1-3, kept for comparison"
+            return r
+
+        def c5_dodge_off():
+            c5 = closed_loop_c5(args.closed_loop_rollouts, dodge=False)
+            r = {k: c5[k] for k in ("value", "unit", "seconds", "converged_steps", "attempted_steps", "rollouts_to_step_cap", "rollouts_stopped_infeasible", "mean_ipm_iters") if k in c5}
+            r["note"] = ("obca_params.dodge = off (NOT the default): the ladder's last rung costs C5 a third of its launch and rescues ~20 of 4096 rollouts -- the launch lasts as long "
+                         "as its longest ROLLOUT (a serial chain of <= 30 steps), and the rescued rollouts, which need the rung again at every later step, are the longest "
+                         "(profiles/r06_c5_dodge.txt); the rung stays on because the reference's own demo11 run needs it (DESIGN.md section 2)")
+            return r
+        legs += [("config_c3", lambda: config_c3(B, classify=cpu, host=host)),
+                 ("closed_loop", lambda: closed_loop_c5(args.closed_loop_rollouts, classify=cpu,
+                                                        classify_max=None if args.classify_all else 48, host=host)),
+                 ("x0_first", x0_first_all),
+                 ("closed_loop_dodge_off", c5_dodge_off),
+                 ("open_loop", lambda: open_loop(classify=cpu)),
+                 ("reference_gif", reference_gif_leg),
+                 ("zeros_first", zeros_first),
+                 ("reference_report_figures", report_figures_leg),
+                 # the same loop with the three static obstacles only, at the batch size BASELINE.json quotes
+                 ("closed_loop_static", lambda: closed_loop_c5(B, n_dyn=0)),
+                 # optional extension, NOT reference behaviour (the reference cold-starts): shifted previous plan
+                 ("closed_loop_static_warm_start", lambda: closed_loop_c5(B, n_dyn=0, warm_start=0.1))]
+    leg_s = {}
+    for name, fn in legs:
+        t_leg = time.time()
+        try:
+            line[name] = fn()
+        except Exception as e:          # noqa: BLE001
+            line[name] = {"value": None, "error": repr(e)} if name.startswith("cpu_") else {"error": repr(e)}
+        leg_s[name] = round(time.time() - t_leg, 1)
+    t_wait = time.time()
+    finish_pending()
+    host.close()
+    leg_s["background_classifications_wait"] = round(time.time() - t_wait, 1)
+    if cpu and line.get("ipopt") == "unavailable" and isinstance(line.get("cpu_baseline"), dict):
+        line["cpu_baseline"]["note"] = "IPOPT unavailable (`import casadi` fails on this box); the reference publishes 3.7 s per solve at N=10 (src/simulation.py:231)"
+    line["leg_seconds"] = leg_s
+    if not args.classify_all:
+        line["classification_budget_seconds"] = args.budget_seconds
 
 
 if __name__ == "__main__":

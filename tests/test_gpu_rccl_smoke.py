@@ -17,7 +17,7 @@ def test_bench_under_torchrun_with_one_rank():
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", "29571", os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "0", "--batch", "1024",
-           "--no-cpu-baseline", "--closed-loop-rollouts", "64"]
+           "--full", "--no-cpu-baseline", "--closed-loop-rollouts", "64"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -39,7 +39,7 @@ def test_bench_under_torchrun_with_two_ranks():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):                 # a bare call: bench.py starts its two ranks itself
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0", "--batch", "1024",
-           "--no-cpu-baseline", "--closed-loop-rollouts", "64"]
+           "--full", "--no-cpu-baseline", "--closed-loop-rollouts", "64"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=1200)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
