@@ -383,6 +383,45 @@ int obca_astar_batch(const uint8_t* grid, int32_t B, int32_t rows, int32_t cols,
 int obca_rasterise_batch(const double* boxes, int32_t B, int32_t K, double resolution, int32_t rows, int32_t cols,
                          uint8_t* grid, void* hip_stream);
 
+/* ------------------------------------------------------------------------------------------------------
+ * Collision audit: true clearance in fp64 between the car footprint (ego as in obca_params: rectangle centre
+ * pose + R(theta)(off, 0), L = ego[0] + ego[2], W = ego[1] + ego[3], off = L/2 - ego[2]) and convex obstacles
+ * {q : A q <= b} given by their rows in edge order (one row: half-plane; two: wedge; three or more: polygon).  Signed
+ * distance: Euclidean distance when separated, minus the penetration depth (separating-axis value) when overlapping.
+ * Read-only: neither call writes solver or rollout state.  Every argument is checked before the first HIP call; a
+ * refused call (OBCA_E_INVAL) has no side effect.  Asynchronous on hip_stream.
+ *
+ * Plan clearance of obca_solve_batch outputs.  ego and m (n_obs entries, 1..OBCA_MAX_EDGES) are HOST pointers; the
+ * rest DEVICE pointers in obca_solve_batch's shapes: x [B,3,N+1], A [B,N+1,M,2], b [B,N+1,M], variant [B] or NULL.
+ * Where variant[b] == 4 every stage is measured against stage 0's rows (what obca_mpc4 reads); otherwise stage k
+ * against its own rows.  Outputs: min_clear [B], arg_stage [B], arg_obst [B] (ties to the lowest stage, then the
+ * lowest obstacle), stage_obst [B,N+1,n_obs] or NULL. */
+int obca_plan_clearance(const double ego[4], int32_t n_obs, const int32_t* m, int32_t N, int32_t B,
+                        const int32_t* variant, const double* x, const double* A, const double* b,
+                        double* min_clear, int32_t* arg_stage, int32_t* arg_obst, double* stage_obst,
+                        int32_t device, void* hip_stream);
+
+/* Rollout audit from the handle's own device state (after obca_rollouts_reset; ego and dmin of that reset).  Rollout
+ * b has the knots x_closed[b, 0..steps[b]]; interval s joins knot s to s + 1 (steps[b] == 0: knot 0 alone).  Within
+ * an interval the pose is interpolated linearly in (x, y, theta) and n_sub + 1 >= 2 samples, both knots included, are
+ * measured (n_sub = 1: the knots only).  Obstacles: the static rows of the reset and EVERY present moving box, sensed
+ * or not, at its recorded position (dyn_hist), moving linearly with heading and size fixed within an interval; the
+ * unrecorded last knot takes the harness's update law (advance by T_closed[s] * speed along the heading, appear at
+ * k == t_start); a box that appears at knot s + 1 counts from that knot on.  Obstacle indices: static i, then
+ * n_static + j for moving box j.  Outputs (DEVICE, [B] unless noted):
+ *   min_clear        smallest sampled signed distance;  arg_step / arg_obst: its interval and obstacle (lowest first)
+ *   lower_bound      certified lower bound of the signed distance over the continuous interpolated motion:
+ *                    min over sub-intervals of (d_j + d_j+1 - delta) / 2 with delta = |dp| + r_max |dtheta| + the
+ *                    largest |dc| of a moving box (r_max: pose point to farthest footprint corner; derivation in
+ *                    csrc/obca_audit_core.h)
+ *   first_collision  first interval with a sampled distance < 0, or -1
+ *   first_violation  first knot with a distance < dmin - 1e-6, or -1
+ *   step_min         [B,max_steps] or NULL: smallest sample per interval (+inf beyond the rollout's intervals) */
+int obca_rollouts_audit(obca_rollouts* r, int32_t n_sub,
+                        double* min_clear, double* lower_bound, int32_t* arg_step, int32_t* arg_obst,
+                        int32_t* first_collision, int32_t* first_violation,
+                        double* step_min, void* hip_stream);
+
 const char* obca_strerror(int code);
 /* "obca_mpc 0.6 (gfx950)": 0.6 = the answer of an exhausted start ladder is the most informative pass's (obca_params: the starts of a
  * solve), the second-order correction's scratch in LDS where it costs no occupancy; 0.5 = obca_params.struct_size (first member; obca_params_init), the dodge rung and the terminal-set screen,

@@ -56,7 +56,8 @@ EXPORTS = ("obca_create", "obca_destroy", "obca_solve_batch", "obca_lds_bytes", 
            "obca_set_profile_buffer", "obca_set_mode", "obca_set_two_sided_sweep", "obca_rollouts_create", "obca_rollouts_destroy", "obca_rollouts_debug_stats", "obca_rollouts_debug_harness",
            "obca_rollouts_reset", "obca_rollouts_step", "obca_rollouts_read", "obca_rollouts_run",
            "obca_rollouts_set_mode", "obca_rollouts_queue_mode", "obca_set_shape_specialisation", "obca_shape_is_specialised", "obca_astar_batch", "obca_astar_workspace_bytes", "obca_primal_size", "obca_set_warm_start",
-           "obca_rollouts_set_warm_start", "obca_dual_size", "obca_set_certificate_buffers", "obca_rasterise_batch")
+           "obca_rollouts_set_warm_start", "obca_dual_size", "obca_set_certificate_buffers", "obca_rasterise_batch",
+           "obca_plan_clearance", "obca_rollouts_audit")
 
 OBCA_MAX_DYN = 4
 RUN, DONE_GOAL, DONE_CAP, DONE_FAILED = 0, 1, 2, 3
@@ -157,6 +158,11 @@ def load():
     lib.obca_rollouts_set_warm_start.restype = ctypes.c_int
     lib.obca_rollouts_read.argtypes = [ctypes.c_void_p] + [vp] * 11
     lib.obca_rollouts_read.restype = ctypes.c_int
+    lib.obca_plan_clearance.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32,
+                                        ctypes.c_int32, i32p, vp, vp, vp, vp, i32p, i32p, vp, ctypes.c_int32, vp]
+    lib.obca_plan_clearance.restype = ctypes.c_int
+    lib.obca_rollouts_audit.argtypes = [ctypes.c_void_p, ctypes.c_int32, vp, vp, i32p, i32p, i32p, i32p, vp, vp]
+    lib.obca_rollouts_audit.restype = ctypes.c_int
     lib.obca_lds_bytes.argtypes = [ctypes.POINTER(ObcaDims)]
     lib.obca_lds_bytes.restype = ctypes.c_int64
     lib.obca_strerror.argtypes = [ctypes.c_int]

@@ -1,0 +1,69 @@
+"""Collision audit on the GPU: true clearance of batched plans and closed-loop rollouts, in fp64.
+
+``plan_clearance`` measures ``BatchSolver`` outputs against the rows the solver was given (obca_plan_clearance);
+``DeviceRollouts.audit`` / ``RolloutCohorts.audit`` measure closed-loop rollouts against the static obstacles and every
+present moving box, between the knots too (obca_rollouts_audit); ``summary`` turns an audit into counts.  Read-only: no
+solver or rollout state changes.  Geometry and the certified bound: csrc/obca_audit_core.h.
+"""
+import ctypes
+
+import numpy as np
+
+from . import _lib
+from .solver import DEFAULT_EGO
+
+
+def _device_tensor(a, dtype, device):
+    import torch
+    return torch.as_tensor(np.asarray(a) if not isinstance(a, torch.Tensor) else a, dtype=dtype, device=device).contiguous()
+
+
+def plan_clearance(x, A, b, m, ego=DEFAULT_EGO, variant=None, per_stage=False, device=None):
+    """x [B,3,N+1], A [B,N+1,M,2], b [B,N+1,M] (torch tensors or numpy arrays), m: rows per obstacle; variant [B] or None
+    (4: every stage against stage 0's rows, as obca_mpc4 reads them).  Returns a dict of device tensors on the current
+    stream: min_clear [B], arg_stage [B], arg_obst [B] and, with per_stage, stage_obst [B,N+1,n_obs]."""
+    import torch
+    dev = torch.device(device) if device is not None else (x.device if isinstance(x, torch.Tensor) and x.is_cuda else
+                                                           torch.device("cuda", torch.cuda.current_device()))
+    lib = _lib.load()
+    m = [int(v) for v in m]
+    x = _device_tensor(x, torch.float64, dev)
+    B, N1 = int(x.shape[0]), int(x.shape[2])
+    M = sum(m)
+    x = x.reshape(B, 3, N1)
+    A = _device_tensor(A, torch.float64, dev).reshape(B, N1, M, 2)
+    b = _device_tensor(b, torch.float64, dev).reshape(B, N1, M)
+    var = None if variant is None else _device_tensor(variant, torch.int32, dev).reshape(B)
+    out = {"min_clear": torch.empty(B, dtype=torch.float64, device=dev),
+           "arg_stage": torch.empty(B, dtype=torch.int32, device=dev),
+           "arg_obst": torch.empty(B, dtype=torch.int32, device=dev)}
+    if per_stage:
+        out["stage_obst"] = torch.empty(B, N1, len(m), dtype=torch.float64, device=dev)
+    p = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
+    ego_c = (ctypes.c_double * 4)(*[float(v) for v in ego])
+    m_c = (ctypes.c_int32 * max(len(m), 1))(*m)
+    stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    _lib.check(lib.obca_plan_clearance(ego_c, len(m), m_c, N1 - 1, B, p(var), p(x), p(A), p(b), p(out["min_clear"]),
+                                       p(out["arg_stage"]), p(out["arg_obst"]), p(out.get("stage_obst")),
+                                       dev.index if dev.index is not None else torch.cuda.current_device(), stream))
+    return out
+
+
+def summary(audit, dmin):
+    """counts and worst values of a rollout audit (DeviceRollouts.audit): rollouts with a sampled collision, with a knot
+    closer than dmin, with a sampled distance below dmin anywhere, with a negative certified lower bound"""
+    g = lambda k: np.asarray(audit[k].cpu() if hasattr(audit[k], "cpu") else audit[k])
+    mc, lb = g("min_clear"), g("lower_bound")
+    fc, fv = g("first_collision"), g("first_violation")
+    worst = int(np.argmin(mc))
+    return {"rollouts": int(len(mc)),
+            "collisions": int((fc >= 0).sum()),
+            "knot_violations": int((fv >= 0).sum()),
+            "below_dmin_sampled": int((mc < float(dmin) - 1e-6).sum()),
+            "negative_lower_bound": int((lb < 0).sum()),
+            "worst_min_clear": float(mc[worst]),
+            "worst_rollout": worst,
+            "worst_step": int(g("arg_step")[worst]),
+            "worst_obstacle": int(g("arg_obst")[worst]),
+            "worst_lower_bound": float(lb.min()),
+            "dmin": float(dmin)}

@@ -1,0 +1,255 @@
+// obca_audit.hip -- collision audit (obca_plan_clearance, obca_rollouts_audit of include/obca_mpc.h): true clearance of
+// batched plans and of closed-loop rollouts in fp64, from the geometry core csrc/obca_audit_core.h.  Read-only: the
+// kernels only read solver outputs and rollout state and write the caller's output buffers.
+//
+// Layout: the lanes of a wavefront are cut into segments of seg = next power of two >= the items of one instance (plan:
+// its N + 1 stages, rollout: its max_steps intervals; at most 64), one instance per segment; a lane walks the items
+// sub, sub + seg, ... of its instance (for a rollout: each interval's samples in order, both ends of every sub-interval
+// in registers), then the segment reduces min / arg-min with xor shuffles that never leave it.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include "obca_device.h"
+#include "obca_audit_core.h"
+
+// defined in obca_rollout.hip (internal, not part of the C ABI): the handle's device-state descriptor, its shape and the
+// parameters of its last obca_rollouts_reset; OBCA_E_INVAL when the handle has not been reset
+int obca_internal_rollouts_view(const obca_rollouts* r, rollout::Dev* D, obca_rollout_dims* dims, obca_params* params);
+
+namespace {
+
+constexpr int WAVE = 64;
+constexpr int BLOCK = 256;
+
+struct PlanArgs {
+    int32_t B, N, n_obs, M;
+    int32_t m[OBCA_MAX_OBST], off[OBCA_MAX_OBST];
+    double ego[4];
+    int32_t seg, log_seg;
+    const int32_t* variant;
+    const double *x, *A, *b;
+    double* min_clear;
+    int32_t *arg_stage, *arg_obst;
+    double* stage_obst;
+};
+
+struct AuditArgs {
+    rollout::Dev D;
+    int32_t n_static;
+    int32_t m[OBCA_MAX_OBST];
+    double ego[4];
+    double dmin;
+    int32_t n_sub, seg, log_seg;
+    double *min_clear, *lower_bound;
+    int32_t *arg_step, *arg_obst, *first_collision, *first_violation;
+    double* step_min;
+};
+
+// (value, step, obstacle) lexicographic: ties to the lowest step, then the lowest obstacle
+__device__ inline bool better(double v, int s, int o, double v2, int s2, int o2) {
+    return v < v2 || (v == v2 && (s < s2 || (s == s2 && o < o2)));
+}
+
+__device__ inline void seg_argmin(double& v, int& s, int& o, int seg) {
+    for (int w = seg >> 1; w > 0; w >>= 1) {
+        const double v2 = __shfl_xor(v, w, WAVE);
+        const int s2 = __shfl_xor(s, w, WAVE), o2 = __shfl_xor(o, w, WAVE);
+        if (better(v2, s2, o2, v, s, o)) { v = v2; s = s2; o = o2; }
+    }
+}
+
+__device__ inline double seg_min(double v, int seg) {
+    for (int w = seg >> 1; w > 0; w >>= 1) v = fmin(v, __shfl_xor(v, w, WAVE));
+    return v;
+}
+
+__device__ inline int seg_min_nonneg(int v, int seg) {        // smallest index >= 0, -1 if none
+    unsigned u = (unsigned)v;                                    // -1 -> UINT_MAX
+    for (int w = seg >> 1; w > 0; w >>= 1) {
+        const unsigned u2 = (unsigned)__shfl_xor((int)u, w, WAVE);
+        u = u2 < u ? u2 : u;
+    }
+    return (int)u;
+}
+
+__global__ void __launch_bounds__(BLOCK) plan_clearance_kernel(PlanArgs P) {
+    const int gl = blockIdx.x * blockDim.x + threadIdx.x;
+    const int inst = gl >> P.log_seg, sub = gl & (P.seg - 1);
+    const bool live = inst < P.B;                               // whole segments are live or not: the shuffles stay uniform
+    const int N1 = P.N + 1;
+    double best = INFINITY;
+    int bs = 0x7fffffff, bo = 0x7fffffff;
+    if (live) {
+        const int v = P.variant ? P.variant[inst] : 0;
+        for (int k = sub; k < N1; k += P.seg) {
+            const double* xb = P.x + (size_t)inst * 3 * N1;
+            double C[4][2];
+            audit::car_corners(xb[k], xb[N1 + k], xb[2 * N1 + k], P.ego, C);
+            const int ks = (v == 4) ? 0 : k;                       // obca_mpc4 reads stage 0's rows at every stage (q5)
+            const double* Ak = P.A + ((size_t)inst * N1 + ks) * P.M * 2;
+            const double* bk = P.b + ((size_t)inst * N1 + ks) * P.M;
+            for (int i = 0; i < P.n_obs; ++i) {
+                const double d = audit::signed_distance<OBCA_MAX_EDGES>(C, Ak + 2 * P.off[i], bk + P.off[i], P.m[i]);
+                if (P.stage_obst) P.stage_obst[((size_t)inst * N1 + k) * P.n_obs + i] = d;
+                if (better(d, k, i, best, bs, bo)) { best = d; bs = k; bo = i; }
+            }
+        }
+    }
+    seg_argmin(best, bs, bo, P.seg);
+    if (live && sub == 0) {
+        P.min_clear[inst] = best;
+        P.arg_stage[inst] = bs;
+        P.arg_obst[inst] = bo;
+    }
+}
+
+// boxes of rollout b at knot kn: the recorded history where the harness recorded it, else the harness's update law
+// from the previous knot (the last knot), else (knot 0 of a rollout that never stepped) the tuple itself
+__device__ inline void boxes_at(const AuditArgs& G, int b, int kn, int steps, int flags, double box[OBCA_MAX_DYN][3]) {
+    const rollout::Dev& D = G.D;
+    const int nd = D.n_dyn, S = D.S;
+    const bool recorded = kn < steps || (kn == steps && flags == OBCA_DONE_FAILED && kn < S);
+    for (int i = 0; i < nd; ++i) {
+        const double* info = D.dyn + ((size_t)b * nd + i) * rollout::DYN_W;
+        if (recorded) {
+            const double* rec = D.dh + (((size_t)b * S + kn) * nd + i) * 4;
+            box[i][0] = rec[0]; box[i][1] = rec[1]; box[i][2] = rec[2];
+        } else if (kn >= 1) {
+            const double* rec = D.dh + (((size_t)b * S + kn - 1) * nd + i) * 4;
+            audit::box_next_knot(info, rec[0], rec[1], kn, D.Tc[(size_t)b * S + kn - 1], box[i]);
+        } else {
+            box[i][0] = info[0]; box[i][1] = info[1]; box[i][2] = (0.0 >= info[9]) ? 1.0 : 0.0;
+        }
+    }
+}
+
+__global__ void __launch_bounds__(BLOCK) rollouts_audit_kernel(AuditArgs G) {
+    const rollout::Dev& D = G.D;
+    const int gl = blockIdx.x * blockDim.x + threadIdx.x;
+    const int b = gl >> G.log_seg, sub = gl & (G.seg - 1);
+    const bool live = b < D.B;
+    const int S = D.S;
+    double best = INFINITY, lower = INFINITY;
+    int bs = 0x7fffffff, bo = 0x7fffffff, coll = -1, viol = -1;
+    if (live) {
+        int steps = D.k[b];
+        steps = steps < 0 ? 0 : (steps > S ? S : steps);
+        const int flags = D.flags[b];
+        const int n_int = steps > 0 ? steps : 1;
+        audit::Scene sc;
+        sc.ego = G.ego;
+        sc.n_static = G.n_static;
+        sc.m = G.m;
+        sc.As = D.As + (size_t)b * D.Ms * 2;
+        sc.bs = D.bs + (size_t)b * D.Ms;
+        sc.nd = D.n_dyn;
+        sc.dyn = D.dyn + (size_t)b * D.n_dyn * rollout::DYN_W;
+        const double viol_at = G.dmin - audit::VIOL_TOL;
+        for (int s = sub; s < S; s += G.seg) {
+            if (s >= n_int) {
+                if (G.step_min) G.step_min[(size_t)b * S + s] = INFINITY;
+                continue;
+            }
+            const bool single = steps == 0;
+            const double* p0 = D.xc + ((size_t)b * (S + 1) + s) * 3;
+            const double* p1 = single ? p0 : p0 + 3;
+            double b0[OBCA_MAX_DYN][3], b1[OBCA_MAX_DYN][3];
+            boxes_at(G, b, s, steps, flags, b0);
+            if (single) {
+                for (int i = 0; i < D.n_dyn; ++i) for (int q = 0; q < 3; ++q) b1[i][q] = b0[i][q];
+            } else {
+                boxes_at(G, b, s + 1, steps, flags, b1);
+            }
+            const audit::IntervalResult R = audit::audit_interval<OBCA_MAX_EDGES>(sc, p0, p1, b0, b1, single ? 0 : G.n_sub);
+            if (G.step_min) G.step_min[(size_t)b * S + s] = R.min_val;
+            if (better(R.min_val, s, R.min_obst, best, bs, bo)) { best = R.min_val; bs = s; bo = R.min_obst; }
+            lower = fmin(lower, R.lower);
+            if (coll < 0 && R.min_val < 0.0) coll = s;
+            if (viol < 0 && R.d0 < viol_at) viol = s;
+            if (viol < 0 && !single && s + 1 == n_int && R.d1 < viol_at) viol = s + 1;
+        }
+    }
+    seg_argmin(best, bs, bo, G.seg);
+    lower = seg_min(lower, G.seg);
+    coll = seg_min_nonneg(coll, G.seg);
+    viol = seg_min_nonneg(viol, G.seg);
+    if (live && sub == 0) {
+        G.min_clear[b] = best;
+        G.lower_bound[b] = lower;
+        G.arg_step[b] = bs;
+        G.arg_obst[b] = bo;
+        G.first_collision[b] = coll;
+        G.first_violation[b] = viol;
+    }
+}
+
+void segment_of(int items, int32_t* seg, int32_t* log_seg) {
+    int s = 1, l = 0;
+    while (s < items && s < WAVE) { s <<= 1; ++l; }
+    *seg = s; *log_seg = l;
+}
+
+bool ego_ok(const double* ego) {
+    if (!ego) return false;
+    for (int j = 0; j < 4; ++j)
+        if (!isfinite(ego[j])) return false;
+    return ego[0] + ego[2] > 0.0 && ego[1] + ego[3] > 0.0;
+}
+
+}  // namespace
+
+extern "C" int obca_plan_clearance(const double ego[4], int32_t n_obs, const int32_t* m, int32_t N, int32_t B,
+                                   const int32_t* variant, const double* x, const double* A, const double* b,
+                                   double* min_clear, int32_t* arg_stage, int32_t* arg_obst, double* stage_obst,
+                                   int32_t device, void* hip_stream) {
+    // every argument is checked before the first HIP call: a refused call has no side effect
+    if (!ego_ok(ego) || n_obs < 1 || n_obs > OBCA_MAX_OBST || !m || N < 1 || N > (1 << 20) || B < 1 || device < 0 ||
+        !x || !A || !b || !min_clear || !arg_stage || !arg_obst)
+        return OBCA_E_INVAL;
+    PlanArgs P;
+    P.M = 0;
+    for (int i = 0; i < n_obs; ++i) {
+        if (m[i] < 1 || m[i] > OBCA_MAX_EDGES) return OBCA_E_INVAL;
+        P.m[i] = m[i];
+        P.off[i] = P.M;
+        P.M += m[i];
+    }
+    P.B = B; P.N = N; P.n_obs = n_obs;
+    for (int j = 0; j < 4; ++j) P.ego[j] = ego[j];
+    segment_of(N + 1, &P.seg, &P.log_seg);
+    P.variant = variant; P.x = x; P.A = A; P.b = b;
+    P.min_clear = min_clear; P.arg_stage = arg_stage; P.arg_obst = arg_obst; P.stage_obst = stage_obst;
+    ObcaDeviceGuard guard(device);
+    if (!guard.ok) return OBCA_E_HIP;
+    const int64_t lanes = (int64_t)B * P.seg;
+    hipLaunchKernelGGL(plan_clearance_kernel, dim3((unsigned)((lanes + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0,
+                       (hipStream_t)hip_stream, P);
+    return hipGetLastError() == hipSuccess ? OBCA_OK : OBCA_E_HIP;
+}
+
+extern "C" int obca_rollouts_audit(obca_rollouts* r, int32_t n_sub, double* min_clear, double* lower_bound,
+                                   int32_t* arg_step, int32_t* arg_obst, int32_t* first_collision,
+                                   int32_t* first_violation, double* step_min, void* hip_stream) {
+    if (!r || n_sub < 1 || n_sub > (1 << 16) || !min_clear || !lower_bound || !arg_step || !arg_obst || !first_collision ||
+        !first_violation)
+        return OBCA_E_INVAL;
+    AuditArgs G;
+    obca_rollout_dims dims;
+    obca_params prm;
+    const int rc = obca_internal_rollouts_view(r, &G.D, &dims, &prm);       // host-side copy; no HIP call
+    if (rc != OBCA_OK) return rc;
+    if (!ego_ok(prm.ego) || !(prm.dmin == prm.dmin)) return OBCA_E_INVAL;
+    G.n_static = dims.n_static;
+    for (int i = 0; i < OBCA_MAX_OBST; ++i) G.m[i] = i < dims.n_static ? dims.m_static[i] : 0;
+    for (int j = 0; j < 4; ++j) G.ego[j] = prm.ego[j];
+    G.dmin = prm.dmin;
+    G.n_sub = n_sub;
+    segment_of(G.D.S, &G.seg, &G.log_seg);
+    G.min_clear = min_clear; G.lower_bound = lower_bound; G.arg_step = arg_step; G.arg_obst = arg_obst;
+    G.first_collision = first_collision; G.first_violation = first_violation; G.step_min = step_min;
+    ObcaDeviceGuard guard(dims.device);
+    if (!guard.ok) return OBCA_E_HIP;
+    const int64_t lanes = (int64_t)G.D.B * G.seg;
+    hipLaunchKernelGGL(rollouts_audit_kernel, dim3((unsigned)((lanes + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0,
+                       (hipStream_t)hip_stream, G);
+    return hipGetLastError() == hipSuccess ? OBCA_OK : OBCA_E_HIP;
+}

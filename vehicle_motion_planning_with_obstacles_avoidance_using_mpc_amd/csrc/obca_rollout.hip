@@ -415,3 +415,13 @@ extern "C" int obca_rollouts_read(obca_rollouts* r, double* x_closed, double* u_
                          hipStreamSynchronize(s) != hipSuccess)) return OBCA_E_HIP;
     return aborted ? OBCA_E_HIP : OBCA_OK;
 }
+
+// internal (not part of the C ABI): what the collision audit (obca_audit.hip) reads -- the device-state descriptor, the shape
+// and the parameters of the last obca_rollouts_reset.  Host-side copies only.
+int obca_internal_rollouts_view(const obca_rollouts* r, rollout::Dev* D, obca_rollout_dims* dims, obca_params* params) {
+    if (!r || !r->ready || !D || !dims || !params) return OBCA_E_INVAL;
+    *D = r->D;
+    *dims = r->dims;
+    *params = r->params;
+    return OBCA_OK;
+}

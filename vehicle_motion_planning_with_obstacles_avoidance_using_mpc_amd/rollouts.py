@@ -158,6 +158,13 @@ class RolloutCohorts:
             st.synchronize()
         return {k: self.torch.cat([o[k] for o in outs]) for k in outs[0]}
 
+    def audit(self, n_sub=8, per_step=False):
+        """DeviceRollouts.audit of every cohort, concatenated in batch order"""
+        outs = self._each(lambda p: p.audit(n_sub, per_step))
+        for st in self.streams:
+            st.synchronize()
+        return {k: self.torch.cat([o[k] for o in outs]) for k in outs[0]}
+
 
 class DeviceRollouts:
     """B rollouts on one GPU.  ``step()`` enqueues one receding-horizon step of every running rollout;
@@ -234,6 +241,22 @@ class DeviceRollouts:
         order = ("x_closed", "u_closed", "T_closed", "x_openloop", "variant", "iters", "status", "dyn", "steps", "flags")
         ptrs = [ctypes.c_void_p(out[k].data_ptr()) if (k != "dyn" or nd) else None for k in order]
         _lib.check(self.lib.obca_rollouts_read(self._h, *ptrs, self._stream()))
+        return out
+
+    def audit(self, n_sub=8, per_step=False):
+        """collision audit of the rollouts' current state (obca_rollouts_audit; read-only): dict of device tensors on the
+        current stream -- min_clear, lower_bound [B] float64; arg_step, arg_obst, first_collision, first_violation [B] int32;
+        with per_step, step_min [B,max_steps] (+inf beyond a rollout's intervals).  n_sub + 1 samples per interval."""
+        t, B = self.torch, self.w.batch
+        f = lambda *shape: t.empty(*shape, dtype=t.float64, device=self.device)
+        i = lambda *shape: t.empty(*shape, dtype=t.int32, device=self.device)
+        out = {"min_clear": f(B), "lower_bound": f(B), "arg_step": i(B), "arg_obst": i(B), "first_collision": i(B),
+               "first_violation": i(B)}
+        if per_step:
+            out["step_min"] = f(B, self.max_steps)
+        order = ("min_clear", "lower_bound", "arg_step", "arg_obst", "first_collision", "first_violation", "step_min")
+        ptrs = [ctypes.c_void_p(out[k].data_ptr()) if k in out else None for k in order]
+        _lib.check(self.lib.obca_rollouts_audit(self._h, int(n_sub), *ptrs, self._stream()))
         return out
 
     def debug_harness(self, k, Ts_opt, x0=None, g=0):
