@@ -301,7 +301,7 @@ typedef struct obca_rollout_dims {
 typedef struct obca_rollouts obca_rollouts;
 
 /* rollout flags */
-enum { OBCA_RUN = 0, OBCA_DONE_GOAL = 1, OBCA_DONE_CAP = 2, OBCA_DONE_FAILED = 3 };
+enum { OBCA_RUN = 0, OBCA_DONE_GOAL = 1, OBCA_DONE_CAP = 2, OBCA_DONE_FAILED = 3, OBCA_DONE_COLLISION = 4 };
 
 int obca_rollouts_create(const obca_rollout_dims* dims, obca_rollouts** out);
 void obca_rollouts_destroy(obca_rollouts* r);
@@ -348,6 +348,22 @@ int obca_rollouts_debug_harness(obca_rollouts* r, int32_t k, double Ts_opt, cons
  * starts from the previous plan moved one stage forward with barrier parameter mu_init.  Call before
  * obca_rollouts_reset; enable = 0 restores the reference's cold starts. */
 int obca_rollouts_set_warm_start(obca_rollouts* r, int enable, double mu_init);
+
+/* Optional collision stop (obca_mpc 0.7), the simulator's contact check -- NOT what the controller knows: after every
+ * applied step k, interval k (knot k -> k + 1) is measured exactly as obca_rollouts_audit measures it (static rows and
+ * EVERY present moving box, sensed or not; n_sub + 1 samples).  Its smallest sample (certified = 1: the certified lower
+ * bound) is recorded; below `clearance` (metres) the rollout ends with OBCA_DONE_COLLISION, which wins over GOAL / CAP
+ * of the same step.  The colliding step stays in the history: a stopped rollout's history equals the unstopped one's
+ * cut after steps = first collision + 1.  n_sub = 0: off (default); else 1..63.  clearance finite, certified 0 / 1;
+ * anything else: OBCA_E_INVAL without side effect.  Call before obca_rollouts_reset, like obca_rollouts_set_warm_start. */
+int obca_rollouts_set_collision_stop(obca_rollouts* r, int32_t n_sub, double clearance, int32_t certified);
+/* Optional, NOT reference behaviour: on = 1 hands the solver the j-th SENSED box's own rectangle, moved with its own
+ * velocity; on = 0 (default) keeps the reference's sensor pairing (the j-th PRESENT box's rectangle with the j-th sensed
+ * box's velocity).  Same problem shapes either way.  on outside {0, 1}: OBCA_E_INVAL.  Call before obca_rollouts_reset. */
+int obca_rollouts_set_exact_sensing(obca_rollouts* r, int32_t on);
+/* Clearance history of the collision stop to a caller-owned DEVICE buffer clear_hist [B,max_steps]: the measured value
+ * of every interval the stop evaluated, +inf elsewhere (stop off, or beyond the rollout's steps).  Asynchronous. */
+int obca_rollouts_read_clearance(obca_rollouts* r, double* clear_hist, void* hip_stream);
 
 /* Copy state and history to caller-owned DEVICE buffers (any may be NULL): x_closed [B,max_steps+1,3],
  * u_closed [B,max_steps,2], T_closed [B,max_steps], x_openloop [B,max_steps,3,max(N,N_fix)+1] (a free-time
@@ -423,7 +439,8 @@ int obca_rollouts_audit(obca_rollouts* r, int32_t n_sub,
                         double* step_min, void* hip_stream);
 
 const char* obca_strerror(int code);
-/* "obca_mpc 0.6 (gfx950)": 0.6 = the answer of an exhausted start ladder is the most informative pass's (obca_params: the starts of a
+/* "obca_mpc 0.7 (gfx950)": 0.7 = opt-in collision stop (OBCA_DONE_COLLISION, obca_rollouts_set_collision_stop,
+ * obca_rollouts_read_clearance) and exact sensing (obca_rollouts_set_exact_sensing); 0.6 = the answer of an exhausted start ladder is the most informative pass's (obca_params: the starts of a
  * solve), the second-order correction's scratch in LDS where it costs no occupancy; 0.5 = obca_params.struct_size (first member; obca_params_init), the dodge rung and the terminal-set screen,
  * OBCA_START_DEFAULT = the window first for obca_mpc4 too, kernel mode 5;
  * 0.2 = the start ladder (start_order / single_start / patience / retry_iter replace restart); 0.3 = second

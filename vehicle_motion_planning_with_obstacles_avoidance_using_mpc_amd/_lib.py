@@ -57,10 +57,12 @@ EXPORTS = ("obca_create", "obca_destroy", "obca_solve_batch", "obca_lds_bytes", 
            "obca_rollouts_reset", "obca_rollouts_step", "obca_rollouts_read", "obca_rollouts_run",
            "obca_rollouts_set_mode", "obca_rollouts_queue_mode", "obca_set_shape_specialisation", "obca_shape_is_specialised", "obca_astar_batch", "obca_astar_workspace_bytes", "obca_primal_size", "obca_set_warm_start",
            "obca_rollouts_set_warm_start", "obca_dual_size", "obca_set_certificate_buffers", "obca_rasterise_batch",
-           "obca_plan_clearance", "obca_rollouts_audit")
+           "obca_plan_clearance", "obca_rollouts_audit", "obca_rollouts_set_collision_stop", "obca_rollouts_set_exact_sensing",
+           "obca_rollouts_read_clearance")
 
 OBCA_MAX_DYN = 4
-RUN, DONE_GOAL, DONE_CAP, DONE_FAILED = 0, 1, 2, 3
+RUN, DONE_GOAL, DONE_CAP, DONE_FAILED, DONE_COLLISION = 0, 1, 2, 3, 4
+FLAG_NAMES = {RUN: "run", DONE_GOAL: "goal", DONE_CAP: "cap", DONE_FAILED: "failed", DONE_COLLISION: "collision"}
 STATUS_SKIPPED = -5
 STATUS_BAD_VARIANT = -6
 
@@ -163,6 +165,12 @@ def load():
     lib.obca_plan_clearance.restype = ctypes.c_int
     lib.obca_rollouts_audit.argtypes = [ctypes.c_void_p, ctypes.c_int32, vp, vp, i32p, i32p, i32p, i32p, vp, vp]
     lib.obca_rollouts_audit.restype = ctypes.c_int
+    lib.obca_rollouts_set_collision_stop.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_double, ctypes.c_int32]
+    lib.obca_rollouts_set_collision_stop.restype = ctypes.c_int
+    lib.obca_rollouts_set_exact_sensing.argtypes = [ctypes.c_void_p, ctypes.c_int32]
+    lib.obca_rollouts_set_exact_sensing.restype = ctypes.c_int
+    lib.obca_rollouts_read_clearance.argtypes = [ctypes.c_void_p, vp, vp]
+    lib.obca_rollouts_read_clearance.restype = ctypes.c_int
     lib.obca_lds_bytes.argtypes = [ctypes.POINTER(ObcaDims)]
     lib.obca_lds_bytes.restype = ctypes.c_int64
     lib.obca_strerror.argtypes = [ctypes.c_int]

@@ -187,11 +187,31 @@ struct Scene {
     const double* dyn;                 // [nd,13] tuples (heading cos / sin at 11, 12; length 3, width 4)
 };
 
-// smallest signed distance over the scene at pose p with the moving boxes at box[j] = (cx, cy, on); arg = obstacle index
-// (static first, then n_static + j; ties to the lowest)
+// Sample j (0..n_sub, both knots included) of one closed-loop interval: poses p0 -> p1 interpolated linearly in
+// (x, y, theta), boxes b0 -> b1 (cx, cy, present at the two knots; a box present at both ends moves linearly, one present
+// only at b1 counts at the end knot only).  n_sub == 0: the single knot p0 / b0.  Every function below evaluates sample j
+// from the interval's ends alone, so that a serial loop over the samples and one lane per sample compute the same words.
+AU_FN void sample_pose(const double* p0, const double* p1, int n_sub, int j, double p[3]) {
+    const bool first = j == 0, last = j == n_sub;
+    const double t = n_sub > 0 ? (double)j / (double)n_sub : 0.0;
+    for (int q = 0; q < 3; ++q) p[q] = first ? p0[q] : (last ? p1[q] : p0[q] + t * (p1[q] - p0[q]));
+}
+
+AU_FN void sample_box(const double (*b0)[3], const double (*b1)[3], int n_sub, int j, int i, double* cx, double* cy, double* on) {
+    const bool first = j == 0, last = j == n_sub;
+    const double t = n_sub > 0 ? (double)j / (double)n_sub : 0.0;
+    if (first) { *cx = b0[i][0]; *cy = b0[i][1]; *on = b0[i][2]; }
+    else if (last) { *cx = b1[i][0]; *cy = b1[i][1]; *on = b1[i][2]; }
+    else { *cx = b0[i][0] + t * (b1[i][0] - b0[i][0]); *cy = b0[i][1] + t * (b1[i][1] - b0[i][1]); *on = b0[i][2]; }
+}
+
+// smallest signed distance over the scene at sample j; arg = obstacle index (static first, then n_static + j; ties to the
+// lowest)
 template <int MAXM>
-AU_FN double scene_distance(const Scene& S, const double* p, const double (*box)[3], int* arg) {
-    double C[4][2];
+AU_FN double sample_distance(const Scene& S, const double* p0, const double* p1, const double (*b0)[3], const double (*b1)[3],
+                             int n_sub, int j, int* arg) {
+    double p[3], C[4][2];
+    sample_pose(p0, p1, n_sub, j, p);
     car_corners(p[0], p[1], p[2], S.ego, C);
     double best = INFINITY;
     int ai = -1, off = 0;
@@ -200,14 +220,38 @@ AU_FN double scene_distance(const Scene& S, const double* p, const double (*box)
         off += S.m[i];
         if (d < best) { best = d; ai = i; }
     }
-    for (int j = 0; j < S.nd; ++j) {
-        if (box[j][2] == 0.0) continue;
-        const double* info = S.dyn + (size_t)j * rollout::DYN_W;
-        const double d = box_distance(C, box[j][0], box[j][1], info[11], info[12], info[3], info[4]);
-        if (d < best) { best = d; ai = S.n_static + j; }
+    for (int i = 0; i < S.nd && i < OBCA_MAX_DYN; ++i) {
+        double cx, cy, on;
+        sample_box(b0, b1, n_sub, j, i, &cx, &cy, &on);
+        if (on == 0.0) continue;
+        const double* info = S.dyn + (size_t)i * rollout::DYN_W;
+        const double d = box_distance(C, cx, cy, info[11], info[12], info[3], info[4]);
+        if (d < best) { best = d; ai = S.n_static + i; }
     }
     *arg = ai;
     return best;
+}
+
+// the certified bound of sub-interval j-1 -> j (j >= 1) from its end distances d_prev, d: the displacement bound delta of
+// the car (|dp| + rmax |dtheta|) plus the largest move of a box present at both knots, then
+// min((d_prev + d - delta) / 2, d_prev, d)
+AU_FN double sub_bound(const Scene& S, const double* p0, const double* p1, const double (*b0)[3], const double (*b1)[3],
+                       int n_sub, int j, double rmax, double d_prev, double d) {
+    double p[3], pp[3];
+    sample_pose(p0, p1, n_sub, j, p);
+    sample_pose(p0, p1, n_sub, j - 1, pp);
+    double dc = 0.0;
+    for (int i = 0; i < S.nd && i < OBCA_MAX_DYN; ++i) {
+        if (!(b0[i][2] != 0.0 && b1[i][2] != 0.0)) continue;
+        double cx, cy, cpx, cpy, on;
+        sample_box(b0, b1, n_sub, j, i, &cx, &cy, &on);
+        sample_box(b0, b1, n_sub, j - 1, i, &cpx, &cpy, &on);
+        const double ux = cx - cpx, uy = cy - cpy;
+        dc = dmax(dc, sqrt(ux * ux + uy * uy));
+    }
+    const double ux = p[0] - pp[0], uy = p[1] - pp[1];
+    const double delta = sqrt(ux * ux + uy * uy) + rmax * fabs(p[2] - pp[2]) + dc;
+    return dmin_((d_prev + d - delta) / 2, dmin_(d_prev, d));
 }
 
 struct IntervalResult {
@@ -217,49 +261,21 @@ struct IntervalResult {
     double d0, d1;                     // distance at the two knots
 };
 
-// one closed-loop interval: poses p0 -> p1 interpolated linearly in (x, y, theta), boxes b0 -> b1 (a box present at
-// both ends moves linearly; one present only at b1 counts at the end knot only), n_sub + 1 samples, both knots included.
-// n_sub == 0: the single knot p0 / b0 (a rollout without steps).
+// one closed-loop interval, n_sub + 1 samples in order (sample_distance / sub_bound above)
 template <int MAXM>
 AU_FN IntervalResult audit_interval(const Scene& S, const double* p0, const double* p1, const double (*b0)[3],
                                     const double (*b1)[3], int n_sub) {
-    constexpr int MD = OBCA_MAX_DYN;
     const double rmax = car_radius(S.ego);
     IntervalResult R;
-    double prev_p[3], prev_c[MD][2], box[MD][3], p[3];
     double prev_d = 0.0;
     int arg;
     R.min_val = INFINITY; R.min_obst = -1; R.min_sub = 0; R.lower = INFINITY; R.d0 = R.d1 = 0.0;
     for (int j = 0; j <= n_sub; ++j) {
-        const bool first = j == 0, last = j == n_sub;
-        const double t = n_sub > 0 ? (double)j / (double)n_sub : 0.0;
-        for (int q = 0; q < 3; ++q) p[q] = first ? p0[q] : (last ? p1[q] : p0[q] + t * (p1[q] - p0[q]));
-        double dc = 0.0;
-        for (int i = 0; i < S.nd && i < MD; ++i) {
-            const bool both = b0[i][2] != 0.0 && b1[i][2] != 0.0;
-            if (first) { box[i][0] = b0[i][0]; box[i][1] = b0[i][1]; box[i][2] = b0[i][2]; }
-            else if (last) { box[i][0] = b1[i][0]; box[i][1] = b1[i][1]; box[i][2] = b1[i][2]; }
-            else {
-                box[i][0] = b0[i][0] + t * (b1[i][0] - b0[i][0]);
-                box[i][1] = b0[i][1] + t * (b1[i][1] - b0[i][1]);
-                box[i][2] = b0[i][2];
-            }
-            if (!first && both) {
-                const double ux = box[i][0] - prev_c[i][0], uy = box[i][1] - prev_c[i][1];
-                dc = dmax(dc, sqrt(ux * ux + uy * uy));
-            }
-            prev_c[i][0] = box[i][0]; prev_c[i][1] = box[i][1];
-        }
-        const double d = scene_distance<MAXM>(S, p, box, &arg);
+        const double d = sample_distance<MAXM>(S, p0, p1, b0, b1, n_sub, j, &arg);
         if (d < R.min_val) { R.min_val = d; R.min_obst = arg; R.min_sub = j; }
-        if (first) R.d0 = d;
-        if (last) R.d1 = d;
-        if (!first) {
-            const double ux = p[0] - prev_p[0], uy = p[1] - prev_p[1];
-            const double delta = sqrt(ux * ux + uy * uy) + rmax * fabs(p[2] - prev_p[2]) + dc;
-            R.lower = dmin_(R.lower, dmin_((prev_d + d - delta) / 2, dmin_(prev_d, d)));
-        }
-        for (int q = 0; q < 3; ++q) prev_p[q] = p[q];
+        if (j == 0) R.d0 = d;
+        if (j == n_sub) R.d1 = d;
+        if (j > 0) R.lower = dmin_(R.lower, sub_bound(S, p0, p1, b0, b1, n_sub, j, rmax, prev_d, d));
         prev_d = d;
     }
     if (n_sub == 0) R.lower = R.min_val;
@@ -267,4 +283,94 @@ AU_FN IntervalResult audit_interval(const Scene& S, const double* p0, const doub
 }
 
 }  // namespace audit
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Collision stop of the closed loop (obca_rollouts_set_collision_stop): the simulator's contact check, NOT the controller's
+// knowledge -- every present moving box counts, sensed or not.  After finish() has applied step k of rollout b, interval
+// k (knot k -> k + 1) is measured with exactly the inputs and rules of the rollout audit (obca_audit.hip): poses from
+// x_closed, the boxes at knot k from the dyn_hist record, at knot k + 1 from the harness's update law with T_closed[k],
+// the static rows, n_sub + 1 samples.  The sampled minimum (stop_certified: the certified lower bound) goes to clr[b, k];
+// below stop_clear the rollout ends with OBCA_DONE_COLLISION, which wins over GOAL / CAP of the same step.  The colliding
+// step stays in the history: a stopped rollout's history is the unstopped one's, cut after that step.
+namespace rollout {
+
+// the interval of the step finish() has just applied to rollout b, or -1 (the stop is off, the rollout did not run this
+// step -- prepare() zeroes var[.][b] of a rollout that is not running -- or its step failed and applied nothing).  Leaves
+// the boxes at the two knots (cx, cy, present) in rollout b's vtx row: b0 = row[0 .. 3 nd), b1 = row[12 .. 12 + 3 nd)
+// (prepare()'s scratch, free after it)
+AU_FN int stop_interval(const Dev& D, int b) {
+    if (D.stop_nsub <= 0 || D.var[D.sel[b]][b] == 0 || D.flags[b] == OBCA_DONE_FAILED) return -1;
+    const int k = D.k[b] - 1, nd = D.n_dyn;
+    if (k < 0) return -1;
+    double* row = D.vtx + (size_t)b * OBCA_MAX_DYN * 8;
+    const double T = D.Tc[(size_t)b * D.S + k];
+    for (int i = 0; i < nd; ++i) {
+        const double* rec = D.dh + (((size_t)b * D.S + k) * nd + i) * 4;
+        const double* info = D.dyn + ((size_t)b * nd + i) * DYN_W;
+        row[3 * i] = rec[0]; row[3 * i + 1] = rec[1]; row[3 * i + 2] = rec[2];
+        audit::box_next_knot(info, rec[0], rec[1], k + 1, T, row + 3 * OBCA_MAX_DYN + 3 * i);
+    }
+    return k;
+}
+
+AU_FN audit::Scene stop_scene(const Dev& D, int b) {
+    audit::Scene sc;
+    sc.ego = D.ego;
+    sc.n_static = D.n_static;
+    sc.m = D.m_static;
+    sc.As = D.As + (size_t)b * D.Ms * 2;
+    sc.bs = D.bs + (size_t)b * D.Ms;
+    sc.nd = D.n_dyn;
+    sc.dyn = D.dyn + (size_t)b * D.n_dyn * DYN_W;
+    return sc;
+}
+
+AU_FN void stop_apply(const Dev& D, int b, int k, double v) {
+    D.clr[(size_t)b * D.S + k] = v;
+    if (v < D.stop_clear) D.flags[b] = OBCA_DONE_COLLISION;
+}
+
+// serial form: one lane (host build, lock-step kernel) runs the samples in order
+AU_FN void stop_check(const Dev& D, int b) {
+    const int k = stop_interval(D, b);
+    if (k < 0) return;
+    const double* row = D.vtx + (size_t)b * OBCA_MAX_DYN * 8;
+    const double* p0 = D.xc + ((size_t)b * (D.S + 1) + k) * 3;
+    const audit::IntervalResult R = audit::audit_interval<OBCA_MAX_EDGES>(
+        stop_scene(D, b), p0, p0 + 3, reinterpret_cast<const double (*)[3]>(row),
+        reinterpret_cast<const double (*)[3]>(row + 3 * OBCA_MAX_DYN), D.stop_nsub);
+    stop_apply(D, b, k, D.stop_certified ? R.lower : R.min_val);
+}
+
+#if defined(__HIPCC__)
+// wavefront form (fused kernel; lock-step stop kernel): called by all 64 lanes of a one-wave workgroup with the same b.
+// Lane j <= n_sub evaluates sample j and the bound of sub-interval j-1 -> j (d_j-1 from lane j-1); min-reductions across
+// the lanes.  Same expressions as the serial loop and min is exact: the same words.
+__device__ inline void stop_check_wave(const Dev& D, int b) {
+    const int lane = threadIdx.x;
+    int k = -1;
+    if (lane == 0) k = stop_interval(D, b);
+    __syncthreads();                                   // the vtx row written by lane 0
+    k = __builtin_amdgcn_readfirstlane(k);
+    if (k < 0) return;
+    const int n = D.stop_nsub;
+    const double* row = D.vtx + (size_t)b * OBCA_MAX_DYN * 8;
+    const double (*b0)[3] = reinterpret_cast<const double (*)[3]>(row);
+    const double (*b1)[3] = reinterpret_cast<const double (*)[3]>(row + 3 * OBCA_MAX_DYN);
+    const double* p0 = D.xc + ((size_t)b * (D.S + 1) + k) * 3;
+    const audit::Scene sc = stop_scene(D, b);
+    double d = INFINITY, term = INFINITY;
+    int arg;
+    if (lane <= n) d = audit::sample_distance<OBCA_MAX_EDGES>(sc, p0, p0 + 3, b0, b1, n, lane, &arg);
+    const double d_prev = __shfl_up(d, 1, 64);
+    if (lane >= 1 && lane <= n) term = audit::sub_bound(sc, p0, p0 + 3, b0, b1, n, lane, audit::car_radius(sc.ego), d_prev, d);
+    for (int w = 32; w > 0; w >>= 1) {
+        d = audit::dmin_(d, __shfl_xor(d, w, 64));
+        term = audit::dmin_(term, __shfl_xor(term, w, 64));
+    }
+    if (lane == 0) stop_apply(D, b, k, D.stop_certified ? term : d);
+}
+#endif
+
+}  // namespace rollout
 #endif

@@ -2686,11 +2686,17 @@ extern "C" __global__ void __launch_bounds__(64) obca_ipm_kernel_gm1(ObcaLaunch 
 // obca_mpc6 runs to max_iter before the fallback) does not hold the others back.  `launches[g + a*MAX_GROUPS]`
 // is the descriptor obca_solve_batch would use for problem shape g (= sensed moving obstacles), a = 1 the retry.
 #include "obca_rollout_core.h"
+#include "obca_audit_core.h"
 
 // The harness runs once per step on lane 0; kept OUT of line so that nothing of it (the ~100 pointers of rollout::Dev,
 // its vertex arrays) is hoisted out of the step loop and kept alive in registers across the solve.
 __device__ __noinline__ void ro_prepare(const rollout::Dev* D, int b) { rollout::prepare(*D, b); }
 __device__ __noinline__ void ro_finish(const rollout::Dev* D, int b) { rollout::finish(*D, b); }
+// the collision stop (opt-in): the whole wave measures the interval finish() has just applied, one sample per lane.
+// Out of line like the harness: inlined, its geometry changes the register allocation of the solve path around it
+// (C5 with the stop off: 2.6 x the HBM writes, +2 % time); out of line it costs only its own frame (callee-saved
+// registers), which is touched only when the stop is on.
+__device__ __noinline__ void ro_stop(const rollout::Dev* D, int b) { rollout::stop_check_wave(*D, b); }
 __device__ __noinline__ int ro_screen(const ObcaLaunch* L, int b) { return terminal_screen_dev(L, b, 0, 1); }
 __device__ __noinline__ int ro_retry(const rollout::Dev* D, int g, int b) { rollout::make_retry(*D, g, b); return D->var8[g][b]; }
 // (flag in the low half, group in the high half: an out-parameter would be a stack slot, i.e. scratch)
@@ -2832,6 +2838,10 @@ __device__ __forceinline__ void rollout_fused_body(const rollout::Dev& D, const 
             ro_solve_step<RPL, ShapeAny>(D, launches, g, b, ro_msg);
             if (lane == 0) ro_finish(&D, b);
             __syncthreads();
+            if (D.stop_nsub) {                  // wave-uniform; a stopped rollout's flag ends it like GOAL / CAP / FAILED
+                ro_stop(&D, b);
+                __syncthreads();
+            }
         }
         }
         if (!running && !sched) break;

@@ -7,6 +7,7 @@
 #include <vector>
 #include "obca_device.h"
 #include "obca_rollout_core.h"
+#include "obca_audit_core.h"
 
 extern "C" __global__ void obca_rollout_fused_kernel_r4(const rollout::Dev* Dp, const ObcaLaunch* launches, int n_steps, int* sched, int qmode);
 extern "C" __global__ void obca_rollout_fused_kernel_r5(const rollout::Dev* Dp, const ObcaLaunch* launches, int n_steps, int* sched, int qmode);
@@ -29,6 +30,15 @@ __global__ void rollout_retry_kernel(rollout::Dev D, int g) {
 __global__ void rollout_finish_kernel(rollout::Dev D) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b < D.B) rollout::finish(D, b);
+}
+// collision stop: one wavefront per rollout, the fused kernel's device function (identical words); the descriptor is
+// read from HBM (a by-value one would be copied to scratch for the Scene's pointer to its row counts)
+__global__ void __launch_bounds__(64) rollout_stop_kernel(const rollout::Dev* Dp) {
+    rollout::stop_check_wave(*Dp, blockIdx.x);
+}
+__global__ void rollout_fill_kernel(double* p, size_t n, double v) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) p[i] = v;
 }
 
 }  // namespace
@@ -114,7 +124,7 @@ extern "C" int obca_rollouts_create(const obca_rollout_dims* d, obca_rollouts** 
     D.Nf = d->N_fix > 0 ? d->N_fix : d->N;
     D.Nm = D.Nf > D.N ? D.Nf : D.N;
     D.Ms = 0;
-    for (int i = 0; i < d->n_static; ++i) D.Ms += d->m_static[i];
+    for (int i = 0; i < d->n_static; ++i) { D.Ms += d->m_static[i]; D.m_static[i] = d->m_static[i]; }
     const size_t B = d->batch, N1 = d->N + 1, S = d->max_steps, nd = d->n_dyn, Nm1 = D.Nm + 1, Nf1 = D.Nf + 1;
     bool ok = true;
     ok = ok && dev_alloc(r, r->goal, B * 2) && dev_alloc(r, r->path, B * 3 * D.P) && dev_alloc(r, r->path_len, B) &&
@@ -204,6 +214,11 @@ extern "C" int obca_rollouts_reset(obca_rollouts* r, const double* start, const 
     D.sense_dis = sense_dis;
     D.ego_l = params->ego[0];                                  // the gate uses ego[0], ego[1] (src/closed_loop.py:594)
     D.ego_w = params->ego[1];
+    for (int j = 0; j < 4; ++j) D.ego[j] = params->ego[j];
+    if (D.clr) {                           // +inf: no interval measured yet
+        const size_t n = B * S;
+        hipLaunchKernelGGL(rollout_fill_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, D.clr, n, (double)INFINITY);
+    }
     hipLaunchKernelGGL(rollout_reset_kernel, dim3((D.B + 63) / 64), dim3(64), 0, s, D, start, dyn, Ts0);
     if (hipGetLastError() != hipSuccess) return OBCA_E_HIP;
     for (int g = 0; g <= D.n_dyn; ++g) {
@@ -276,8 +291,41 @@ extern "C" int obca_rollouts_step(obca_rollouts* r, void* hip_stream) {
         if (hipEventRecord(r->join[g], gs) != hipSuccess || hipStreamWaitEvent(s, r->join[g], 0) != hipSuccess) return OBCA_E_HIP;
     }
     hipLaunchKernelGGL(rollout_finish_kernel, grid, block, 0, s, D);
+    if (D.stop_nsub) hipLaunchKernelGGL(rollout_stop_kernel, dim3(D.B), block, 0, s, (const rollout::Dev*)r->dD);
     if (hipGetLastError() != hipSuccess) return OBCA_E_HIP;
     return OBCA_OK;
+}
+
+extern "C" int obca_rollouts_set_collision_stop(obca_rollouts* r, int32_t n_sub, double clearance, int32_t certified) {
+    // checked before anything is touched: a refused call has no side effect
+    if (!r || n_sub < 0 || n_sub > 63 || !isfinite(clearance) || (certified != 0 && certified != 1)) return OBCA_E_INVAL;
+    ObcaDeviceGuard guard(r->dims.device);
+    if (!guard.ok) return OBCA_E_HIP;
+    rollout::Dev& D = r->D;
+    if (n_sub > 0 && !D.clr && !dev_alloc(r, D.clr, (size_t)D.B * D.S)) return OBCA_E_NOMEM;
+    D.stop_nsub = n_sub;
+    D.stop_clear = n_sub > 0 ? clearance : 0.0;
+    D.stop_certified = n_sub > 0 ? certified : 0;
+    r->ready = false;                      // takes effect with the next obca_rollouts_reset
+    return OBCA_OK;
+}
+
+extern "C" int obca_rollouts_set_exact_sensing(obca_rollouts* r, int32_t on) {
+    if (!r || (on != 0 && on != 1)) return OBCA_E_INVAL;
+    r->D.exact_sense = on;
+    r->ready = false;                      // takes effect with the next obca_rollouts_reset
+    return OBCA_OK;
+}
+
+extern "C" int obca_rollouts_read_clearance(obca_rollouts* r, double* clear_hist, void* hip_stream) {
+    if (!r || !r->ready || !clear_hist) return OBCA_E_INVAL;
+    ObcaDeviceGuard guard(r->dims.device);
+    if (!guard.ok) return OBCA_E_HIP;
+    hipStream_t s = (hipStream_t)hip_stream;
+    const size_t n = (size_t)r->D.B * r->D.S;
+    if (r->D.clr) return hipMemcpyAsync(clear_hist, r->D.clr, sizeof(double) * n, hipMemcpyDeviceToDevice, s) == hipSuccess ? OBCA_OK : OBCA_E_HIP;
+    hipLaunchKernelGGL(rollout_fill_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, clear_hist, n, (double)INFINITY);
+    return hipGetLastError() == hipSuccess ? OBCA_OK : OBCA_E_HIP;
 }
 
 extern "C" int obca_rollouts_set_warm_start(obca_rollouts* r, int enable, double mu_init) {

@@ -59,6 +59,13 @@ struct Dev {
     int32_t warm;
     double* wz[MAX_GROUPS];
     int32_t* wuse[MAX_GROUPS];
+    // optional collision stop (obca_rollouts_set_collision_stop; rollout::stop_check in obca_audit_core.h) and exact sensing
+    // (obca_rollouts_set_exact_sensing): zero / NULL = off
+    int32_t stop_nsub, stop_certified, exact_sense;
+    double stop_clear;
+    int32_t m_static[OBCA_MAX_OBST];   // row counts of the static obstacles (the audit's Scene)
+    double ego[4];                     // the footprint of obca_params.ego
+    double* clr;                       // [B, S] clearance of every measured interval, +inf elsewhere
 };
 
 // one polygon edge -> one row [a0 a1 | b]; branch order and exact comparisons of src/model_obstacle.py:63-89
@@ -227,7 +234,8 @@ RO_FN void prepare(const Dev& D, int b) {
     D.Ts[b] = Ts_opt;
     D.term[3 * b] = x0[0] + 5; D.term[3 * b + 1] = 1.0; D.term[3 * b + 2] = 9.0;      // :371
 
-    // S5/S4: static rows, then the first ns PRESENT rectangles (q8) moved with the SENSED obstacles' velocities
+    // S5/S4: static rows, then the first ns PRESENT rectangles (q8) moved with the SENSED obstacles' velocities;
+    // exact_sense: the j-th SENSED rectangle itself (its position in the present list: vj)
     const int g = ns, Mg = D.Ms + 4 * ns;
     double* Ag = D.A[g] + (size_t)b * Nf1 * Mg * 2;
     double* bg = D.b[g] + (size_t)b * Nf1 * Mg;
@@ -237,12 +245,17 @@ RO_FN void prepare(const Dev& D, int b) {
         for (int q = 0; q < 2 * D.Ms; ++q) Ak[q] = As[q];
         for (int q = 0; q < D.Ms; ++q) bk[q] = bs[q];
         for (int j = 0; j < ns; ++j) {
-            const double* info = D.dyn + ((size_t)b * nd + (int)((sensed >> (4 * j)) & 15u)) * DYN_W;
+            const int pj = (int)((sensed >> (4 * j)) & 15u);
+            const double* info = D.dyn + ((size_t)b * nd + pj) * DYN_W;
+            int vj = j;
+            if (D.exact_sense)
+                for (int q = 0; q < np; ++q)
+                    if ((int)((present >> (4 * q)) & 15u) == pj) vj = q;
             const double sx = Ts_opt * info[5] * info[11] * (double)kk;
             const double sy = Ts_opt * info[5] * info[12] * (double)kk;
             // (the four moved vertices as scalars: a local array indexed in a loop is a stack frame)
-            const double x0_ = V[j][0][0] + sx, y0_ = V[j][0][1] + sy, x1_ = V[j][1][0] + sx, y1_ = V[j][1][1] + sy;
-            const double x2_ = V[j][2][0] + sx, y2_ = V[j][2][1] + sy, x3_ = V[j][3][0] + sx, y3_ = V[j][3][1] + sy;
+            const double x0_ = V[vj][0][0] + sx, y0_ = V[vj][0][1] + sy, x1_ = V[vj][1][0] + sx, y1_ = V[vj][1][1] + sy;
+            const double x2_ = V[vj][2][0] + sx, y2_ = V[vj][2][1] + sy, x3_ = V[vj][3][0] + sx, y3_ = V[vj][3][1] + sy;
             double* Ar = Ak + 2 * (D.Ms + 4 * j);
             double* br = bk + D.Ms + 4 * j;
             edge_row(x0_, y0_, x1_, y1_, Ar, br);

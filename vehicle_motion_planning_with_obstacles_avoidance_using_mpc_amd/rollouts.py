@@ -113,6 +113,24 @@ def rollout_dims(w, N, max_steps, device=0, N_fix=None):
     return d
 
 
+FLAG_NAMES = _lib.FLAG_NAMES          # flags[b] -> "run" | "goal" | "cap" | "failed" | "collision"
+
+
+def _stop_options(collision_stop):
+    """None | n_sub | {n_sub, clearance=0.0, certified=False} -> None or the full dict (n_sub = 0: off)"""
+    if collision_stop is None:
+        return None
+    if isinstance(collision_stop, dict):
+        unknown = set(collision_stop) - {"n_sub", "clearance", "certified"}
+        if unknown or "n_sub" not in collision_stop:
+            raise ValueError("collision_stop: a dict {n_sub, clearance=0.0, certified=False}, got keys %s" % sorted(collision_stop))
+        cs = {"n_sub": int(collision_stop["n_sub"]), "clearance": float(collision_stop.get("clearance", 0.0)),
+              "certified": bool(collision_stop.get("certified", False))}
+    else:
+        cs = {"n_sub": int(collision_stop), "clearance": 0.0, "certified": False}
+    return cs if cs["n_sub"] != 0 else None
+
+
 class RolloutCohorts:
     """The batch cut into ``cohorts`` independent lock-step groups, each on its own HIP stream.  One step of a
     group lasts as long as its slowest solve (an infeasible obca_mpc6 runs to max_iter = 1000 before the obca_mpc8
@@ -170,12 +188,18 @@ class DeviceRollouts:
     """B rollouts on one GPU.  ``step()`` enqueues one receding-horizon step of every running rollout;
     ``run()`` all of them; ``read()`` returns state and history (torch tensors on the device)."""
 
-    def __init__(self, worlds, N=6, params=None, Ts0=0.1, max_steps=30, device=None, warm_start=None, N_fix=None):
+    def __init__(self, worlds, N=6, params=None, Ts0=0.1, max_steps=30, device=None, warm_start=None, N_fix=None,
+                 collision_stop=None, exact_sensing=False):
         """N: horizon of the free-time problem, N_fix (default N): of the fixed-time problems (the reference's committed
         default is N_free = N_fix = 6, src/closed_loop.py:84,91; N_fix must be a multiple of N with N_fix - 5 <= N).
         params: None = the reference's controller constants with the position box of the worlds (setting.xL / xU).
         warm_start: None = the reference's cold start of every solve; a float mu_init = start each step whose
-        problem shape equals the previous step's from the shifted previous plan (NOT reference behaviour)."""
+        problem shape equals the previous step's from the shifted previous plan (NOT reference behaviour).
+        collision_stop: None (default) = off; an int n_sub or a dict {n_sub, clearance=0.0, certified=False} = end a
+        rollout with flag "collision" when the interval of its last applied step comes closer than `clearance` to an
+        obstacle, every present moving box counted (obca_rollouts_set_collision_stop); read() then adds "clearance".
+        exact_sensing: hand the solver each sensed box's own rectangle instead of the reference's pairing (NOT reference
+        behaviour; obca_rollouts_set_exact_sensing)."""
         import torch
         if not torch.cuda.is_available():
             raise RuntimeError("DeviceRollouts needs a ROCm GPU; there is no CPU fallback on the product path")
@@ -195,6 +219,12 @@ class DeviceRollouts:
         self.mode = 0
         if warm_start is not None:
             _lib.check(self.lib.obca_rollouts_set_warm_start(self._h, 1, float(warm_start)))
+        self.collision_stop = _stop_options(collision_stop)
+        if self.collision_stop is not None:
+            cs = self.collision_stop
+            _lib.check(self.lib.obca_rollouts_set_collision_stop(self._h, cs["n_sub"], cs["clearance"], int(cs["certified"])))
+        if exact_sensing:
+            _lib.check(self.lib.obca_rollouts_set_exact_sensing(self._h, 1))
         self.reset()
 
     def _stream(self):
@@ -241,6 +271,9 @@ class DeviceRollouts:
         order = ("x_closed", "u_closed", "T_closed", "x_openloop", "variant", "iters", "status", "dyn", "steps", "flags")
         ptrs = [ctypes.c_void_p(out[k].data_ptr()) if (k != "dyn" or nd) else None for k in order]
         _lib.check(self.lib.obca_rollouts_read(self._h, *ptrs, self._stream()))
+        if self.collision_stop is not None:
+            out["clearance"] = f(B, S)
+            _lib.check(self.lib.obca_rollouts_read_clearance(self._h, ctypes.c_void_p(out["clearance"].data_ptr()), self._stream()))
         return out
 
     def audit(self, n_sub=8, per_step=False):
