@@ -411,7 +411,8 @@ int obca_rasterise_batch(const double* boxes, int32_t B, int32_t K, double resol
  * rest DEVICE pointers in obca_solve_batch's shapes: x [B,3,N+1], A [B,N+1,M,2], b [B,N+1,M], variant [B] or NULL.
  * Where variant[b] == 4 every stage is measured against stage 0's rows (what obca_mpc4 reads); otherwise stage k
  * against its own rows.  Outputs: min_clear [B], arg_stage [B], arg_obst [B] (ties to the lowest stage, then the
- * lowest obstacle), stage_obst [B,N+1,n_obs] or NULL. */
+ * lowest obstacle), stage_obst [B,N+1,n_obs] or NULL.  A (stage, obstacle) pair whose pose, rows or distance is not
+ * finite measures NaN, and NaN ranks below every number: min_clear is then NaN, arg_stage / arg_obst the first such pair. */
 int obca_plan_clearance(const double ego[4], int32_t n_obs, const int32_t* m, int32_t N, int32_t B,
                         const int32_t* variant, const double* x, const double* A, const double* b,
                         double* min_clear, int32_t* arg_stage, int32_t* arg_obst, double* stage_obst,

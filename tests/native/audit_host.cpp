@@ -34,3 +34,42 @@ extern "C" int audit_host_interval(const double* ego, int n_static, const int* m
 extern "C" void audit_host_box_next(const double* info, double cx, double cy, int s_next, double T, double* out) {
     audit::box_next_knot(info, cx, cy, s_next, T, out);
 }
+
+// the plan audit of one batch (obca_plan_clearance's per-instance reduction, csrc/obca_audit.hip plan_clearance_kernel)
+// run serially over stages and obstacles with the shared audit::plan_distance / audit::better: x [B,3,N+1],
+// A [B,N+1,M,2], b [B,N+1,M] with M = sum(m), variant [B] or NULL (4: stage 0's rows at every stage); outputs min_clear,
+// arg_stage, arg_obst [B], stage_obst [B,N+1,n_obs]
+extern "C" int audit_host_plan_clearance(const double* ego, int n_obs, const int* m, int N, int B, const int* variant,
+                                         const double* x, const double* A, const double* b, double* min_clear, int* arg_stage,
+                                         int* arg_obst, double* stage_obst) {
+    if (n_obs < 1 || n_obs > OBCA_MAX_OBST || N < 1 || B < 1) return -22;
+    int off[OBCA_MAX_OBST], M = 0;
+    for (int i = 0; i < n_obs; ++i) {
+        if (m[i] < 1 || m[i] > HOST_MAXM) return -22;
+        off[i] = M;
+        M += m[i];
+    }
+    const int N1 = N + 1;
+    for (int inst = 0; inst < B; ++inst) {
+        const int v = variant ? variant[inst] : 0;
+        const double* xb = x + (size_t)inst * 3 * N1;
+        double best = INFINITY;
+        int bs = 0x7fffffff, bo = 0x7fffffff;
+        for (int k = 0; k < N1; ++k) {
+            double C[4][2];
+            audit::car_corners(xb[k], xb[N1 + k], xb[2 * N1 + k], ego, C);
+            const int ks = (v == 4) ? 0 : k;
+            const double* Ak = A + ((size_t)inst * N1 + ks) * M * 2;
+            const double* bk = b + ((size_t)inst * N1 + ks) * M;
+            for (int i = 0; i < n_obs; ++i) {
+                const double d = audit::plan_distance<HOST_MAXM>(C, Ak + 2 * off[i], bk + off[i], m[i]);
+                stage_obst[((size_t)inst * N1 + k) * n_obs + i] = d;
+                if (audit::better(d, k, i, best, bs, bo)) { best = d; bs = k; bo = i; }
+            }
+        }
+        min_clear[inst] = best;
+        arg_stage[inst] = bs;
+        arg_obst[inst] = bo;
+    }
+    return 0;
+}

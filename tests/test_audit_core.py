@@ -24,8 +24,7 @@ MAXM = 8                    # HOST_MAXM of audit_host.cpp
 E_INVAL = -22
 
 
-@pytest.fixture(scope="module")
-def host():
+def load_host():
     """the host shim, compiled the way tests/native_build.py compiles its own"""
     if not os.path.exists(OUT) or any(os.path.getmtime(d) > os.path.getmtime(OUT) for d in DEPS):
         os.makedirs(os.path.dirname(OUT), exist_ok=True)
@@ -34,7 +33,13 @@ def host():
     lib.audit_host_distance.restype = ctypes.c_int
     lib.audit_host_interval.restype = ctypes.c_int
     lib.audit_host_box_next.restype = None
+    lib.audit_host_plan_clearance.restype = ctypes.c_int
     return lib
+
+
+@pytest.fixture(scope="module")
+def host():
+    return load_host()
 
 
 def _p(a):
@@ -188,6 +193,196 @@ def test_box_update_law(host):
     assert list(out) == [1.0, 2.0, 1.0]
     host.audit_host_box_next(_p(info), ctypes.c_double(1.0), ctypes.c_double(2.0), 4, ctypes.c_double(0.5), _p(out))
     assert list(out) == [1.0 + 0.5 * 0.4 * info[11], 2.0 + 0.5 * 0.4 * info[12], 1.0]
+
+
+# ------------------------------------------------------------------------------------------------ plan audit reduction
+PLAN_M = {1: [1], 3: [1, 3, 1], 8: [1, 2, 3, 4, 1, 2, 3, 4]}    # obstacle 0 and TIE_OBST[n_obs] are half-planes
+TIE_OBST = {1: None, 3: 2, 8: 4}
+
+
+def _obstacle_rows(rng, m):
+    """rows of one obstacle near the origin: half-plane (m = 1), wedge (2), triangle (3), rotated box (4)"""
+    c = rng.uniform(-4, 4, 2)
+    if m == 1:
+        a = rng.uniform(0, 2 * math.pi)
+        q = c + 3 * np.array([math.cos(a), math.sin(a)])
+        return _rows([[float(c[0]), float(c[1])], [float(q[0]), float(q[1])]])
+    if m == 4:
+        return _rows(rectangle_vertices(c[0], c[1], rng.uniform(-math.pi, math.pi), rng.uniform(1, 4), rng.uniform(1, 4)))
+    while True:
+        pts = _clockwise(rng, 5, c, rng.uniform(1, 4))[:3] if m == 2 else _clockwise(rng, 3, c, rng.uniform(1, 4))
+        A, b = _rows(pts)
+        if (kkt_check._wedge_vertices(A, b) if m == 2 else kkt_check._polygon_vertices(A, b)) is not None:
+            return A, b
+
+
+def random_plans(rng, B, N, n_obs, variants=(0, 4, 6, 8)):
+    """B plans over N + 1 stages against the obstacles of PLAN_M[n_obs], every stage's rows translated on their own:
+    x [B,3,N+1], A [B,N+1,M,2], b [B,N+1,M], variant [B], and per instance the constructed tie (s0, s1) or None.  Poses
+    over [-6, 6]^2 around obstacles in [-4, 4]^2, so both signs of distance occur.  Every other instance carries an exact
+    tie: its stage s0 pose 40 m deep in half-plane 0 (the rows that stage is measured against), stage s1 > s0 a copy of
+    stage s0 (pose and rows), half-plane TIE_OBST[n_obs] a copy of half-plane 0 -- so the smallest value occurs at
+    (s0, 0), (s1, 0) and the copies; s1 = s0 + 64 (the same lane of a 64-wide segment) where N + 1 allows it."""
+    m = PLAN_M[n_obs]
+    M, N1 = sum(m), N + 1
+    off = np.concatenate([[0], np.cumsum(m)]).astype(int)
+    x = np.stack([rng.uniform(-6, 6, (B, N1)), rng.uniform(-6, 6, (B, N1)), rng.uniform(-math.pi, math.pi, (B, N1))], 1)
+    A, b = np.zeros((B, N1, M, 2)), np.zeros((B, N1, M))
+    variant = rng.choice(np.asarray(variants, np.int32), B).astype(np.int32)
+    ties = []
+    for i in range(B):
+        rows = [_obstacle_rows(rng, mi) for mi in m]
+        tie = i % 2 == 1 and (n_obs > 1 or N1 > 1)
+        if tie and TIE_OBST[n_obs] is not None:
+            rows[TIE_OBST[n_obs]] = rows[0]
+        A0, b0 = np.concatenate([r[0] for r in rows]), np.concatenate([r[1] for r in rows])
+        for k in range(N1):
+            t = rng.uniform(-1.5, 1.5, 2)
+            A[i, k], b[i, k] = A0, b0 + A0 @ t
+        if not tie:
+            ties.append(None)
+            continue
+        s0 = int(rng.integers(0, N1 - 1))
+        s1 = s0 + 64 if s0 + 64 < N1 and rng.uniform() < 0.5 else int(rng.integers(s0 + 1, N1))
+        ks = 0 if variant[i] == 4 else s0
+        a, bb = A[i, ks, 0], b[i, ks, 0]
+        x[i, :2, s0] = a * bb / (a @ a) - 40.0 * a / np.linalg.norm(a)
+        x[i, :, s1], A[i, s1], b[i, s1] = x[i, :, s0], A[i, s0], b[i, s0]
+        ties.append((s0, s1))
+    return x, A, b, variant, ties
+
+
+def host_plan_clearance(host, x, A, b, m, variant=None, ego=EGO):
+    """audit_host_plan_clearance: (min_clear [B], arg_stage [B], arg_obst [B], stage_obst [B,N+1,n_obs])"""
+    B, N1 = x.shape[0], x.shape[2]
+    mc, st, ob = np.zeros(B), np.zeros(B, np.int32), np.zeros(B, np.int32)
+    so = np.zeros((B, N1, len(m)))
+    x, A, b = (np.ascontiguousarray(a, float) for a in (x, A, b))
+    var = None if variant is None else np.ascontiguousarray(variant, np.int32)
+    rc = host.audit_host_plan_clearance(_p(np.asarray(ego, float)), len(m), _p(np.asarray(m, np.int32)), N1 - 1, B,
+                                        None if var is None else _p(var), _p(x), _p(A), _p(b), _p(mc), _p(st), _p(ob), _p(so))
+    assert rc == 0
+    return mc, st, ob, so
+
+
+def numpy_stage_obst(x, A, b, m, variant, idx, ego=EGO):
+    """kkt_check.polytope_distance per (stage, obstacle) of the instances idx: [len(idx),N+1,n_obs]; stage 0's rows
+    wherever the variant is 4"""
+    off = np.concatenate([[0], np.cumsum(m)]).astype(int)
+    out = np.zeros((len(idx), x.shape[2], len(m)))
+    for r, i in enumerate(idx):
+        for k in range(x.shape[2]):
+            ks = 0 if variant is not None and variant[i] == 4 else k
+            car = kkt_check.car_corners(x[i, :, k], ego)
+            for o in range(len(m)):
+                out[r, k, o] = kkt_check.polytope_distance(car, A[i, ks, off[o]:off[o + 1]], b[i, ks, off[o]:off[o + 1]])
+    return out
+
+
+def first_argmin(stage_obst):
+    """(value, stage, obstacle) per instance under the audit's order: the first NaN in (stage, obstacle) order if there
+    is one, else the first occurrence of the minimum (np.argmin does both)"""
+    B, N1, n = stage_obst.shape
+    flat = stage_obst.reshape(B, -1)
+    am = np.argmin(flat, 1)
+    return flat[np.arange(B), am], (am // n).astype(np.int32), (am % n).astype(np.int32)
+
+
+@pytest.mark.parametrize("n_obs", [1, 3, 8])
+def test_plan_reduction_equals_polytope_distance(host, n_obs):
+    """the kernel's per-instance reduction, run serially: every (stage, obstacle) distance against kkt_check, the minimum
+    and its (stage, obstacle) under the tie rule on constructed exact ties across stages and obstacles"""
+    rng = np.random.default_rng(21 + n_obs)
+    m = PLAN_M[n_obs]
+    x, A, b, variant, ties = random_plans(rng, 48, 9, n_obs)
+    mc, st, ob, so = host_plan_clearance(host, x, A, b, m, variant)
+    ref = numpy_stage_obst(x, A, b, m, variant, range(len(x)))
+    assert np.abs(so - ref).max() <= 1e-9
+    assert (ref < 0).sum() >= 20 and (ref > 0).sum() >= 20
+    v, s, o = first_argmin(so)
+    assert np.array_equal(mc, v) and np.array_equal(st, s) and np.array_equal(ob, o)
+    assert np.abs(mc - ref.reshape(len(x), -1).min(1)).max() <= 1e-9
+    stage_ties = obst_ties = 0
+    for i, t in enumerate(ties):                     # the constructed ties: the lower stage, then the lower obstacle wins
+        if t is None:
+            continue
+        assert np.array_equal(so[i, t[0]], so[i, t[1]])
+        if mc[i] == so[i, t[0]].min():
+            assert (st[i], ob[i]) == (t[0], int(np.argmin(so[i, t[0]]))), (i, t, st[i], ob[i])
+            stage_ties += 1
+            obst_ties += TIE_OBST[n_obs] is not None and ob[i] == 0 and so[i, t[0], TIE_OBST[n_obs]] == mc[i]
+    assert stage_ties >= 18 and (obst_ties >= 12 or n_obs == 1), (stage_ties, obst_ties)
+    # variant 4 reads stage 0's rows only
+    A2, b2 = A.copy(), b.copy()
+    b2[:, 1:] -= 3.0
+    mc2, st2, _, _ = host_plan_clearance(host, x, A2, b2, m, variant)
+    v4 = variant == 4
+    assert v4.any() and np.array_equal(mc2[v4], mc[v4]) and np.array_equal(st2[v4], st[v4])
+    assert not np.array_equal(mc2[~v4], mc[~v4])
+
+
+def nan_plans(rng, N=7, n_obs=3):
+    """finite plans and one each of: a NaN pose at one stage, a NaN in one obstacle's row at one stage, an infinite pose,
+    an all-NaN plan (variant 0).  Returns x, A, b, variant, the index of the first non-finite instance and, per non-finite
+    instance, the (stage, obstacle) pairs that must measure NaN"""
+    x, A, b, variant, _ = random_plans(rng, 12, N, n_obs)
+    m = PLAN_M[n_obs]
+    off = np.concatenate([[0], np.cumsum(m)]).astype(int)
+    N1, B0 = N + 1, len(x)
+    nx, nA, nb = x[:4].copy(), A[:4].copy(), b[:4].copy()
+    nv = np.zeros(4, np.int32)
+    bad = []
+    nx[0, 1, 5] = np.nan                                            # NaN pose: every obstacle of that stage
+    bad.append({(5, o) for o in range(n_obs)})
+    nA[1, 3, off[n_obs - 1], 1] = np.nan                            # NaN row: that obstacle at that stage
+    bad.append({(3, n_obs - 1)})
+    nx[2, 0, 6] = np.inf                                            # infinite pose
+    bad.append({(6, o) for o in range(n_obs)})
+    nx[3] = np.nan                                                  # all NaN
+    bad.append({(k, o) for k in range(N1) for o in range(n_obs)})
+    return (np.concatenate([x, nx]), np.concatenate([A, nA]), np.concatenate([b, nb]), np.concatenate([variant, nv]),
+            B0, bad)
+
+
+def test_plan_reduction_reports_nan_for_non_finite_inputs(host):
+    """a NaN or infinite pose, a NaN row, an all-NaN plan: the pairs they touch measure NaN, min_clear is NaN and the
+    arg-min names the first such pair -- never the minimum of the finite rest (which would call "unknown" "safe")"""
+    rng = np.random.default_rng(5)
+    m = PLAN_M[3]
+    x, A, b, variant, B0, bad = nan_plans(rng)
+    mc, st, ob, so = host_plan_clearance(host, x, A, b, m, variant)
+    assert np.isfinite(so[:B0]).all() and np.isfinite(mc[:B0]).all()
+    for j, pairs in enumerate(bad):
+        i = B0 + j
+        got = {(int(k), int(o)) for k, o in zip(*np.nonzero(np.isnan(so[i])))}
+        assert got == pairs, (j, got)
+        assert np.isnan(mc[i]), (j, mc[i])
+        assert (st[i], ob[i]) == min(pairs), (j, st[i], ob[i])
+    assert (st[B0 + 3], ob[B0 + 3]) == (0, 0)
+    ref = host_plan_clearance(host, x[:B0], A[:B0], b[:B0], m, variant[:B0])      # the finite instances do not notice
+    for got, want in zip((mc, st, ob, so), ref):
+        assert np.array_equal(got[:B0], want)
+
+
+def test_better_orders_nan_first_then_value_stage_obstacle(host):
+    """the order itself through the reduction: one instance, one stage per value, the values given directly"""
+    # two obstacles, half-planes y <= b: the car at the origin (heading 0, y in [-0.75, 0.75]) measures -0.75 - b
+    cases = [([7.3, np.nan, -0.7], np.nan, 1), ([7.3, 2.0, -0.7], -0.7, 2), ([np.nan] * 3, np.nan, 0),
+             ([1.0, 1.0, 1.0], 1.0, 0), ([np.inf, 1.0, 2.0], np.nan, 0), ([-np.inf, 1.0, 2.0], np.nan, 0)]
+    for vals, want, stage in cases:
+        N1 = len(vals)
+        x = np.zeros((1, 3, N1))
+        A = np.zeros((1, N1, 2, 2))
+        A[..., 1] = 1.0
+        b = np.zeros((1, N1, 2))
+        for k, v in enumerate(vals):
+            b[0, k] = -0.75 - v if np.isfinite(v) else v
+        mc, st, ob, so = host_plan_clearance(host, x, A, b, [1, 1])
+        if np.isnan(want):
+            assert np.isnan(mc[0]), (vals, mc[0])
+        else:
+            assert mc[0] == pytest.approx(want, abs=1e-12), (vals, mc[0])
+        assert (st[0], ob[0]) == (stage, 0), (vals, st[0], ob[0])
 
 
 # ------------------------------------------------------------------------------------------------ C ABI argument checks

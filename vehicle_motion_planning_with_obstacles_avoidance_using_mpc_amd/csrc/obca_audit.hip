@@ -44,10 +44,7 @@ struct AuditArgs {
     double* step_min;
 };
 
-// (value, step, obstacle) lexicographic: ties to the lowest step, then the lowest obstacle
-__device__ inline bool better(double v, int s, int o, double v2, int s2, int o2) {
-    return v < v2 || (v == v2 && (s < s2 || (s == s2 && o < o2)));
-}
+using audit::better;
 
 __device__ inline void seg_argmin(double& v, int& s, int& o, int seg) {
     for (int w = seg >> 1; w > 0; w >>= 1) {
@@ -88,7 +85,7 @@ __global__ void __launch_bounds__(BLOCK) plan_clearance_kernel(PlanArgs P) {
             const double* Ak = P.A + ((size_t)inst * N1 + ks) * P.M * 2;
             const double* bk = P.b + ((size_t)inst * N1 + ks) * P.M;
             for (int i = 0; i < P.n_obs; ++i) {
-                const double d = audit::signed_distance<OBCA_MAX_EDGES>(C, Ak + 2 * P.off[i], bk + P.off[i], P.m[i]);
+                const double d = audit::plan_distance<OBCA_MAX_EDGES>(C, Ak + 2 * P.off[i], bk + P.off[i], P.m[i]);
                 if (P.stage_obst) P.stage_obst[((size_t)inst * N1 + k) * P.n_obs + i] = d;
                 if (better(d, k, i, best, bs, bo)) { best = d; bs = k; bo = i; }
             }

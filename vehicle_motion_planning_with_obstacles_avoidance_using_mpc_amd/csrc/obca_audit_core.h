@@ -150,6 +150,27 @@ AU_FN double signed_distance(const double C[4][2], const double* A, const double
     return dm;
 }
 
+// (value, stage / step, obstacle) lexicographic, a NaN value below every number: ties (among NaNs as among equal values)
+// to the lowest stage, then the lowest obstacle.  A total order on distinct (stage, obstacle), so any reduction order
+// gives the same winner.
+AU_FN bool better(double v, int s, int o, double v2, int s2, int o2) {
+    const bool n = v != v, n2 = v2 != v2;
+    if (n != n2) return n;
+    return (n || v == v2) ? (s < s2 || (s == s2 && o < o2)) : v < v2;
+}
+
+// one (stage, obstacle) distance of the plan audit: NaN when a corner of the car, a row or the distance itself is not
+// finite.  signed_distance's dmin_ / dmax drop a NaN operand, so a non-finite input must not reach it as a number: the
+// audit never turns "unknown" into "safe".
+template <int MAXM>
+AU_FN double plan_distance(const double C[4][2], const double* A, const double* b, int m) {
+    bool ok = true;
+    for (int v = 0; v < 4; ++v) ok = ok && isfinite(C[v][0]) && isfinite(C[v][1]);
+    for (int j = 0; j < m; ++j) ok = ok && isfinite(A[2 * j]) && isfinite(A[2 * j + 1]) && isfinite(b[j]);
+    const double d = ok ? signed_distance<MAXM>(C, A, b, m) : NAN;
+    return isfinite(d) ? d : NAN;
+}
+
 // a moving rectangle (centre, heading cos / sin, length, width) as the harness hands it to the solver: clockwise vertices
 // (rect_vertices), one row per edge (edge_row)
 AU_FN double box_distance(const double C[4][2], double cx, double cy, double c, double s, double length, double width) {
