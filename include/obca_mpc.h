@@ -361,6 +361,19 @@ int obca_rollouts_set_collision_stop(obca_rollouts* r, int32_t n_sub, double cle
  * velocity; on = 0 (default) keeps the reference's sensor pairing (the j-th PRESENT box's rectangle with the j-th sensed
  * box's velocity).  Same problem shapes either way.  on outside {0, 1}: OBCA_E_INVAL.  Call before obca_rollouts_reset. */
 int obca_rollouts_set_exact_sensing(obca_rollouts* r, int32_t on);
+/* Optional swept, inflated rows of the sensed moving boxes (obca_mpc 0.8), NOT reference behaviour: stage kk of a
+ * fixed-time problem gets, for every sensed box, the four rows of the rectangle that covers the box -- inflated by `margin`
+ * metres -- at every stage time in [kk - half_window, kk + half_window] (same heading, centre at the box's stage-kk
+ * position, length + 2 (half_window |Ts_opt v| + margin), width + 2 margin) instead of the rows of the box at stage kk.
+ * Same problem shapes, same kernels.  With half_window >= 1/2 a feasible obca_mpc6 / obca_mpc8 step keeps the interpolated
+ * car at least dmin + margin - half_window delta - eps away from every box sensed at that step, delta = |dp| + r_max
+ * |dtheta| of the applied interval (derivation, eps: csrc/obca_rollout_core.h, moving_box_rows); a grown box can swallow
+ * the fixed stage-0 pose, which ends the rollout as OBCA_DONE_FAILED.  Both zero: off (default), every word as without
+ * the call.  half_window in [0, 1], margin in [0, 2], finite; anything else: OBCA_E_INVAL without side effect.  Needs exact
+ * sensing (the box's own rectangle AND velocity): obca_rollouts_reset returns OBCA_E_INVAL, before it touches anything,
+ * while swept rows are on and exact sensing is off.  Call before obca_rollouts_reset.  obca_rollouts_debug_harness shows
+ * the swept rows as the solver gets them. */
+int obca_rollouts_set_swept_rows(obca_rollouts* r, double half_window, double margin);
 /* Clearance history of the collision stop to a caller-owned DEVICE buffer clear_hist [B,max_steps]: the measured value
  * of every interval the stop evaluated, +inf elsewhere (stop off, or beyond the rollout's steps).  Asynchronous. */
 int obca_rollouts_read_clearance(obca_rollouts* r, double* clear_hist, void* hip_stream);
@@ -439,8 +452,24 @@ int obca_rollouts_audit(obca_rollouts* r, int32_t n_sub,
                         int32_t* first_collision, int32_t* first_violation,
                         double* step_min, void* hip_stream);
 
+/* ------------------------------------------------------------------------------------------------------
+ * Obstacle rows of moving rectangles for obca_solve_batch, built on the device: what the closed loop's harness writes
+ * for its sensed boxes (exact sensing), for callers that solve batches directly.  Per instance and horizon stage
+ * kk = 0..N the Ms static rows are copied and every box gets the four rows of obca_rollouts_set_swept_rows' rectangle
+ * (half_window = margin = 0: the box itself at stage kk, the harness's words).  DEVICE pointers: static_A [B,Ms,2],
+ * static_b [B,Ms] (may be NULL when Ms = 0), boxes [B,n_box,13] -- the tuple of obca_rollouts_reset's dyn: centre now
+ * 0, 1; length 3, width 4; speed 5; cos / sin of the heading 11, 12 -- and Ts [B], the step length of the solve (both may
+ * be NULL when n_box = 0); outputs A [B,N+1,Ms + 4 n_box,2], b [B,N+1,Ms + 4 n_box].  static_A and A must be 16-byte
+ * aligned (hipMalloc's are).  N >= 1, B >= 1, 0 <= Ms <= 32, 0 <= n_box <= 8, Ms + 4 n_box >= 1, half_window in [0, 1],
+ * margin in [0, 2].  Every argument is checked before the first HIP call; a refused call (OBCA_E_INVAL) has no side
+ * effect.  Asynchronous on hip_stream. */
+int obca_moving_rows_batch(int32_t B, int32_t N, int32_t Ms, int32_t n_box, const double* static_A, const double* static_b,
+                           const double* boxes, const double* Ts, double half_window, double margin, double* A, double* b,
+                           int32_t device, void* hip_stream);
+
 const char* obca_strerror(int code);
-/* "obca_mpc 0.7 (gfx950)": 0.7 = opt-in collision stop (OBCA_DONE_COLLISION, obca_rollouts_set_collision_stop,
+/* "obca_mpc 0.8 (gfx950)": 0.8 = opt-in swept, inflated rows of moving boxes (obca_rollouts_set_swept_rows, obca_moving_rows_batch);
+ * 0.7 = opt-in collision stop (OBCA_DONE_COLLISION, obca_rollouts_set_collision_stop,
  * obca_rollouts_read_clearance) and exact sensing (obca_rollouts_set_exact_sensing); 0.6 = the answer of an exhausted start ladder is the most informative pass's (obca_params: the starts of a
  * solve), the second-order correction's scratch in LDS where it costs no occupancy; 0.5 = obca_params.struct_size (first member; obca_params_init), the dodge rung and the terminal-set screen,
  * OBCA_START_DEFAULT = the window first for obca_mpc4 too, kernel mode 5;

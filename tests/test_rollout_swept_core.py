@@ -1,0 +1,291 @@
+"""CPU tier of the closed loop's opt-in swept, inflated rows of moving boxes (rollout::moving_box_rows, sweep_h / sweep_r in
+csrc/obca_rollout_core.h), built for the host from tests/native/rollout_swept_host.cpp.  Off, the loop is the exact-sensing
+loop word for word; the rows contain the box, inflated, over the stage's time window and touch it; and a feasible fixed-time
+step keeps the interpolated car dmin + r - h delta - eps away from every box it sensed -- the bound derived in the core's
+header, checked here with a numpy signed distance of the test's own."""
+import ctypes
+import math
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from oracle import c_oracle
+from tests import native_build
+from tests.test_rollout_stop_core import EGO, KEYS, N, STEPS, _inputs, _p, edge_row, q8_case, rect_vertices
+from vehicle_motion_planning_with_obstacles_avoidance_using_mpc_amd.rollouts import DeviceRollouts, pack_worlds, rollout_dims
+from vehicle_motion_planning_with_obstacles_avoidance_using_mpc_amd.scenarios import make_world_c5
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+SRC = os.path.join(HERE, "native", "rollout_swept_host.cpp")
+OUT = os.path.join(HERE, "native", "_build", "librollout_swept_host.so")
+CSRC = os.path.join(ROOT, "vehicle_motion_planning_with_obstacles_avoidance_using_mpc_amd", "csrc")
+DEPS = native_build.DEPS + [SRC, os.path.join(HERE, "native", "rollout_stop_host.cpp"), os.path.join(CSRC, "obca_audit_core.h")]
+DMIN = 0.05                       # c_oracle.default_params / SolverParams
+TAU = 1e-6 + 1e-8                 # obca_params defaults: feas_tol (elastic variables) + tol (row residuals)
+N_SUB = 16
+GUARANTEE_WORLDS = 16
+
+
+@pytest.fixture(scope="module")
+def host():
+    """the shim in its own library, compiled the way tests/test_rollout_stop_core.py compiles its one"""
+    if not os.path.exists(OUT) or any(os.path.getmtime(d) > os.path.getmtime(OUT) for d in DEPS):
+        os.makedirs(os.path.dirname(OUT), exist_ok=True)
+        subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fopenmp", "-Wno-unknown-pragmas",
+                        SRC, "-o", OUT], check=True)
+    lib = ctypes.CDLL(OUT)
+    for f in ("rollout_stop_host_run", "rollout_swept_host_run", "rollout_swept_host_harness", "rollout_swept_host_rows_batch"):
+        getattr(lib, f).restype = ctypes.c_int
+    return lib
+
+
+def _outputs(w):
+    B, S, N1, nd = w.batch, STEPS, N + 1, w.n_dyn
+    return {"x_closed": np.zeros((B, S + 1, 3)), "u_closed": np.zeros((B, S, 2)), "T_closed": np.zeros((B, S)),
+            "x_openloop": np.zeros((B, S, 3, N1)), "variant": np.zeros((B, S), np.int32), "iters": np.zeros((B, S), np.int32),
+            "status": np.zeros((B, S), np.int32), "dyn": np.zeros((B, S, max(nd, 1), 4)), "steps": np.zeros(B, np.int32),
+            "flags": np.zeros(B, np.int32), "clearance": np.zeros((B, S))}
+
+
+def run(host, w, h, r, stop_nsub=N_SUB, exact=1, swept=True):
+    """the host closed loop: rollout_swept_host_run, or (swept=False) rollout_stop_host_run of the same library"""
+    d = rollout_dims(w, N, STEPS)
+    out = _outputs(w)
+    params = c_oracle.default_params()
+    head = [ctypes.byref(d), *[_p(a) for a in _inputs(w)], ctypes.c_double(0.1), ctypes.c_double(w.sense_dis), ctypes.byref(params),
+            STEPS, stop_nsub, ctypes.c_double(0.0), 0, exact]
+    tail = [*[_p(out[k]) for k in KEYS], _p(out["clearance"])]
+    if swept:
+        rc = host.rollout_swept_host_run(*head, ctypes.c_double(h), ctypes.c_double(r), *tail)
+    else:
+        rc = host.rollout_stop_host_run(*head, *tail)
+    return rc, out
+
+
+def host_rows(host, static_A, static_b, boxes, Ts, n, h, r):
+    """rollout_swept_host_rows_batch: the host twin of obca_moving_rows_batch"""
+    static_A, static_b = np.ascontiguousarray(static_A, float), np.ascontiguousarray(static_b, float)
+    boxes, Ts = np.ascontiguousarray(boxes, float), np.ascontiguousarray(Ts, float)
+    B, nb, Ms = boxes.shape[0], boxes.shape[1], static_b.shape[1]
+    A, b = np.zeros((B, n + 1, Ms + 4 * nb, 2)), np.zeros((B, n + 1, Ms + 4 * nb))
+    rc = host.rollout_swept_host_rows_batch(B, n, Ms, nb, _p(static_A), _p(static_b), _p(boxes), _p(Ts), ctypes.c_double(h),
+                                            ctypes.c_double(r), _p(A), _p(b))
+    assert rc == 0
+    return A, b
+
+
+# ------------------------------------------------------------------------------------------------------------------ off
+def test_off_is_the_exact_sensing_loop_word_for_word(host):
+    w = pack_worlds([make_world_c5(i) for i in range(8)])
+    rc, ref = run(host, w, 0.0, 0.0, swept=False)
+    assert rc == 0
+    rc, got = run(host, w, 0.0, 0.0)
+    assert rc == 0
+    assert (ref["variant"] >= 6).any()                                   # fixed-time steps: the rows in question were built
+    for k in ref:
+        assert np.array_equal(got[k], ref[k]), k
+
+
+def test_swept_rows_without_exact_sensing_are_refused(host):
+    w = pack_worlds([make_world_c5(0)])
+    assert run(host, w, 0.5, 0.0, exact=0)[0] == -22
+    assert run(host, w, 0.0, 0.25, exact=0)[0] == -22
+    assert run(host, w, 0.0, 0.0, exact=0, stop_nsub=0)[0] == 0
+
+
+# ----------------------------------------------------------------------------------------------------------------- rows
+def swept_rectangle(info, Ts, kk, h, r):
+    """(cx, cy, length, width) of the rectangle of stage kk as include/obca_mpc.h states it"""
+    cx = info[0] + Ts * info[5] * info[11] * float(kk)
+    cy = info[1] + Ts * info[5] * info[12] * float(kk)
+    return cx, cy, info[3] + 2 * (h * abs(Ts * info[5]) + r), info[4] + 2 * r
+
+
+def expected_rows(info, Ts, kk, h, r):
+    """rect_vertices + edge_row (the restatements of tests/test_rollout_stop_core.py) on the swept rectangle: [4,2], [4]"""
+    cx, cy, length, width = swept_rectangle(info, Ts, kk, h, r)
+    V = rect_vertices(cx, cy, info[11], info[12], length, width)
+    A, b = np.zeros((4, 2)), np.zeros(4)
+    for e in range(4):
+        (a0, a1), bb = edge_row(V[e][0], V[e][1], V[(e + 1) % 4][0], V[(e + 1) % 4][1])
+        A[e] = a0, a1
+        b[e] = bb
+    return A, b
+
+
+def inflated_corners(info, Ts, t, r):
+    """the four corners of the box at stage time t, pushed out by r along both box axes: [4,2]"""
+    c, s = info[11], info[12]
+    cx, cy = info[0] + t * Ts * info[5] * c, info[1] + t * Ts * info[5] * s
+    l, w = info[3] / 2 + r, info[4] / 2 + r
+    return np.array([(cx + a * l * c - e * w * s, cy + a * l * s + e * w * c) for a in (-1, 1) for e in (-1, 1)])
+
+
+def random_boxes(kind, n, rng):
+    out = np.zeros((n, 13))
+    for i in range(n):
+        if kind == "axis":
+            th = float(rng.choice([0.0, math.pi / 2, -math.pi / 2]))              # +-pi/2: cos = 6e-17, as C5 stores them
+        else:
+            th = float(rng.uniform(-math.pi, math.pi))
+        out[i, :6] = rng.uniform(5, 35), rng.uniform(1, 9), th, rng.uniform(1, 5), rng.uniform(0.5, 3), rng.uniform(-1.5, 1.5)
+        out[i, 11], out[i, 12] = np.cos(th), np.sin(th)
+    return out
+
+
+@pytest.mark.parametrize("kind", ["axis", "oblique"])
+def test_rows_contain_the_inflated_box_over_the_window_and_touch_it(host, kind):
+    rng = np.random.default_rng(7 if kind == "axis" else 11)
+    boxes = random_boxes(kind, 24, rng)
+    Ts = rng.uniform(0.05, 1.0, len(boxes))
+    for h in (0.25, 0.5, 1.0):
+        for r in (0.0, 0.3):
+            A, b = host_rows(host, np.zeros((len(boxes), 0, 2)), np.zeros((len(boxes), 0)), boxes[:, None, :], Ts, N, h, r)
+            for i, info in enumerate(boxes):
+                for kk in range(N + 1):
+                    Ak, bk = A[i, kk], b[i, kk]
+                    eA, eb = expected_rows(info, Ts[i], kk, h, r)
+                    assert np.array_equal(Ak, eA) and np.array_equal(bk, eb), (kind, i, kk, h, r)   # row order, branch forms
+                    Q = np.concatenate([inflated_corners(info, Ts[i], t, r) for t in np.linspace(kk - h, kk + h, 9)])
+                    gap = Q @ Ak.T - bk                                          # [36,4]: <= 0 inside
+                    scale = np.maximum(1.0, np.abs(bk) + np.abs(Q) @ np.abs(Ak).T)
+                    assert (gap <= 1e-12 * scale).all(), (kind, i, kk, h, r, float((gap / scale).max()))      # containment
+                    assert ((gap / scale).max(axis=0) >= -1e-12).all(), (kind, i, kk, h, r)                   # tightness
+
+
+def test_harness_rows_are_the_builder_rows(host):
+    """the rows prepare() hands the solver on a step with one sensed box = the batch builder's rows of that box, swept and
+    (half_window = margin = 0) plain"""
+    w, x0, Ts, info, V = q8_case()
+    d = rollout_dims(w, N, STEPS)
+    Ms = w.static_A.shape[1]
+    for h, r in ((0.0, 0.0), (0.5, 0.5), (1.0, 0.0), (0.0, 0.25)):
+        A, b, var, now = np.zeros((N + 1, Ms + 4, 2)), np.zeros((N + 1, Ms + 4)), np.zeros(1, np.int32), np.zeros((w.n_dyn, 13))
+        rc = host.rollout_swept_host_harness(ctypes.byref(d), *[_p(a) for a in _inputs(w)], ctypes.c_double(w.sense_dis),
+                                             _p(np.asarray(EGO, float)), 1, ctypes.c_double(Ts), _p(np.ascontiguousarray(x0)), 1,
+                                             ctypes.c_double(h), ctypes.c_double(r), _p(var), _p(A), _p(b), _p(now))
+        assert rc == 0 and var[0] == 6
+        assert np.array_equal(now[1, :2], info[1][:2])                          # box 1, advanced to step 1, is the sensed one
+        eA, eb = host_rows(host, w.static_A[:1], w.static_b[:1], now[None, 1:2], [Ts], N, h, r)
+        assert np.array_equal(A, eA[0]) and np.array_equal(b, eb[0]), (h, r)
+        if h == 0.0 and r == 0.0:
+            from tests.test_rollout_stop_core import expected_box_rows
+            xA, xb = expected_box_rows(1)
+            assert np.array_equal(A[:, Ms:], xA) and np.array_equal(b[:, Ms:], xb)
+
+
+# ------------------------------------------------------------------------------------------------------------ guarantee
+def car_polygon(p, ego=EGO):
+    """kkt_check.car_corners: the footprint at pose p, [4,2] in order"""
+    L, W = ego[0] + ego[2], ego[1] + ego[3]
+    off = L / 2 - ego[2]
+    c, s = math.cos(p[2]), math.sin(p[2])
+    cx, cy = p[0] + c * off, p[1] + s * off
+    return np.array([(cx + a * c * L / 2 - e * s * W / 2, cy + a * s * L / 2 + e * c * W / 2) for a, e in ((1, 1), (1, -1), (-1, -1), (-1, 1))])
+
+
+def box_polygon(cx, cy, c, s, length, width):
+    return np.array(rect_vertices(cx, cy, c, s, length, width))
+
+
+def _seg_dist(p, a, b):
+    ab = b - a
+    t = min(1.0, max(0.0, float((p - a) @ ab) / max(float(ab @ ab), 1e-300)))
+    return float(np.linalg.norm(p - (a + t * ab)))
+
+
+def signed_distance(P, Q):
+    """two convex polygons (vertices in order, either orientation): Euclidean distance when separated, minus the
+    penetration depth (largest separating-axis value over the edge normals of both) when not"""
+    best = -math.inf
+    for X, Y in ((P, Q), (Q, P)):
+        ctr = X.mean(axis=0)
+        for i in range(len(X)):
+            e = X[(i + 1) % len(X)] - X[i]
+            n = np.array([e[1], -e[0]]) / np.linalg.norm(e)
+            if (ctr - X[i]) @ n > 0:
+                n = -n                                                           # outward
+            best = max(best, float(((Y - X[i]) @ n).min()))
+    if best <= 0.0:
+        return best
+    return min(min(_seg_dist(p, Y[i], Y[(i + 1) % len(Y)]) for p in X for i in range(len(Y))) for X, Y in ((P, Q), (Q, P)))
+
+
+def epsilon(info, Ts, h, r, dmin=DMIN, ego=EGO):
+    """eps of csrc/obca_rollout_core.h (moving_box_rows): tau (1 + dmin / 2 + 3 (L + W) / 2 + a (L' + W') + sqrt 2 + r_max)"""
+    L, W = ego[0] + ego[2], ego[1] + ego[3]
+    off = L / 2 - ego[2]
+    r_max = math.hypot(abs(off) + L / 2, W / 2)
+    _, _, Lb, Wb = swept_rectangle(info, Ts, 0, h, r)
+    a = max(np.linalg.norm(expected_rows(info, Ts, kk, h, r)[0], axis=1).max() for kk in (0, 1))
+    return TAU * (1 + dmin / 2 + 1.5 * (L + W) + a * (Lb + Wb) + math.sqrt(2) + r_max), r_max
+
+
+def check_guarantee(out, w, h, r, n_sub=N_SUB, dmin=DMIN):
+    """every (rollout, step s, box j) with a feasible obca_mpc6 / obca_mpc8 step and box j sensed at s: all n_sub + 1 samples
+    of interval s at least dmin + r - h delta_s - eps from box j.  Returns the pairs checked per rollout and the smallest
+    (distance - bound) seen."""
+    pairs = np.zeros(w.batch, int)
+    worst = math.inf
+    for b in range(w.batch):
+        for s in range(STEPS):
+            if out["variant"][b, s] not in (6, 8) or out["status"][b, s] not in (0, 1):
+                continue
+            assert s < out["steps"][b]                                          # a feasible step is applied
+            p0, p1 = out["x_closed"][b, s], out["x_closed"][b, s + 1]
+            T = out["T_closed"][b, s]
+            for j in range(w.n_dyn):
+                if out["dyn"][b, s, j, 3] != 1.0:
+                    continue
+                info = w.dyn[b, j]
+                eps, r_max = epsilon(info, T, h, r, dmin)
+                delta = math.hypot(p1[0] - p0[0], p1[1] - p0[1]) + r_max * abs(p1[2] - p0[2])
+                bound = dmin + r - h * delta - eps
+                c0 = out["dyn"][b, s, j, :2]
+                c1 = c0 + T * info[5] * info[11:13]                             # the harness's update law to knot s + 1
+                for q in range(n_sub + 1):
+                    u = q / n_sub
+                    d = signed_distance(car_polygon(p0 + u * (p1 - p0)),
+                                        box_polygon(*(c0 + u * (c1 - c0)), info[11], info[12], info[3], info[4]))
+                    worst = min(worst, d - bound)
+                    assert d >= bound, (b, s, j, q, d, bound, delta)
+                pairs[b] += 1
+    return pairs, worst
+
+
+def test_signed_distance_of_the_test_itself():
+    sq = lambda x, y, h: np.array([(x - h, y - h), (x + h, y - h), (x + h, y + h), (x - h, y + h)])
+    assert signed_distance(sq(0, 0, 1), sq(3, 0, 1)) == pytest.approx(1.0)
+    assert signed_distance(sq(0, 0, 1), sq(3, 3, 1)) == pytest.approx(math.sqrt(2))
+    assert signed_distance(sq(0, 0, 1), sq(1.5, 0.2, 1)) == pytest.approx(-0.5)
+    assert signed_distance(sq(0, 0, 1), sq(2, 0, 1)) == pytest.approx(0.0, abs=1e-15)
+
+
+def test_clearance_between_knots_on_the_host_core(host):
+    w = pack_worlds([make_world_c5(i) for i in range(GUARANTEE_WORLDS)])
+    rc, out = run(host, w, 0.5, 0.5)
+    assert rc == 0
+    pairs, worst = check_guarantee(out, w, 0.5, 0.5)
+    print("pairs per world", pairs.tolist(), "smallest distance - bound", worst)
+    assert (pairs > 0).sum() * 2 >= w.batch, pairs
+
+
+# ------------------------------------------------------------------------------------------------------ Python arguments
+@pytest.mark.parametrize("kw", [dict(swept_rows={"half_window": 0.5, "margin": 0.5, "extra": 1}, exact_sensing=True),
+                                dict(swept_rows={"margin": 0.5}, exact_sensing=True),
+                                dict(swept_rows=0.5, exact_sensing=True),
+                                dict(swept_rows={"half_window": 0.5, "margin": 0.5}),
+                                dict(swept_rows={"half_window": 0.5}, exact_sensing=False),
+                                dict(swept_rows={"half_window": 1.5}, exact_sensing=True),
+                                dict(swept_rows={"half_window": -0.1}, exact_sensing=True),
+                                dict(swept_rows={"half_window": 0.5, "margin": 2.5}, exact_sensing=True),
+                                dict(swept_rows={"half_window": 0.5, "margin": -1.0}, exact_sensing=True),
+                                dict(swept_rows={"half_window": math.nan}, exact_sensing=True),
+                                dict(swept_rows={"half_window": 0.5, "margin": math.inf}, exact_sensing=True)])
+def test_python_arguments_are_checked_before_anything_is_created(kw):
+    w = pack_worlds([make_world_c5(0)])
+    with pytest.raises(ValueError, match="swept_rows"):
+        DeviceRollouts(w, N=N, **kw)

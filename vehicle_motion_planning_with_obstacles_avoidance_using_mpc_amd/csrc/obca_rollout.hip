@@ -189,6 +189,8 @@ extern "C" int obca_rollouts_reset(obca_rollouts* r, const double* start, const 
             !obca_resolve_starts(&probe, params->start_order, params->single_start, params->patience, params->retry_iter, r->dims.N, params->dodge, params->terminal_screen))
             return OBCA_E_INVAL;
     }
+    // swept rows are built from the sensed box's own rectangle and velocity together: only exact sensing pairs the two
+    if ((r->D.sweep_h != 0.0 || r->D.sweep_r != 0.0) && !r->D.exact_sense) return OBCA_E_INVAL;
     ObcaDeviceGuard guard(r->dims.device);
     if (!guard.ok) return OBCA_E_HIP;
     hipStream_t s = (hipStream_t)hip_stream;
@@ -313,6 +315,15 @@ extern "C" int obca_rollouts_set_collision_stop(obca_rollouts* r, int32_t n_sub,
 extern "C" int obca_rollouts_set_exact_sensing(obca_rollouts* r, int32_t on) {
     if (!r || (on != 0 && on != 1)) return OBCA_E_INVAL;
     r->D.exact_sense = on;
+    r->ready = false;                      // takes effect with the next obca_rollouts_reset
+    return OBCA_OK;
+}
+
+extern "C" int obca_rollouts_set_swept_rows(obca_rollouts* r, double half_window, double margin) {
+    // checked before anything is touched: a refused call has no side effect (NaN fails both comparisons)
+    if (!r || !(half_window >= 0.0 && half_window <= 1.0) || !(margin >= 0.0 && margin <= 2.0)) return OBCA_E_INVAL;
+    r->D.sweep_h = half_window;
+    r->D.sweep_r = margin;
     r->ready = false;                      // takes effect with the next obca_rollouts_reset
     return OBCA_OK;
 }

@@ -66,6 +66,8 @@ struct Dev {
     int32_t m_static[OBCA_MAX_OBST];   // row counts of the static obstacles (the audit's Scene)
     double ego[4];                     // the footprint of obca_params.ego
     double* clr;                       // [B, S] clearance of every measured interval, +inf elsewhere
+    // optional swept, inflated rows of the sensed boxes (obca_rollouts_set_swept_rows; moving_box_rows below): both zero = off
+    double sweep_h, sweep_r;
 };
 
 // one polygon edge -> one row [a0 a1 | b]; branch order and exact comparisons of src/model_obstacle.py:63-89
@@ -95,6 +97,68 @@ RO_FN void rect_vertices(double cx, double cy, double c, double s, double length
     V[1][0] = cx + l * c - w * s; V[1][1] = cy + l * s + w * c;
     V[2][0] = cx + l * c + w * s; V[2][1] = cy + l * s - w * c;
     V[3][0] = cx - l * c + w * s; V[3][1] = cy - l * s - w * c;
+}
+
+// The four rows [a0 a1 | b] of one moving rectangle at horizon stage kk (obca_rollouts_set_swept_rows, obca_moving_rows_batch).
+// info = the 13-double tuple with the box's PRESENT centre in info[0], info[1]; Ts_opt = the step length of the solve.
+//
+// h == 0 and r == 0 (off): the harness's rows of an exact-sensing step, operation for operation -- the vertices of the
+// rectangle where it is now, moved by kk * Ts_opt * v along the heading.
+//
+// Otherwise (h = half window in steps, r = margin in metres) the rectangle that covers the box, inflated by r, at every
+// stage time in [kk - h, kk + h]: the box translates along its own heading, so what it sweeps is a rectangle of the same
+// orientation, longer by 2 h |Ts_opt v|; the offset by r with mitred corners -- a superset of the inflation by a disc of
+// radius r -- makes it longer and wider by 2 r.  Centre (info[0] + kk Ts_opt v c, info[1] + kk Ts_opt v s), length
+// info[3] + 2 (h |Ts_opt v| + r), width info[4] + 2 r; vertices and rows by rect_vertices / edge_row as ever.
+//
+// What the closed loop gains (NOT reference behaviour; tests/test_rollout_swept_core.py checks it on the host core).  Take a
+// fixed-time step s (obca_mpc6 / obca_mpc8) that ends feasible, box j sensed at s, rows built with h >= 1/2.  The box
+// advances by the same Ts_opt v per step that separates the stages, so stage 1 of step s is centred on the box's position
+// at knot s + 1.  The stage-0 rectangle R0 covers the r-inflated box at the times [0, h] after knot s, the stage-1 rectangle
+// R1 at [1 - h, 1]: together the whole interval.  Let tau bound what a row of the solved problem is violated by
+// (obca_params.feas_tol for the elastic variables plus tol for the row residuals).  Rows of box j at one stage: lambda >= 0
+// [4], mu >= 0 [4], rotation G' mu + R(theta)' A' lambda = 0 [2], norm |A' lambda|^2 <= 1, distance
+// -g' mu + (A t - b)' lambda >= dmin with t = p + R(theta) (off, 0) the footprint's centre, G y <= g the footprint
+// (g = (L/2, W/2, L/2, W/2)).  For a footprint point e = t + R y and a point q of the rectangle (A q <= b), c = A' lambda:
+//     c'(e - q)  =  c' t - lambda' b  +  lambda' (b - A q)  +  c' R y
+//     lambda' (b - A q) >= -tau sum_j (b_j - A_j q) >= -tau a (L' + W')        lambda_j >= -tau; opposite rows of a rectangle
+//                                                                              of size L' x W' add up to a x its extent,
+//                                                                              a = the largest row norm (1 for an
+//                                                                              axis-parallel box)
+//     c' R y = (rho - G' mu)' y >= -g' mu - tau (L + W) / 2 - tau (L + W)      |rho_i| <= tau on the rotation rows;
+//                                                                              mu' (g - G y) >= -tau sum_i (g_i - G_i y)
+//     c'(e - q) >= dmin - tau (1 + 3 (L + W) / 2 + a (L' + W')),   |c| <= sqrt(1 + tau),   1 / sqrt(1 + tau) >= 1 - tau / 2
+// so the footprint at the solver's stage pose is at least dmin - tau (1 + dmin / 2 + 3 (L + W) / 2 + a (L' + W')) away from
+// the stage's rectangle.  The stage-1 pose IS knot s + 1; the stage-0 pose is knot s up to the elastic initial-state rows
+// (tau on x, y, theta: no footprint point moves by more than tau (sqrt 2 + r_max), r_max = audit::car_radius).  With
+//     eps = tau (1 + dmin / 2 + 3 (L + W) / 2 + a (L' + W') + sqrt 2 + r_max)
+// the footprint at either knot is at least D = dmin - eps > 0 away from that knot's rectangle.  A point at distance >= D from
+// a convex set that contains the r-dilation of the box is at least D + r from the box (step r from the box's nearest point
+// towards it: still inside the set).  Along the interpolated pose no footprint point is further than u delta_s from where it
+// is at knot s, nor than (1 - u) delta_s from where it is at knot s + 1 (delta_s = |dp| + r_max |dtheta| of interval s: the
+// audit's delta for the car alone, csrc/obca_audit_core.h), and the signed distance is 1-Lipschitz under that (same place).
+// Fractions u <= h lean on knot s and R0, u >= 1 - h on knot s + 1 and R1; with h >= 1/2 the nearer knot is never more
+// than delta_s / 2 away, and no more than h delta_s whichever side is taken:
+//     signed distance(car(u), box j at time u) >= dmin + r - h delta_s - eps         for every u in [0, 1].
+// Boxes the lidar gate does not see at step s, free-time steps and failed steps are promised nothing.
+RO_FN void moving_box_rows(const double* info, double Ts_opt, int kk, double h, double r, double* Ar, double* br) {
+    RO_EXACT
+    double V[4][2];                                  // (constant indices only: registers, no stack frame)
+    double sx = Ts_opt * info[5] * info[11] * (double)kk;
+    double sy = Ts_opt * info[5] * info[12] * (double)kk;
+    if (h == 0.0 && r == 0.0) {
+        rect_vertices(info[0], info[1], info[11], info[12], info[3], info[4], V);
+    } else {
+        rect_vertices(info[0] + sx, info[1] + sy, info[11], info[12], info[3] + 2 * (h * fabs(Ts_opt * info[5]) + r),
+                      info[4] + 2 * r, V);
+        sx = 0.0; sy = 0.0;
+    }
+    const double x0_ = V[0][0] + sx, y0_ = V[0][1] + sy, x1_ = V[1][0] + sx, y1_ = V[1][1] + sy;
+    const double x2_ = V[2][0] + sx, y2_ = V[2][1] + sy, x3_ = V[3][0] + sx, y3_ = V[3][1] + sy;
+    edge_row(x0_, y0_, x1_, y1_, Ar, br);
+    edge_row(x1_, y1_, x2_, y2_, Ar + 2, br + 1);
+    edge_row(x2_, y2_, x3_, y3_, Ar + 4, br + 2);
+    edge_row(x3_, y3_, x0_, y0_, Ar + 6, br + 3);
 }
 
 RO_FN bool at_goal(const Dev& D, int b) {
@@ -235,7 +299,8 @@ RO_FN void prepare(const Dev& D, int b) {
     D.term[3 * b] = x0[0] + 5; D.term[3 * b + 1] = 1.0; D.term[3 * b + 2] = 9.0;      // :371
 
     // S5/S4: static rows, then the first ns PRESENT rectangles (q8) moved with the SENSED obstacles' velocities;
-    // exact_sense: the j-th SENSED rectangle itself (its position in the present list: vj)
+    // exact_sense: the j-th SENSED rectangle itself (its position in the present list: vj); sweep_h / sweep_r: that
+    // rectangle swept over the stage's time window and inflated (moving_box_rows)
     const int g = ns, Mg = D.Ms + 4 * ns;
     double* Ag = D.A[g] + (size_t)b * Nf1 * Mg * 2;
     double* bg = D.b[g] + (size_t)b * Nf1 * Mg;
@@ -247,6 +312,10 @@ RO_FN void prepare(const Dev& D, int b) {
         for (int j = 0; j < ns; ++j) {
             const int pj = (int)((sensed >> (4 * j)) & 15u);
             const double* info = D.dyn + ((size_t)b * nd + pj) * DYN_W;
+            if (D.sweep_h != 0.0 || D.sweep_r != 0.0) {                  // swept, inflated rows (exact sensing: box pj's own)
+                moving_box_rows(info, Ts_opt, kk, D.sweep_h, D.sweep_r, Ak + 2 * (D.Ms + 4 * j), bk + D.Ms + 4 * j);
+                continue;
+            }
             int vj = j;
             if (D.exact_sense)
                 for (int q = 0; q < np; ++q)

@@ -131,6 +131,23 @@ def _stop_options(collision_stop):
     return cs if cs["n_sub"] != 0 else None
 
 
+def _swept_options(swept_rows, exact_sensing):
+    """None | {half_window, margin=0.0} -> None or the full dict (both zero: off); needs exact_sensing"""
+    if swept_rows is None:
+        return None
+    if not isinstance(swept_rows, dict) or set(swept_rows) - {"half_window", "margin"} or "half_window" not in swept_rows:
+        raise ValueError("swept_rows: a dict {half_window, margin=0.0}, got %s" %
+                         (sorted(swept_rows) if isinstance(swept_rows, dict) else type(swept_rows).__name__))
+    sw = {"half_window": float(swept_rows["half_window"]), "margin": float(swept_rows.get("margin", 0.0))}
+    if not (0.0 <= sw["half_window"] <= 1.0) or not (0.0 <= sw["margin"] <= 2.0):
+        raise ValueError("swept_rows: half_window in [0, 1] and margin in [0, 2], got %r" % (sw,))
+    if sw["half_window"] == 0.0 and sw["margin"] == 0.0:
+        return None
+    if not exact_sensing:
+        raise ValueError("swept_rows needs exact_sensing=True: the rows are built from the sensed box's own rectangle and velocity")
+    return sw
+
+
 class RolloutCohorts:
     """The batch cut into ``cohorts`` independent lock-step groups, each on its own HIP stream.  One step of a
     group lasts as long as its slowest solve (an infeasible obca_mpc6 runs to max_iter = 1000 before the obca_mpc8
@@ -189,7 +206,7 @@ class DeviceRollouts:
     ``run()`` all of them; ``read()`` returns state and history (torch tensors on the device)."""
 
     def __init__(self, worlds, N=6, params=None, Ts0=0.1, max_steps=30, device=None, warm_start=None, N_fix=None,
-                 collision_stop=None, exact_sensing=False):
+                 collision_stop=None, exact_sensing=False, swept_rows=None):
         """N: horizon of the free-time problem, N_fix (default N): of the fixed-time problems (the reference's committed
         default is N_free = N_fix = 6, src/closed_loop.py:84,91; N_fix must be a multiple of N with N_fix - 5 <= N).
         params: None = the reference's controller constants with the position box of the worlds (setting.xL / xU).
@@ -199,7 +216,11 @@ class DeviceRollouts:
         rollout with flag "collision" when the interval of its last applied step comes closer than `clearance` to an
         obstacle, every present moving box counted (obca_rollouts_set_collision_stop); read() then adds "clearance".
         exact_sensing: hand the solver each sensed box's own rectangle instead of the reference's pairing (NOT reference
-        behaviour; obca_rollouts_set_exact_sensing)."""
+        behaviour; obca_rollouts_set_exact_sensing).
+        swept_rows: None (default) = off; a dict {half_window, margin=0.0} = every sensed box's rows cover the box, inflated
+        by `margin` metres, over `half_window` steps on either side of each stage (NOT reference behaviour;
+        obca_rollouts_set_swept_rows; needs exact_sensing)."""
+        self.swept_rows = _swept_options(swept_rows, exact_sensing)     # (checked before anything is created)
         import torch
         if not torch.cuda.is_available():
             raise RuntimeError("DeviceRollouts needs a ROCm GPU; there is no CPU fallback on the product path")
@@ -225,6 +246,8 @@ class DeviceRollouts:
             _lib.check(self.lib.obca_rollouts_set_collision_stop(self._h, cs["n_sub"], cs["clearance"], int(cs["certified"])))
         if exact_sensing:
             _lib.check(self.lib.obca_rollouts_set_exact_sensing(self._h, 1))
+        if self.swept_rows is not None:
+            _lib.check(self.lib.obca_rollouts_set_swept_rows(self._h, self.swept_rows["half_window"], self.swept_rows["margin"]))
         self.reset()
 
     def _stream(self):

@@ -202,6 +202,38 @@ class BatchSolver:
         return out
 
 
+def moving_rows(static_A, static_b, boxes, Ts, N, half_window=0.0, margin=0.0, device=None):
+    """Obstacle rows of B instances with moving rectangles, built on the GPU (obca_moving_rows_batch): static_A [B,Ms,2],
+    static_b [B,Ms], boxes [B,n_box,13] (the closed loop's tuple: centre now 0, 1; length 3, width 4; speed 5; cos / sin of
+    the heading 11, 12), Ts [B] or a float.  Returns (A [B,N+1,M,2], b [B,N+1,M]), M = Ms + 4 n_box, device tensors on the
+    current stream that feed ``BatchSolver.solve`` of a handle with m = static edge counts + [4] * n_box.  half_window
+    (steps) / margin (metres) > 0: every stage's rectangle covers the box, inflated by the margin, over the half window on
+    either side of the stage (include/obca_mpc.h: obca_rollouts_set_swept_rows); both 0: the box itself at each stage."""
+    if not torch.cuda.is_available():
+        raise RuntimeError("moving_rows needs a ROCm GPU; there is no CPU fallback on the product path")
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    lib = _lib.load()
+    t = lambda a: torch.as_tensor(a, dtype=torch.float64, device=dev).contiguous()
+    static_A, static_b, boxes = t(static_A), t(static_b), t(boxes)
+    B, n_box = int(boxes.shape[0]), int(boxes.shape[1])
+    Ms = int(static_b.shape[1])
+    if tuple(static_A.shape) != (B, Ms, 2) or tuple(static_b.shape) != (B, Ms) or tuple(boxes.shape) != (B, n_box, 13):
+        raise ValueError("expected static_A [B,Ms,2], static_b [B,Ms], boxes [B,n_box,13], got %s, %s, %s" %
+                         (tuple(static_A.shape), tuple(static_b.shape), tuple(boxes.shape)))
+    Ts = t(Ts).expand(B).contiguous() if torch.as_tensor(Ts).dim() == 0 else t(Ts)
+    if tuple(Ts.shape) != (B,):
+        raise ValueError("expected Ts [B] or a scalar, got %s" % (tuple(Ts.shape),))
+    M = Ms + 4 * n_box
+    A = torch.empty(B, int(N) + 1, M, 2, dtype=torch.float64, device=dev)
+    b = torch.empty(B, int(N) + 1, M, dtype=torch.float64, device=dev)
+    ptr = lambda x: ctypes.c_void_p(x.data_ptr()) if x.numel() else None
+    _lib.check(lib.obca_moving_rows_batch(B, int(N), Ms, n_box, ptr(static_A), ptr(static_b), ptr(boxes), ptr(Ts),
+                                          float(half_window), float(margin), ptr(A), ptr(b),
+                                          dev.index if dev.index is not None else torch.cuda.current_device(),
+                                          ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+    return A, b
+
+
 def pack_reference_call(variant, Ts, N, x0, xref, nObs, vObs, AObs, bObs, u0, terminal_set=None):
     """One reference-style call -> the canonical per-instance arrays (numpy).
 
