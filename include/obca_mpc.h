@@ -431,6 +431,31 @@ int obca_plan_clearance(const double ego[4], int32_t n_obs, const int32_t* m, in
                         double* min_clear, int32_t* arg_stage, int32_t* arg_obst, double* stage_obst,
                         int32_t device, void* hip_stream);
 
+/* Swept audit of obca_solve_batch outputs (obca_mpc 0.9): the plan between its knots.  Arguments, shapes and the host /
+ * device split as obca_plan_clearance.  Interval s (0 <= s < N) joins stage s to stage s + 1; n_sub + 1 samples, both
+ * knots included, are measured at the fractions t = j / n_sub (n_sub = 1: the knots only).  The pose is interpolated
+ * linearly in (x, y, theta); obstacle rows entry by entry, A(t) = A_s + t (A_s+1 - A_s), b likewise -- exact for a set that
+ * translates at constant velocity (the harness's boxes, obca_moving_rows_batch's rectangles); the knots use the stages'
+ * own words.  Where variant[b] == 4 every sample is measured against stage 0's rows.  Outputs (DEVICE, [B] unless noted):
+ *   min_clear        smallest sample;  arg_interval / arg_obst: its interval and obstacle (ties to the lowest interval,
+ *                    then the lowest obstacle: a minimum on the knot shared by intervals s and s + 1 reports s)
+ *   lower_bound      certified lower bound of the signed distance over the continuous interpolated motion: min over
+ *                    sub-intervals of min((d_j-1 + d_j - delta) / 2, d_j-1, d_j), delta = |dp| + r_max |dtheta| of the
+ *                    sub-interval + the largest |dc_i| / n_sub, dc_i = the least-squares (minimum-norm) solution of
+ *                    A_s,i dc = b_s+1,i - b_s,i.  Certified for translating obstacles only: NaN when some obstacle's A
+ *                    changes by more than 1e-9 max |A_s,i| or the residual exceeds 1e-9 (1 + max |b|) in some interval
+ *                    (derivation in csrc/obca_audit_core.h)
+ *   first_collision  first interval with a sample < 0, or -1
+ *   interval_min     [B,N] or NULL: smallest sample per interval
+ * NaN as in obca_plan_clearance: a sample whose pose, rows or distance is not finite measures NaN and NaN ranks below
+ * every number, in min_clear (arg_interval the first interval touching it), interval_min and lower_bound.
+ * 1 <= n_sub <= 65536; otherwise the checks of obca_plan_clearance. */
+int obca_plan_sweep(const double ego[4], int32_t n_obs, const int32_t* m, int32_t N, int32_t B,
+                    const int32_t* variant, const double* x, const double* A, const double* b, int32_t n_sub,
+                    double* min_clear, double* lower_bound, int32_t* arg_interval, int32_t* arg_obst,
+                    int32_t* first_collision, double* interval_min /* [B,N] or NULL */,
+                    int32_t device, void* hip_stream);
+
 /* Rollout audit from the handle's own device state (after obca_rollouts_reset; ego and dmin of that reset).  Rollout
  * b has the knots x_closed[b, 0..steps[b]]; interval s joins knot s to s + 1 (steps[b] == 0: knot 0 alone).  Within
  * an interval the pose is interpolated linearly in (x, y, theta) and n_sub + 1 >= 2 samples, both knots included, are
@@ -468,7 +493,8 @@ int obca_moving_rows_batch(int32_t B, int32_t N, int32_t Ms, int32_t n_box, cons
                            int32_t device, void* hip_stream);
 
 const char* obca_strerror(int code);
-/* "obca_mpc 0.8 (gfx950)": 0.8 = opt-in swept, inflated rows of moving boxes (obca_rollouts_set_swept_rows, obca_moving_rows_batch);
+/* "obca_mpc 0.9 (gfx950)": 0.9 = swept audit of batched plans (obca_plan_sweep);
+ * 0.8 = opt-in swept, inflated rows of moving boxes (obca_rollouts_set_swept_rows, obca_moving_rows_batch);
  * 0.7 = opt-in collision stop (OBCA_DONE_COLLISION, obca_rollouts_set_collision_stop,
  * obca_rollouts_read_clearance) and exact sensing (obca_rollouts_set_exact_sensing); 0.6 = the answer of an exhausted start ladder is the most informative pass's (obca_params: the starts of a
  * solve), the second-order correction's scratch in LDS where it costs no occupancy; 0.5 = obca_params.struct_size (first member; obca_params_init), the dodge rung and the terminal-set screen,

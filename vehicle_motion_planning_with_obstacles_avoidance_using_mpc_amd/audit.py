@@ -1,6 +1,8 @@
 """Collision audit on the GPU: true clearance of batched plans and closed-loop rollouts, in fp64.
 
-``plan_clearance`` measures ``BatchSolver`` outputs against the rows the solver was given (obca_plan_clearance);
+``plan_clearance`` measures ``BatchSolver`` outputs against the rows the solver was given (obca_plan_clearance), at the
+knots; ``plan_sweep`` measures them between the knots as well and bounds the continuous motion from below
+(obca_plan_sweep), ``plan_summary`` turns a sweep into counts;
 ``DeviceRollouts.audit`` / ``RolloutCohorts.audit`` measure closed-loop rollouts against the static obstacles and every
 present moving box, between the knots too (obca_rollouts_audit); ``summary`` turns an audit into counts.  Read-only: no
 solver or rollout state changes.  Geometry and the certified bound: csrc/obca_audit_core.h.
@@ -46,6 +48,66 @@ def plan_clearance(x, A, b, m, ego=DEFAULT_EGO, variant=None, per_stage=False, d
     _lib.check(lib.obca_plan_clearance(ego_c, len(m), m_c, N1 - 1, B, p(var), p(x), p(A), p(b), p(out["min_clear"]),
                                        p(out["arg_stage"]), p(out["arg_obst"]), p(out.get("stage_obst")),
                                        dev.index if dev.index is not None else torch.cuda.current_device(), stream))
+    return out
+
+
+def plan_sweep(x, A, b, m, n_sub=16, ego=DEFAULT_EGO, variant=None, per_interval=False, device=None):
+    """plan_clearance's arguments; every interval stage s -> s + 1 is measured at n_sub + 1 samples (n_sub = 1: the knots
+    only), pose and obstacle rows interpolated linearly.  Returns a dict of device tensors on the current stream:
+    min_clear, lower_bound (certified for translating obstacles, else NaN), arg_interval, arg_obst, first_collision [B]
+    and, with per_interval, interval_min [B,N]."""
+    import torch
+    dev = torch.device(device) if device is not None else (x.device if isinstance(x, torch.Tensor) and x.is_cuda else
+                                                           torch.device("cuda", torch.cuda.current_device()))
+    lib = _lib.load()
+    m = [int(v) for v in m]
+    x = _device_tensor(x, torch.float64, dev)
+    B, N1 = int(x.shape[0]), int(x.shape[2])
+    M = sum(m)
+    x = x.reshape(B, 3, N1)
+    A = _device_tensor(A, torch.float64, dev).reshape(B, N1, M, 2)
+    b = _device_tensor(b, torch.float64, dev).reshape(B, N1, M)
+    var = None if variant is None else _device_tensor(variant, torch.int32, dev).reshape(B)
+    out = {"min_clear": torch.empty(B, dtype=torch.float64, device=dev),
+           "lower_bound": torch.empty(B, dtype=torch.float64, device=dev),
+           "arg_interval": torch.empty(B, dtype=torch.int32, device=dev),
+           "arg_obst": torch.empty(B, dtype=torch.int32, device=dev),
+           "first_collision": torch.empty(B, dtype=torch.int32, device=dev)}
+    if per_interval:
+        out["interval_min"] = torch.empty(B, max(N1 - 1, 0), dtype=torch.float64, device=dev)
+    p = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
+    ego_c = (ctypes.c_double * 4)(*[float(v) for v in ego])
+    m_c = (ctypes.c_int32 * max(len(m), 1))(*m)
+    stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    _lib.check(lib.obca_plan_sweep(ego_c, len(m), m_c, N1 - 1, B, p(var), p(x), p(A), p(b), int(n_sub), p(out["min_clear"]),
+                                   p(out["lower_bound"]), p(out["arg_interval"]), p(out["arg_obst"]), p(out["first_collision"]),
+                                   p(out.get("interval_min")), dev.index if dev.index is not None else torch.cuda.current_device(),
+                                   stream))
+    return out
+
+
+def plan_summary(sweep, knots=None):
+    """counts and worst values of a plan sweep (plan_sweep): plans with a sampled collision, with a negative certified
+    bound, with a bound that is not certified (NaN) and, given the knot audit of the same plans (plan_clearance), plans
+    that are clear at every knot and collide between them.  Plans that measure NaN are counted apart and are not the worst."""
+    g = lambda d, k: np.asarray(d[k].cpu() if hasattr(d[k], "cpu") else d[k])
+    mc, lb, fc = g(sweep, "min_clear"), g(sweep, "lower_bound"), g(sweep, "first_collision")
+    out = {"plans": int(len(mc)),
+           "collisions": int((mc < 0).sum()),
+           "negative_lower_bound": int((lb < 0).sum()),
+           "uncertified_lower_bound": int(np.isnan(lb).sum()),
+           "not_finite": int(np.isnan(mc).sum()),
+           "first_collision_interval_histogram": np.bincount(fc[fc >= 0]).tolist()}
+    if knots is not None:
+        kc = g(knots, "min_clear")
+        out["collisions_at_a_knot"] = int((kc < 0).sum())
+        out["collisions_between_clear_knots"] = int(((mc < 0) & (kc >= 0)).sum())
+    if np.isfinite(mc).any():
+        worst = int(np.nanargmin(mc))
+        out.update({"worst_min_clear": float(mc[worst]), "worst_plan": worst,
+                    "worst_interval": int(g(sweep, "arg_interval")[worst]), "worst_obstacle": int(g(sweep, "arg_obst")[worst])})
+    if np.isfinite(lb).any():
+        out["worst_lower_bound"] = float(np.nanmin(lb))
     return out
 
 

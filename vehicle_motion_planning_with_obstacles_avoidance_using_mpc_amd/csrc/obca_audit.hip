@@ -1,11 +1,11 @@
-// obca_audit.hip -- collision audit (obca_plan_clearance, obca_rollouts_audit of include/obca_mpc.h): true clearance of
-// batched plans and of closed-loop rollouts in fp64, from the geometry core csrc/obca_audit_core.h.  Read-only: the
+// obca_audit.hip -- collision audit (obca_plan_clearance, obca_plan_sweep, obca_rollouts_audit of include/obca_mpc.h): true
+// clearance of batched plans (at the knots; swept between them) and of closed-loop rollouts in fp64, from the geometry core csrc/obca_audit_core.h.  Read-only: the
 // kernels only read solver outputs and rollout state and write the caller's output buffers.
 //
 // Layout: the lanes of a wavefront are cut into segments of seg = next power of two >= the items of one instance (plan:
-// its N + 1 stages, rollout: its max_steps intervals; at most 64), one instance per segment; a lane walks the items
-// sub, sub + seg, ... of its instance (for a rollout: each interval's samples in order, both ends of every sub-interval
-// in registers), then the segment reduces min / arg-min with xor shuffles that never leave it.
+// its N + 1 stages, plan sweep: its N intervals, rollout: its max_steps intervals; at most 64), one instance per segment;
+// a lane walks the items sub, sub + seg, ... of its instance (for an interval: its samples in order, both ends of every
+// sub-interval in registers), then the segment reduces min / arg-min with xor shuffles that never leave it.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include "obca_device.h"
@@ -32,6 +32,18 @@ struct PlanArgs {
     double* stage_obst;
 };
 
+struct SweepArgs {
+    int32_t B, N, n_obs, M;
+    int32_t m[OBCA_MAX_OBST], off[OBCA_MAX_OBST];
+    double ego[4];
+    int32_t seg, log_seg, n_sub;
+    const int32_t* variant;
+    const double *x, *A, *b;
+    double *min_clear, *lower_bound;
+    int32_t *arg_interval, *arg_obst, *first_collision;
+    double* interval_min;
+};
+
 struct AuditArgs {
     rollout::Dev D;
     int32_t n_static;
@@ -56,6 +68,11 @@ __device__ inline void seg_argmin(double& v, int& s, int& o, int seg) {
 
 __device__ inline double seg_min(double v, int seg) {
     for (int w = seg >> 1; w > 0; w >>= 1) v = fmin(v, __shfl_xor(v, w, WAVE));
+    return v;
+}
+
+__device__ inline double seg_min_nan(double v, int seg) {      // a NaN in the segment wins (audit::min_nan)
+    for (int w = seg >> 1; w > 0; w >>= 1) v = audit::min_nan(v, __shfl_xor(v, w, WAVE));
     return v;
 }
 
@@ -96,6 +113,43 @@ __global__ void __launch_bounds__(BLOCK) plan_clearance_kernel(PlanArgs P) {
         P.min_clear[inst] = best;
         P.arg_stage[inst] = bs;
         P.arg_obst[inst] = bo;
+    }
+}
+
+// one lane per (instance, interval): audit::plan_interval on the plan's own arrays, the rows of both stages read in place
+__global__ void __launch_bounds__(BLOCK) plan_sweep_kernel(SweepArgs P) {
+    const int64_t gl = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t inst = gl >> P.log_seg;
+    const int sub = (int)(gl & (P.seg - 1));
+    const bool live = inst < P.B;                               // whole segments are live or not: the shuffles stay uniform
+    const int N1 = P.N + 1;
+    audit::PlanSweepAcc acc;
+    audit::plan_acc_init(acc);
+    if (live) {
+        const int v = P.variant ? P.variant[inst] : 0;
+        audit::PlanScene sc;
+        sc.ego = P.ego; sc.n_obs = P.n_obs; sc.m = P.m; sc.off = P.off;
+        const double* xb = P.x + (size_t)inst * 3 * N1;
+        for (int s = sub; s < P.N; s += P.seg) {
+            const double p0[3] = {xb[s], xb[N1 + s], xb[2 * N1 + s]};
+            const double p1[3] = {xb[s + 1], xb[N1 + s + 1], xb[2 * N1 + s + 1]};
+            const size_t k0 = (size_t)inst * N1 + ((v == 4) ? 0 : s);       // obca_mpc4 reads stage 0's rows at every stage
+            const size_t k1 = (v == 4) ? k0 : k0 + 1;
+            const audit::PlanIntervalResult R = audit::plan_interval<OBCA_MAX_EDGES>(
+                sc, p0, p1, P.A + k0 * P.M * 2, P.b + k0 * P.M, P.A + k1 * P.M * 2, P.b + k1 * P.M, P.n_sub);
+            if (P.interval_min) P.interval_min[(size_t)inst * P.N + s] = R.min_val;
+            audit::plan_acc_add(acc, s, R);
+        }
+    }
+    seg_argmin(acc.best, acc.bs, acc.bo, P.seg);
+    acc.lower = seg_min_nan(acc.lower, P.seg);
+    acc.coll = seg_min_nonneg(acc.coll, P.seg);
+    if (live && sub == 0) {
+        P.min_clear[inst] = acc.best;
+        P.lower_bound[inst] = acc.lower;
+        P.arg_interval[inst] = acc.bs;
+        P.arg_obst[inst] = acc.bo;
+        P.first_collision[inst] = acc.coll;
     }
 }
 
@@ -219,6 +273,39 @@ extern "C" int obca_plan_clearance(const double ego[4], int32_t n_obs, const int
     if (!guard.ok) return OBCA_E_HIP;
     const int64_t lanes = (int64_t)B * P.seg;
     hipLaunchKernelGGL(plan_clearance_kernel, dim3((unsigned)((lanes + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0,
+                       (hipStream_t)hip_stream, P);
+    return hipGetLastError() == hipSuccess ? OBCA_OK : OBCA_E_HIP;
+}
+
+extern "C" int obca_plan_sweep(const double ego[4], int32_t n_obs, const int32_t* m, int32_t N, int32_t B,
+                               const int32_t* variant, const double* x, const double* A, const double* b, int32_t n_sub,
+                               double* min_clear, double* lower_bound, int32_t* arg_interval, int32_t* arg_obst,
+                               int32_t* first_collision, double* interval_min, int32_t device, void* hip_stream) {
+    // every argument is checked before the first HIP call: a refused call has no side effect
+    if (!ego_ok(ego) || n_obs < 1 || n_obs > OBCA_MAX_OBST || !m || N < 1 || N > (1 << 20) || B < 1 || device < 0 ||
+        n_sub < 1 || n_sub > (1 << 16) || !x || !A || !b || !min_clear || !lower_bound || !arg_interval || !arg_obst ||
+        !first_collision)
+        return OBCA_E_INVAL;
+    SweepArgs P;
+    P.M = 0;
+    for (int i = 0; i < OBCA_MAX_OBST; ++i) {
+        P.m[i] = 0; P.off[i] = 0;
+        if (i >= n_obs) continue;
+        if (m[i] < 1 || m[i] > OBCA_MAX_EDGES) return OBCA_E_INVAL;
+        P.m[i] = m[i];
+        P.off[i] = P.M;
+        P.M += m[i];
+    }
+    P.B = B; P.N = N; P.n_obs = n_obs; P.n_sub = n_sub;
+    for (int j = 0; j < 4; ++j) P.ego[j] = ego[j];
+    segment_of(N, &P.seg, &P.log_seg);
+    P.variant = variant; P.x = x; P.A = A; P.b = b;
+    P.min_clear = min_clear; P.lower_bound = lower_bound; P.arg_interval = arg_interval; P.arg_obst = arg_obst;
+    P.first_collision = first_collision; P.interval_min = interval_min;
+    ObcaDeviceGuard guard(device);
+    if (!guard.ok) return OBCA_E_HIP;
+    const int64_t lanes = (int64_t)B * P.seg;
+    hipLaunchKernelGGL(plan_sweep_kernel, dim3((unsigned)((lanes + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0,
                        (hipStream_t)hip_stream, P);
     return hipGetLastError() == hipSuccess ? OBCA_OK : OBCA_E_HIP;
 }

@@ -303,6 +303,180 @@ AU_FN IntervalResult audit_interval(const Scene& S, const double* p0, const doub
     return R;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Swept audit of one plan interval (obca_plan_sweep): stage s -> s + 1 of an obca_solve_batch plan, whose obstacles are
+// rows per stage (A0 / b0 [M,2], [M] of stage s, A1 / b1 of stage s + 1; obca_mpc4 reads stage 0's rows at every stage, so
+// its caller passes stage 0's rows as both ends).  Sample j = 0..n_sub, both knots included: the pose as sample_pose
+// interpolates it, obstacle i's rows entry by entry, A(t) = A0 + t (A1 - A0), b(t) = b0 + t (b1 - b0), t = j / n_sub; at
+// j = 0 and j = n_sub the stage's own words.  The distance is plan_distance with its NaN rule.
+//
+// What the interpolated rows are.  Let K = {q : A q <= b0} and let stage s + 1 hold the rows of K + c, a translation:
+// A (q - c) <= b0, that is A q <= b0 + A c, so A1 = A and db = b1 - b0 = A c.  Then b(t) = b0 + A (t c): the interpolated
+// rows are exactly those of K + t c, the set moving at constant velocity -- the harness's boxes and the swept, inflated
+// rectangles of obca_moving_rows_batch at any half_window / margin alike (their size does not change along the horizon).
+// Certified bound.  db determines the moved set: every c' with A c' = db gives the same rows, hence the same set, so the
+// displacement to charge is the smallest such c' -- the least-squares solution dc of A dc = db over the obstacle's rows
+// (normal equations G dc = A^T db, G = A^T A, 2 x 2), of minimum norm where G is singular (one row, or parallel rows: a
+// half-plane or a strip moves along its normal only, dc = A^T db / trace G).  Over a sub-interval the set then moves by
+// |dc| / n_sub, every point of the car by at most |dp| + r_max |dtheta| of the sub-interval (header of this file), and
+// the signed distance is 1-Lipschitz under both (same place), so with delta their sum and end values d_j-1, d_j
+//     d(u) >= min((d_j-1 + d_j - delta) / 2, d_j-1, d_j)         for every fraction u of the sub-interval,
+// sub_bound's formula, and the minimum over the obstacles is bounded by the largest |dc| among them.  The argument needs
+// a translation.  Rows whose normals change (max |A1 - A0| > 1e-9 max |A0|: beyond the roundoff that edge_row leaves on
+// translated vertices) or whose db no translation explains (least-squares residual |A dc - db|_2 > 1e-9 (1 + max |b|),
+// b over both stages) describe a set that turns or changes shape between the knots; linear interpolation of its rows is
+// then no rigid motion, no displacement bound is known, and the obstacle's move -- with it the bound of every
+// sub-interval of the interval and the instance's lower_bound -- is NaN.  The sampled values are reported either way.
+constexpr double SWEEP_ROW_TOL = 1e-9;     // relative change of A, and residual of the translation fit
+constexpr double SWEEP_RANK_TOL = 1e-12;   // det G <= tol (trace G)^2: the rows are parallel
+
+// min with NaN below every number (the order of better()): a NaN operand wins
+AU_FN double min_nan(double a, double b) { return (a != a || b != b) ? NAN : (a < b ? a : b); }
+
+AU_FN double lerp_end(double v0, double v1, int n_sub, int j) {
+    return j == 0 ? v0 : (j == n_sub ? v1 : v0 + ((double)j / (double)n_sub) * (v1 - v0));
+}
+
+// |dc| of one obstacle (m rows at A0 / b0 and A1 / b1) over the whole interval, NaN when no translation is certified
+AU_FN double plan_obstacle_move(const double* A0, const double* b0, const double* A1, const double* b1, int m) {
+    if (A0 == A1 && b0 == b1) return 0.0;                            // obca_mpc4: the rows stand still
+    double g00 = 0.0, g01 = 0.0, g11 = 0.0, r0 = 0.0, r1 = 0.0, amax = 0.0, dmaxA = 0.0, bmax = 0.0;
+    for (int j = 0; j < m; ++j) {
+        const double a0 = A0[2 * j], a1 = A0[2 * j + 1], db = b1[j] - b0[j];
+        g00 += a0 * a0; g01 += a0 * a1; g11 += a1 * a1;
+        r0 += a0 * db; r1 += a1 * db;
+        amax = dmax(amax, dmax(fabs(a0), fabs(a1)));
+        dmaxA = dmax(dmaxA, dmax(fabs(A1[2 * j] - a0), fabs(A1[2 * j + 1] - a1)));
+        bmax = dmax(bmax, dmax(fabs(b0[j]), fabs(b1[j])));
+    }
+    const double tr = g00 + g11, det = g00 * g11 - g01 * g01;
+    double cx, cy;
+    if (det <= SWEEP_RANK_TOL * tr * tr) { cx = r0 / tr; cy = r1 / tr; }
+    else { cx = (g11 * r0 - g01 * r1) / det; cy = (g00 * r1 - g01 * r0) / det; }
+    double res = 0.0;
+    for (int j = 0; j < m; ++j) {
+        const double e = A0[2 * j] * cx + A0[2 * j + 1] * cy - (b1[j] - b0[j]);
+        res += e * e;
+    }
+    const double move = sqrt(cx * cx + cy * cy);
+    // written so that a NaN anywhere (a non-finite row, tr = 0) fails the test
+    const bool ok = dmaxA <= SWEEP_ROW_TOL * amax && sqrt(res) <= SWEEP_ROW_TOL * (1.0 + bmax) && isfinite(move);
+    return ok ? move : NAN;
+}
+
+// the obstacles of one plan: n_obs obstacles of m[i] rows starting at row off[i] of a stage
+struct PlanScene {
+    const double* ego;
+    int n_obs;
+    const int32_t *m, *off;
+};
+
+// largest plan_obstacle_move over the obstacles (NaN if any is)
+AU_FN double plan_move(const PlanScene& S, const double* A0, const double* b0, const double* A1, const double* b1) {
+    double mv = 0.0;
+    for (int i = 0; i < S.n_obs; ++i) {
+        const double mi = plan_obstacle_move(A0 + 2 * S.off[i], b0 + S.off[i], A1 + 2 * S.off[i], b1 + S.off[i], S.m[i]);
+        mv = (mv != mv || mi != mi) ? NAN : dmax(mv, mi);
+    }
+    return mv;
+}
+
+// distance to one obstacle of K rows (A0 / b0, A1 / b1: its rows at the two stages) at sample j.  K is a compile-time
+// constant so that every loop over the rows unrolls and the interpolated rows live in registers: with a run-time row
+// count the device compiler keeps them in an indexed array (LDS or scratch).
+template <int MAXM, int K>
+AU_FN double plan_rows_distance(const double C[4][2], const double* A0, const double* b0, const double* A1, const double* b1,
+                                int n_sub, int j) {
+    double A[2 * K], b[K];
+    for (int r = 0; r < K; ++r) {
+        A[2 * r] = lerp_end(A0[2 * r], A1[2 * r], n_sub, j);
+        A[2 * r + 1] = lerp_end(A0[2 * r + 1], A1[2 * r + 1], n_sub, j);
+        b[r] = lerp_end(b0[r], b1[r], n_sub, j);
+    }
+    return plan_distance<MAXM>(C, A, b, K);
+}
+
+// the same for a run-time row count 1 <= m <= MAXM
+template <int MAXM, int K = 1>
+AU_FN double plan_rows_distance_m(const double C[4][2], const double* A0, const double* b0, const double* A1,
+                                  const double* b1, int m, int n_sub, int j) {
+    if constexpr (K < MAXM) {
+        if (m != K) return plan_rows_distance_m<MAXM, K + 1>(C, A0, b0, A1, b1, m, n_sub, j);
+    }
+    return plan_rows_distance<MAXM, K>(C, A0, b0, A1, b1, n_sub, j);
+}
+
+// smallest distance over the obstacles at sample j, one obstacle's interpolated rows at a time; arg = its obstacle
+// (lowest among equals, a NaN first).  Evaluated from the interval's ends alone, like sample_distance.
+template <int MAXM>
+AU_FN double plan_sample_distance(const PlanScene& S, const double* p0, const double* p1, const double* A0, const double* b0,
+                                  const double* A1, const double* b1, int n_sub, int j, int* arg) {
+    double p[3], C[4][2];
+    sample_pose(p0, p1, n_sub, j, p);
+    car_corners(p[0], p[1], p[2], S.ego, C);
+    double best = INFINITY;
+    int ai = 0x7fffffff;
+    for (int i = 0; i < S.n_obs; ++i) {
+        const int o = S.off[i];
+        const double d = plan_rows_distance_m<MAXM>(C, A0 + 2 * o, b0 + o, A1 + 2 * o, b1 + o, S.m[i], n_sub, j);
+        if (better(d, 0, i, best, 0, ai)) { best = d; ai = i; }
+    }
+    *arg = ai;
+    return best;
+}
+
+// certified bound of sub-interval j-1 -> j (j >= 1): sub_bound's formula with the obstacles' move of the whole interval
+// (plan_move); NaN when an end value or the move is
+AU_FN double plan_sub_bound(const double* p0, const double* p1, int n_sub, int j, double rmax, double move, double d_prev,
+                            double d) {
+    double p[3], pp[3];
+    sample_pose(p0, p1, n_sub, j, p);
+    sample_pose(p0, p1, n_sub, j - 1, pp);
+    const double ux = p[0] - pp[0], uy = p[1] - pp[1];
+    const double delta = sqrt(ux * ux + uy * uy) + rmax * fabs(p[2] - pp[2]) + move / (double)n_sub;
+    return min_nan((d_prev + d - delta) / 2, min_nan(d_prev, d));
+}
+
+struct PlanIntervalResult {
+    double min_val;                    // smallest sample (NaN if any sample is)
+    int min_obst;                      // its obstacle: the lowest among equal samples
+    double lower;                      // certified lower bound over the continuous interpolated motion, or NaN
+};
+
+// one plan interval, n_sub >= 1: n_sub + 1 samples in order
+template <int MAXM>
+AU_FN PlanIntervalResult plan_interval(const PlanScene& S, const double* p0, const double* p1, const double* A0,
+                                       const double* b0, const double* A1, const double* b1, int n_sub) {
+    const double rmax = car_radius(S.ego);
+    const double move = plan_move(S, A0, b0, A1, b1);
+    PlanIntervalResult R;
+    R.min_val = INFINITY; R.min_obst = 0x7fffffff; R.lower = INFINITY;
+    double prev_d = 0.0;
+    for (int j = 0; j <= n_sub; ++j) {
+        int arg;
+        const double d = plan_sample_distance<MAXM>(S, p0, p1, A0, b0, A1, b1, n_sub, j, &arg);
+        if (better(d, 0, arg, R.min_val, 0, R.min_obst)) { R.min_val = d; R.min_obst = arg; }
+        if (j > 0) R.lower = min_nan(R.lower, plan_sub_bound(p0, p1, n_sub, j, rmax, move, prev_d, d));
+        prev_d = d;
+    }
+    return R;
+}
+
+// per-instance reduction of the sweep over its intervals: (value, interval, obstacle) under better(), the bound under
+// min_nan, the first colliding interval.  Both are total orders / commutative, so any reduction order gives the same words.
+struct PlanSweepAcc {
+    double best, lower;
+    int bs, bo, coll;
+};
+
+AU_FN void plan_acc_init(PlanSweepAcc& a) { a.best = INFINITY; a.lower = INFINITY; a.bs = a.bo = 0x7fffffff; a.coll = -1; }
+
+AU_FN void plan_acc_add(PlanSweepAcc& a, int s, const PlanIntervalResult& R) {
+    if (better(R.min_val, s, R.min_obst, a.best, a.bs, a.bo)) { a.best = R.min_val; a.bs = s; a.bo = R.min_obst; }
+    a.lower = min_nan(a.lower, R.lower);
+    if (R.min_val < 0.0 && (a.coll < 0 || s < a.coll)) a.coll = s;
+}
+
 }  // namespace audit
 
 // ---------------------------------------------------------------------------------------------------------------------
