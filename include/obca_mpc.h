@@ -397,7 +397,9 @@ int obca_rollouts_read(obca_rollouts* r, double* x_closed, double* u_closed, dou
  *   yaw9  HOST pointer, 9 doubles: arctan2(dy, dx) for dy, dx in {-1,0,1} at index (dy+1)*3+(dx+1), as the
  *         caller's libm evaluates them (the reference uses numpy's)
  *   path  [B,3,path_max] x / y / yaw rows, padded with the last point; path_len [B]: points, or
- *         -1 no route, -2 open list overflow, -3 path_max too small
+ *         -1 no route (an occupied goal included; an occupied start is left like any other cell), -2 open list
+ *         overflow, -3 path_max too small, -4 start or goal outside [0,rows) x [0,cols): that instance returns before
+ *         it touches its workspace.  The path of an instance with a negative code is not written.
  *   workspace: device buffer of obca_astar_workspace_bytes(B, rows, cols) bytes.
  * path / path_len are what obca_rollouts_reset takes. */
 int64_t obca_astar_workspace_bytes(int32_t B, int32_t rows, int32_t cols);
@@ -408,7 +410,10 @@ int obca_astar_batch(const uint8_t* grid, int32_t B, int32_t rows, int32_t cols,
 /* Occupancy grids of B worlds on the device -- the reference's mapModel.shape2grid (src/model_map.py:21-56; vertex
  * re-ordering :88-101 and the division by the resolution :58-71 included): boxes [B,K,4] = (xmin, ymin, xmax, ymax) of each
  * obstacle polygon in world units (an entry with xmin > xmax or NaN is padding), grid [B,rows,cols] uint8 (1 = occupied),
- * rows = int((map_y - 1)/resolution) + 1, cols likewise (src/model_map.py:17).  The grid is what obca_astar_batch takes. */
+ * rows = int((map_y - 1)/resolution) + 1, cols likewise (src/model_map.py:17).  Cells x .. x + int(xmax/res - xmin/res),
+ * y .. y + int(ymax/res - ymin/res) are set, x = int(xmin/res), y = int(ymin/res) (truncation towards zero), CLIPPED to the
+ * map: the part of a box outside the grid is dropped, a box wholly outside marks nothing (the reference raises there).  Box
+ * coordinates divided by the resolution have to fit an int32.  The grid is what obca_astar_batch takes. */
 int obca_rasterise_batch(const double* boxes, int32_t B, int32_t K, double resolution, int32_t rows, int32_t cols,
                          uint8_t* grid, void* hip_stream);
 

@@ -17,6 +17,11 @@ Two families of vectors are captured:
    dynamic-obstacle advance, fixed-time preparation, A* routes, and a driver
    trace with a scripted stand-in solver.
 
+3. ``astar_edges.json`` -- the reference's ``a_star`` routes on small tie-heavy grids (empty squares, 1xN and Nx1
+   strips, a 13x13 serpentine, seeded random grids up to 13x13 and two of 41x61): the raw goal->start chain and,
+   for two or more cells, the trajectory of ``create_reference_path``.  Pins tie order and the re-queue rules
+   beyond the four demo grids of F9.  ``make_golden.py astar_edges`` writes this fixture alone.
+
 No reference source text is stored; only numbers.
 """
 import contextlib
@@ -386,14 +391,79 @@ def problemSettingTable(demo):
         return [list(r) for r in problemSetting(demo).dyn_obs_info]
 
 
+# ---------------------------------------------------------------------------
+# 3. A* routes on tie-heavy grids
+# ---------------------------------------------------------------------------
+
+def astar_edge_cases():
+    from a_star import a_star
+    cases = []
+
+    def add(name, grid, start, goal):
+        grid = np.asarray(grid, float)
+        start, goal = tuple(int(v) for v in start), tuple(int(v) for v in goal)
+        pl = a_star(grid, start, goal)
+        route = pl.solve(grid, start, goal)
+        ref = None
+        if route is not False and len(route) >= 2:          # create_reference_path needs two points
+            ref = np.asarray(pl.create_reference_path(pl.rebuild_path(route)), float).T
+        cases.append({"name": name, "grid": tolist(grid.astype(int)), "start": list(start), "goal": list(goal),
+                      "route": None if route is False else [[int(r), int(c)] for r, c in route], "ref": tolist(ref)})
+
+    for n in (2, 3, 5, 8, 13):                               # empty squares: every cell of a diagonal band ties
+        e = np.zeros((n, n))
+        add("empty%d_diag" % n, e, (0, 0), (n - 1, n - 1))
+        add("empty%d_anti" % n, e, (n - 1, 0), (0, n - 1))
+        if n >= 5:
+            add("empty%d_knight" % n, e, (0, 0), (n - 1, n // 2))
+            add("empty%d_back" % n, e, (n // 2, n - 1), (n - 1, 0))
+    for n in (2, 7, 13):
+        add("strip1x%d_fwd" % n, np.zeros((1, n)), (0, 0), (0, n - 1))
+        add("strip1x%d_rev" % n, np.zeros((1, n)), (0, n - 1), (0, 0))
+    add("strip13x1_fwd", np.zeros((13, 1)), (0, 0), (12, 0))
+    add("strip13x1_rev", np.zeros((13, 1)), (12, 0), (0, 0))
+    add("single_cell", np.zeros((1, 1)), (0, 0), (0, 0))
+    s = np.zeros((13, 13))                                   # serpentine: odd rows are walls, one gap at alternating ends
+    for k, r in enumerate(range(1, 13, 2)):
+        s[r, :] = 1
+        s[r, 12 if k % 2 == 0 else 0] = 0
+    add("serpentine13_fwd", s, (0, 0), (12, 12))
+    add("serpentine13_rev", s, (12, 12), (0, 0))
+    rng = np.random.default_rng(20261017)
+    for i in range(16):
+        rows, cols = (int(v) for v in rng.integers(2, 14, 2))
+        g = (rng.uniform(size=(rows, cols)) < (0.1, 0.3, 0.45)[i % 3]).astype(float)
+        free = np.argwhere(g == 0)
+        if len(free) < 2:
+            g[:] = 0
+            free = np.argwhere(g == 0)
+        add("random%d_%dx%d" % (i, rows, cols), g, free[rng.integers(len(free))], free[rng.integers(len(free))])
+    for i in range(2):
+        g = (rng.uniform(size=(41, 61)) < 0.25).astype(float)
+        g[1, 1] = g[39, 59] = 0
+        add("random41x61_%d" % i, g, (1, 1) if i == 0 else (39, 59), (39, 59) if i == 0 else (1, 1))
+    return cases
+
+
+def write_astar_edges():
+    cases = astar_edge_cases()
+    with open(os.path.join(HERE, "astar_edges.json"), "w") as f:
+        json.dump(cases, f, separators=(",", ":"))
+    print("astar edge cases:", len(cases), "routes:", sum(c["route"] is not None for c in cases))
+
+
 def main():
     nc = _install_stubs()
+    if sys.argv[1:] == ["astar_edges"]:
+        write_astar_edges()
+        return
     nlp = nlp_cases(nc)
     with open(os.path.join(HERE, "nlp_eval.json"), "w") as f:
         json.dump(nlp, f)
     har = harness_cases()
     with open(os.path.join(HERE, "harness.json"), "w") as f:
         json.dump(har, f)
+    write_astar_edges()
     print("nlp cases:", [(c["name"], len(c["points"][0]["cons"])) for c in nlp])
     print("harness keys:", {k: len(v) for k, v in har.items()})
 

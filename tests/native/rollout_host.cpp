@@ -131,3 +131,16 @@ extern "C" int astar_host_batch(const unsigned char* grid, int B, int rows, int 
                                   goal[2 * b + 1], work.data(), yaw9, path + (size_t)b * 3 * path_max, path_max);
     return 0;
 }
+
+// the same with the caller's workspace laid out as on the device (instance b at work + b * astar_host_work_bytes), so a
+// test can surround and pre-fill it
+extern "C" long long astar_host_work_bytes(int rows, int cols) { return (long long)astar::work_bytes(rows * cols); }
+
+extern "C" int astar_host_batch_ws(const unsigned char* grid, int B, int rows, int cols, const int* start, const int* goal,
+                                   const double* yaw9, int path_max, double* path, int* path_len, unsigned char* work) {
+    const size_t stride = astar::work_bytes(rows * cols);
+    for (int b = 0; b < B; ++b)
+        path_len[b] = astar::plan(grid + (size_t)b * rows * cols, rows, cols, start[2 * b], start[2 * b + 1], goal[2 * b],
+                                  goal[2 * b + 1], work + (size_t)b * stride, yaw9, path + (size_t)b * 3 * path_max, path_max);
+    return 0;
+}

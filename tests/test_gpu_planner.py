@@ -8,15 +8,6 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 
-def _mirror(grid, start, goal):
-    from vehicle_motion_planning_with_obstacles_avoidance_using_mpc_amd.a_star import a_star
-    pl = a_star(grid, start, goal)
-    route = pl.solve(grid, start, goal)
-    if route is False or len(route) < 2:
-        return None
-    return np.asarray(pl.create_reference_path(pl.rebuild_path(route)), float).T
-
-
 def test_golden_demo_routes_on_device(harness_golden):
     from vehicle_motion_planning_with_obstacles_avoidance_using_mpc_amd.demo_setting import problemSetting
     from vehicle_motion_planning_with_obstacles_avoidance_using_mpc_amd.planner import plan_batch
@@ -31,6 +22,7 @@ def test_golden_demo_routes_on_device(harness_golden):
 
 
 def test_random_grids_on_device_match_the_mirror():
+    from tests.test_astar_core import mirror_path
     from vehicle_motion_planning_with_obstacles_avoidance_using_mpc_amd.planner import plan_batch
     rng = np.random.default_rng(7)
     shape, B = (41, 61), 96
@@ -40,17 +32,30 @@ def test_random_grids_on_device_match_the_mirror():
         free = np.argwhere(g == 0)
         starts.append(tuple(int(v) for v in free[rng.integers(len(free))]))
         goals.append(tuple(int(v) for v in free[rng.integers(len(free))]))
+    # three more lanes with the short answers forced: start == goal (0), a goal next to the start (1, yaw 0.0), a walled-in
+    # goal (-1) -- each code and the one-point path's content are asserted exactly, none stands in for another
+    near = next((r, c) for r, c in np.argwhere(grids[1] == 0) if c + 1 < shape[1] and grids[1][r, c + 1] == 0)
+    walled = grids[2].copy()
+    walled[9:12, 9:12] = 1
+    walled[10, 10] = walled[0, 0] = 0
+    grids = np.concatenate([grids, grids[0:2], walled[None]])
+    starts += [starts[0], (int(near[0]), int(near[1])), (0, 0)]
+    goals += [starts[0], (int(near[0]), int(near[1]) + 1), (10, 10)]
     path, plen = plan_batch(grids, starts, goals)
     path, plen = path.cpu().numpy(), plen.cpu().numpy()
+    assert plen[B:].tolist() == [0, 1, -1]
+    assert path[B + 1, :, 0].tolist() == [goals[B + 1][1], goals[B + 1][0], 0.0]
     routes = 0
-    for i in range(B):
-        e = _mirror(grids[i].astype(float), starts[i], goals[i])
+    for i in range(B + 3):
+        e = mirror_path(grids[i].astype(float), starts[i], goals[i])
         if e is None:
-            assert plen[i] in (-1, 0, 1)
+            assert plen[i] == -1, (i, plen[i])
             continue
-        routes += 1
-        assert plen[i] == e.shape[1]
+        assert plen[i] == e.shape[1], (i, plen[i], e.shape)
         assert np.array_equal(path[i, :, :plen[i]], e)
+        if plen[i]:
+            assert np.array_equal(path[i, :, plen[i]:], np.repeat(e[:, -1:], path.shape[2] - plen[i], axis=1))   # padding
+        routes += int(e.shape[1] >= 2)
     assert routes > B // 3
 
 

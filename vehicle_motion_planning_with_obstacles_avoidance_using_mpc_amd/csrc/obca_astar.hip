@@ -30,7 +30,8 @@ __global__ void __launch_bounds__(64) astar_kernel(AstarLaunch A) {
 // Occupancy grid of B worlds (reference mapModel.shape2grid, src/model_map.py:21-56, with reOrderVertex :88-101 and
 // world2gridmap :58-71 applied by the caller / here): obstacle k of world b is the axis-aligned bounding box
 // (xmin, ymin, xmax, ymax) of its polygon; cells x .. x + int(xmax/res - xmin/res), y .. y + int(ymax/res - ymin/res) are
-// set, x = int(xmin/res), y = int(ymin/res) -- the reference's truncations.  One thread per cell: byte work, coalesced.
+// set, x = int(xmin/res), y = int(ymin/res) -- the reference's truncations -- clipped to the map (a cell outside has no
+// thread).  One thread per cell: byte work, coalesced.
 __global__ void __launch_bounds__(256) rasterise_kernel(const double* __restrict__ boxes, int B, int K, double res, int rows,
                                                         int cols, uint8_t* __restrict__ grid) {
     const size_t cells = (size_t)rows * cols;

@@ -31,7 +31,7 @@
 
 namespace astar {
 
-enum { NO_ROUTE = -1, HEAP_OVERFLOW = -2, PATH_TOO_LONG = -3 };
+enum { NO_ROUTE = -1, HEAP_OVERFLOW = -2, PATH_TOO_LONG = -3, BAD_ENDPOINT = -4 };
 
 AS_FN int heap_capacity(int cells) { return 4 * cells + 64; }
 AS_FN size_t align8(size_t v) { return (v + 7) & ~(size_t)7; }
@@ -104,9 +104,13 @@ AS_FN double cell_distance(int r0, int c0, int r1, int c1) {
 // grid [rows*cols] (1 = occupied); start/goal as (row, col).  Writes the reference trajectory x/y/yaw into
 // path[0..2][*] (row stride path_max) and returns its length, or a negative code.  yaw9[(dy+1)*3 + (dx+1)] =
 // arctan2(dy, dx) as the host evaluates it (lattice steps only take these nine values).
+// A start or goal outside [0, rows) x [0, cols) returns BAD_ENDPOINT with workspace and path untouched (the cells index
+// the private workspace).  An occupied start is left like any other cell, as in the reference; an occupied goal is never
+// entered: NO_ROUTE.
 AS_FN int plan(const uint8_t* grid, int rows, int cols, int sr, int sc, int gr, int gc, unsigned char* work,
                const double* yaw9, double* path, int path_max) {
     AS_EXACT
+    if (sr < 0 || sr >= rows || sc < 0 || sc >= cols || gr < 0 || gr >= rows || gc < 0 || gc >= cols) return BAD_ENDPOINT;
     const int cells = rows * cols;
     Work W;
     bind(W, work, cells);

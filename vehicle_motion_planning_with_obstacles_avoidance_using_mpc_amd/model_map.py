@@ -12,7 +12,8 @@ class mapModel:
         self.resolution = resolution
 
     def shape2grid(self, org_gridMap, obstacle_location):
-        """Mark the axis-aligned bounding box of every obstacle polygon (cells are 1 m squares)."""
+        """Mark the axis-aligned bounding box of every obstacle polygon, clipped to the map: the part of a box outside
+        the grid is dropped (the reference indexes cell by cell and raises there; ``obca_rasterise_batch`` clips too)."""
         grid = self.grid_map if (isinstance(org_gridMap, list) and len(org_gridMap) == 0) else org_gridMap
         for poly in obstacle_location:
             xs = [p[0] / self.resolution for p in poly]
@@ -20,5 +21,5 @@ class mapModel:
             x0, y0 = int(min(xs)), int(min(ys))
             nx = int(max(xs) - min(xs)) + 1
             ny = int(max(ys) - min(ys)) + 1
-            grid[y0:y0 + ny, x0:x0 + nx] = 1
+            grid[max(y0, 0):max(y0 + ny, 0), max(x0, 0):max(x0 + nx, 0)] = 1   # a negative slice bound would wrap
         return grid

@@ -22,7 +22,8 @@ def yaw_table():
 def plan_batch(grids, starts, goals, path_max=None, device=None):
     """grids [B,rows,cols] (1 = occupied; ``setting.org_gridMap``), starts / goals [B,2] as (row, col) =
     (pose_y, pose_x).  Returns device tensors path [B,3,path_max] (x, y, yaw; padded with the last point) and
-    path_len [B] (negative: -1 no route, -2 open list overflow, -3 path_max too small)."""
+    path_len [B] (negative: -1 no route, -2 open list overflow, -3 path_max too small, -4 start or goal outside the
+    grid; the path of an instance with a negative code is left unwritten)."""
     import torch
     if not torch.cuda.is_available():
         raise RuntimeError("plan_batch needs a ROCm GPU; there is no CPU fallback on the product path")
