@@ -461,6 +461,34 @@ int obca_plan_sweep(const double ego[4], int32_t n_obs, const int32_t* m, int32_
                     int32_t* first_collision, double* interval_min /* [B,N] or NULL */,
                     int32_t device, void* hip_stream);
 
+/* Clearance repair of obca_solve_batch outputs (obca_mpc 0.11): one round of "measure, grow the rows where the plan comes
+ * too close, say which instances to solve again".  Arguments, shapes, the host / device split and the checks as
+ * obca_plan_sweep; status [B] is obca_solve_batch's.  For every instance with variant != 0 and status 0 or 1, every interval
+ * s and obstacle i, d[s,i] is the smallest of obca_plan_sweep's n_sub + 1 samples against that obstacle alone (certified = 1:
+ * the obstacle's own certified bound over the interval, NaN where its rows turn), always against A / b as given.  Then
+ *   need[s,i]  = gain (target - d[s,i]) where d[s,i] < target, else 0
+ *   grow[k,i]  = min(grow_max, grow[k,i] + max(need[k-1,i], need[k,i])) over the intervals that exist; where variant == 4
+ *                the largest need[.,i] at every stage (obca_mpc4 reads stage 0's rows only).  In/out, [B,N+1,n_obs],
+ *                metres; never decreases.  Zero it before the first round.
+ *   b_out[k,r] = b[k,r] + grow[k,i] hypot(A[k,r,0], A[k,r,1]) for every row r of obstacle i: the offset polygon contains the
+ *                obstacle grown by a disc of radius grow[k,i], so a knot that keeps dmin from the rows (A, b_out) keeps
+ *                dmin + grow[k,i] from the obstacle itself.  Solve again with b_out in place of b; A is not changed.
+ *   variant_out[b] = variant[b] if some grow[b,.,.] rose in this call, else 0: passed to obca_solve_batch as its variant it
+ *                re-solves exactly the instances whose rows changed and leaves the outputs of the others untouched.
+ *   min_clear  [B] or NULL: the smallest d[s,i] of the instance.
+ * Passed through -- grow untouched, b_out = b + grow |a| as it stood, variant_out = 0 --: variant 0 and a status outside
+ * {0, 1} (not measured, min_clear NaN), and an instance one of whose measurements is not finite (min_clear NaN, the NaN rule
+ * of obca_plan_clearance).  b_out must not alias b (it holds intermediate values during the call).  n_sub as
+ * obca_plan_sweep, certified 0 or 1, target finite, 0 < gain <= 8, 0 <= grow_max <= 2; variant, status, grow, b_out and
+ * variant_out must not be NULL. */
+int obca_plan_tighten(const double ego[4], int32_t n_obs, const int32_t* m, int32_t N, int32_t B,
+                      const int32_t* variant, const int32_t* status,
+                      const double* x, const double* A, const double* b,
+                      int32_t n_sub, int32_t certified, double target, double gain, double grow_max,
+                      double* grow /* [B,N+1,n_obs], in/out */, double* b_out /* [B,N+1,M] */,
+                      int32_t* variant_out /* [B] */, double* min_clear /* [B] or NULL */,
+                      int32_t device, void* hip_stream);
+
 /* Rollout audit from the handle's own device state (after obca_rollouts_reset; ego and dmin of that reset).  Rollout
  * b has the knots x_closed[b, 0..steps[b]]; interval s joins knot s to s + 1 (steps[b] == 0: knot 0 alone).  Within
  * an interval the pose is interpolated linearly in (x, y, theta) and n_sub + 1 >= 2 samples, both knots included, are
@@ -498,7 +526,9 @@ int obca_moving_rows_batch(int32_t B, int32_t N, int32_t Ms, int32_t n_box, cons
                            int32_t device, void* hip_stream);
 
 const char* obca_strerror(int code);
-/* "obca_mpc 0.9 (gfx950)": 0.9 = swept audit of batched plans (obca_plan_sweep);
+/* "obca_mpc 0.11 (gfx950)": 0.11 = clearance repair of batched plans (obca_plan_tighten);
+ * 0.10 = obca_astar_batch's code -4 (start or goal outside the grid), obca_rasterise_batch clips boxes to the map;
+ * 0.9 = swept audit of batched plans (obca_plan_sweep);
  * 0.8 = opt-in swept, inflated rows of moving boxes (obca_rollouts_set_swept_rows, obca_moving_rows_batch);
  * 0.7 = opt-in collision stop (OBCA_DONE_COLLISION, obca_rollouts_set_collision_stop,
  * obca_rollouts_read_clearance) and exact sensing (obca_rollouts_set_exact_sensing); 0.6 = the answer of an exhausted start ladder is the most informative pass's (obca_params: the starts of a

@@ -57,7 +57,7 @@ EXPORTS = ("obca_create", "obca_destroy", "obca_solve_batch", "obca_lds_bytes", 
            "obca_rollouts_reset", "obca_rollouts_step", "obca_rollouts_read", "obca_rollouts_run",
            "obca_rollouts_set_mode", "obca_rollouts_queue_mode", "obca_set_shape_specialisation", "obca_shape_is_specialised", "obca_astar_batch", "obca_astar_workspace_bytes", "obca_primal_size", "obca_set_warm_start",
            "obca_rollouts_set_warm_start", "obca_dual_size", "obca_set_certificate_buffers", "obca_rasterise_batch",
-           "obca_plan_clearance", "obca_plan_sweep", "obca_rollouts_audit", "obca_rollouts_set_collision_stop", "obca_rollouts_set_exact_sensing",
+           "obca_plan_clearance", "obca_plan_sweep", "obca_plan_tighten", "obca_rollouts_audit", "obca_rollouts_set_collision_stop", "obca_rollouts_set_exact_sensing",
            "obca_rollouts_read_clearance", "obca_rollouts_set_swept_rows", "obca_moving_rows_batch")
 
 OBCA_MAX_DYN = 4
@@ -166,6 +166,10 @@ def load():
     lib.obca_plan_sweep.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32,
                                     ctypes.c_int32, i32p, vp, vp, vp, ctypes.c_int32, vp, vp, i32p, i32p, i32p, vp, ctypes.c_int32, vp]
     lib.obca_plan_sweep.restype = ctypes.c_int
+    lib.obca_plan_tighten.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32,
+                                      ctypes.c_int32, i32p, i32p, vp, vp, vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_double,
+                                      ctypes.c_double, ctypes.c_double, vp, vp, i32p, vp, ctypes.c_int32, vp]
+    lib.obca_plan_tighten.restype = ctypes.c_int
     lib.obca_rollouts_audit.argtypes = [ctypes.c_void_p, ctypes.c_int32, vp, vp, i32p, i32p, i32p, i32p, vp, vp]
     lib.obca_rollouts_audit.restype = ctypes.c_int
     lib.obca_rollouts_set_collision_stop.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_double, ctypes.c_int32]

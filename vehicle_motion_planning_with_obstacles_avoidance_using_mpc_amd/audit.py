@@ -2,7 +2,8 @@
 
 ``plan_clearance`` measures ``BatchSolver`` outputs against the rows the solver was given (obca_plan_clearance), at the
 knots; ``plan_sweep`` measures them between the knots as well and bounds the continuous motion from below
-(obca_plan_sweep), ``plan_summary`` turns a sweep into counts;
+(obca_plan_sweep), ``plan_summary`` turns a sweep into counts; ``plan_tighten`` is one round of the clearance repair
+(obca_plan_tighten: measure, grow the rows where the plan comes too close; the loop around it is ``clear.solve_clear``);
 ``DeviceRollouts.audit`` / ``RolloutCohorts.audit`` measure closed-loop rollouts against the static obstacles and every
 present moving box, between the knots too (obca_rollouts_audit); ``summary`` turns an audit into counts.  Read-only: no
 solver or rollout state changes.  Geometry and the certified bound: csrc/obca_audit_core.h.
@@ -83,6 +84,49 @@ def plan_sweep(x, A, b, m, n_sub=16, ego=DEFAULT_EGO, variant=None, per_interval
                                    p(out["lower_bound"]), p(out["arg_interval"]), p(out["arg_obst"]), p(out["first_collision"]),
                                    p(out.get("interval_min")), dev.index if dev.index is not None else torch.cuda.current_device(),
                                    stream))
+    return out
+
+
+def plan_tighten(x, A, b, m, variant, status, grow=None, b_out=None, n_sub=16, certified=False, target=0.0, gain=1.0,
+                 grow_max=2.0, ego=DEFAULT_EGO, device=None):
+    """One round of the clearance repair (obca_plan_tighten): plan_sweep's arguments plus status [B] of the solve and the
+    in/out state grow [B,N+1,n_obs] (None: zeros).  Every feasible plan (variant != 0, status 0 / 1) is measured per
+    interval and obstacle against A / b; where it comes closer than target, that obstacle grows at the two stages next to
+    the interval by gain times the shortfall, up to grow_max.  Returns a dict of device tensors on the current stream: grow
+    (the tensor passed in, updated in place), b_out [B,N+1,M] = b + grow |a| (the rows to solve again with; written into
+    b_out if given, which must not be b), variant_out [B] (variant where grow rose, else 0: the variant argument of the
+    next solve) and min_clear [B] (NaN: not measured, or not finite)."""
+    import torch
+    dev = torch.device(device) if device is not None else (x.device if isinstance(x, torch.Tensor) and x.is_cuda else
+                                                           torch.device("cuda", torch.cuda.current_device()))
+    lib = _lib.load()
+    m = [int(v) for v in m]
+    x = _device_tensor(x, torch.float64, dev)
+    B, N1 = int(x.shape[0]), int(x.shape[2])
+    M = sum(m)
+    x = x.reshape(B, 3, N1)
+    A = _device_tensor(A, torch.float64, dev).reshape(B, N1, M, 2)
+    b = _device_tensor(b, torch.float64, dev).reshape(B, N1, M)
+    var = _device_tensor(variant, torch.int32, dev).reshape(B)
+    st = _device_tensor(status, torch.int32, dev).reshape(B)
+    if grow is None:
+        grow = torch.zeros(B, N1, len(m), dtype=torch.float64, device=dev)
+    if b_out is None:
+        b_out = torch.empty(B, N1, M, dtype=torch.float64, device=dev)
+    for t, shape in ((grow, (B, N1, len(m))), (b_out, (B, N1, M))):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and
+                tuple(t.shape) == shape):
+            raise ValueError("grow / b_out: expected a contiguous float64 device tensor of shape %s" % (shape,))
+    out = {"grow": grow, "b_out": b_out, "variant_out": torch.empty(B, dtype=torch.int32, device=dev),
+           "min_clear": torch.empty(B, dtype=torch.float64, device=dev)}
+    p = lambda t: ctypes.c_void_p(t.data_ptr())
+    ego_c = (ctypes.c_double * 4)(*[float(v) for v in ego])
+    m_c = (ctypes.c_int32 * max(len(m), 1))(*m)
+    stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    _lib.check(lib.obca_plan_tighten(ego_c, len(m), m_c, N1 - 1, B, p(var), p(st), p(x), p(A), p(b), int(n_sub), int(bool(certified)),
+                                     float(target), float(gain), float(grow_max), p(grow), p(b_out), p(out["variant_out"]),
+                                     p(out["min_clear"]), dev.index if dev.index is not None else torch.cuda.current_device(),
+                                     stream))
     return out
 
 

@@ -1,6 +1,7 @@
 // obca_audit.hip -- collision audit (obca_plan_clearance, obca_plan_sweep, obca_rollouts_audit of include/obca_mpc.h): true
-// clearance of batched plans (at the knots; swept between them) and of closed-loop rollouts in fp64, from the geometry core csrc/obca_audit_core.h.  Read-only: the
-// kernels only read solver outputs and rollout state and write the caller's output buffers.
+// clearance of batched plans (at the knots; swept between them) and of closed-loop rollouts in fp64, and the clearance repair's
+// round (obca_plan_tighten: measure, grow the rows), from the geometry core csrc/obca_audit_core.h.  Read-only towards the
+// solver and the rollouts: the kernels only read their outputs and state and write the caller's output buffers.
 //
 // Layout: the lanes of a wavefront are cut into segments of seg = next power of two >= the items of one instance (plan:
 // its N + 1 stages, plan sweep: its N intervals, rollout: its max_steps intervals; at most 64), one instance per segment;
@@ -42,6 +43,19 @@ struct SweepArgs {
     double *min_clear, *lower_bound;
     int32_t *arg_interval, *arg_obst, *first_collision;
     double* interval_min;
+};
+
+struct TightenArgs {
+    int32_t B, N, n_obs, M;
+    int32_t m[OBCA_MAX_OBST], off[OBCA_MAX_OBST];
+    double ego[4];
+    int32_t seg, log_seg, n_sub, certified;
+    double target, gain, grow_max;
+    const int32_t *variant, *status;
+    const double *x, *A, *b;
+    double *grow, *b_out;
+    int32_t* variant_out;
+    double* min_clear;
 };
 
 struct AuditArgs {
@@ -150,6 +164,86 @@ __global__ void __launch_bounds__(BLOCK) plan_sweep_kernel(SweepArgs P) {
         P.arg_interval[inst] = acc.bs;
         P.arg_obst[inst] = acc.bo;
         P.first_collision[inst] = acc.coll;
+    }
+}
+
+__device__ inline double seg_max(double v, int seg) {
+    for (int w = seg >> 1; w > 0; w >>= 1) v = fmax(v, __shfl_xor(v, w, WAVE));
+    return v;
+}
+
+// Clearance repair (audit::plan_tighten_* of csrc/obca_audit_core.h).  plan_sweep_kernel's layout: lane `sub` of a segment
+// owns the intervals s = sub, sub + seg, ... of its instance and with interval s the stage s (with interval N - 1 stage N as
+// well).  Two phases, because whether the instance is repaired at all (a NaN anywhere passes it through) and obca_mpc4's
+// need (the largest over all intervals) are known only after every interval is measured:
+//   1  d[s,i] of the lane's intervals, parked in b_out[inst, s, off[i]] -- the first row of obstacle i at stage s, which
+//      this lane alone reads back and overwrites in phase 2 (hence b_out must not alias b) -- and the segment's min_clear
+//   2  per obstacle: need[s,i] from the parked d; stage s wants need[s-1,i] as well, which is the left lane's of the same
+//      pass, or for lane 0 the last lane's of the pass before (kept in `carry`): one rotate-by-one shuffle inside the
+//      segment, in which the last lane sends its carry and every other lane its current need.
+// Every shuffle sits outside the per-instance conditions and the pass loops have the same trip count in every lane, so
+// all 64 lanes reach each one.
+__global__ void __launch_bounds__(BLOCK) plan_tighten_kernel(TightenArgs P) {
+    const int64_t gl = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t inst = gl >> P.log_seg;
+    const int sub = (int)(gl & (P.seg - 1));
+    const bool live = inst < P.B;                               // whole segments are live or not: the shuffles stay uniform
+    const int N1 = P.N + 1, N = P.N, seg = P.seg;
+    const int v = live ? P.variant[inst] : 0;
+    const bool active = live && audit::plan_tighten_active(v, P.status[inst]);
+    const size_t st0 = live ? (size_t)inst * N1 : 0;             // first stage of the instance
+    audit::PlanScene sc;
+    sc.ego = P.ego; sc.n_obs = P.n_obs; sc.m = P.m; sc.off = P.off;
+    double mc = active ? INFINITY : NAN;
+    if (active) {
+        const double rmax = audit::car_radius(P.ego);
+        const double* xb = P.x + (size_t)inst * 3 * N1;
+        for (int s = sub; s < N; s += seg) {
+            const double p0[3] = {xb[s], xb[N1 + s], xb[2 * N1 + s]};
+            const double p1[3] = {xb[s + 1], xb[N1 + s + 1], xb[2 * N1 + s + 1]};
+            const size_t k0 = st0 + ((v == 4) ? 0 : s);                     // obca_mpc4 reads stage 0's rows at every stage
+            const size_t k1 = (v == 4) ? k0 : k0 + 1;
+            for (int i = 0; i < P.n_obs; ++i) {
+                const double d = audit::plan_tighten_distance<OBCA_MAX_EDGES>(sc, i, p0, p1, P.A + k0 * P.M * 2, P.b + k0 * P.M,
+                                                                              P.A + k1 * P.M * 2, P.b + k1 * P.M, P.n_sub,
+                                                                              P.certified, rmax);
+                P.b_out[(st0 + s) * P.M + P.off[i]] = d;
+                mc = audit::min_nan(mc, d);
+            }
+        }
+    }
+    mc = seg_min_nan(mc, seg);
+    const bool ok = active && mc == mc;                          // repaired; otherwise passed through
+    int rose = 0;
+    for (int i = 0; i < P.n_obs; ++i) {
+        const int o = P.off[i];
+        double nmax = 0.0;
+        if (ok)
+            for (int s = sub; s < N; s += seg)
+                nmax = fmax(nmax, audit::plan_tighten_need(P.b_out[(st0 + s) * P.M + o], P.target, P.gain));
+        nmax = seg_max(nmax, seg);
+        double carry = 0.0;
+        for (int s0 = 0; s0 < N; s0 += seg) {
+            const int s = s0 + sub;
+            const bool has = live && s < N;
+            const double nd = (ok && has) ? audit::plan_tighten_need(P.b_out[(st0 + s) * P.M + o], P.target, P.gain) : 0.0;
+            const double left = __shfl(sub == seg - 1 ? carry : nd, (sub - 1) & (seg - 1), seg);
+            carry = nd;
+            if (has) {
+                const size_t k = st0 + s;
+                rose |= audit::plan_tighten_stage(P.A + (k * P.M + o) * 2, P.b + k * P.M + o, P.m[i], v == 4 ? nmax : fmax(left, nd),
+                                                  P.grow_max, ok, P.grow + k * P.n_obs + i, P.b_out + k * P.M + o);
+                if (s == N - 1)
+                    rose |= audit::plan_tighten_stage(P.A + ((k + 1) * P.M + o) * 2, P.b + (k + 1) * P.M + o, P.m[i],
+                                                      v == 4 ? nmax : nd, P.grow_max, ok, P.grow + (k + 1) * P.n_obs + i,
+                                                      P.b_out + (k + 1) * P.M + o);
+            }
+        }
+    }
+    for (int w = seg >> 1; w > 0; w >>= 1) rose |= __shfl_xor(rose, w, WAVE);
+    if (live && sub == 0) {
+        P.variant_out[inst] = rose ? v : 0;
+        if (P.min_clear) P.min_clear[inst] = mc;
     }
 }
 
@@ -306,6 +400,41 @@ extern "C" int obca_plan_sweep(const double ego[4], int32_t n_obs, const int32_t
     if (!guard.ok) return OBCA_E_HIP;
     const int64_t lanes = (int64_t)B * P.seg;
     hipLaunchKernelGGL(plan_sweep_kernel, dim3((unsigned)((lanes + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0,
+                       (hipStream_t)hip_stream, P);
+    return hipGetLastError() == hipSuccess ? OBCA_OK : OBCA_E_HIP;
+}
+
+extern "C" int obca_plan_tighten(const double ego[4], int32_t n_obs, const int32_t* m, int32_t N, int32_t B,
+                                 const int32_t* variant, const int32_t* status, const double* x, const double* A,
+                                 const double* b, int32_t n_sub, int32_t certified, double target, double gain,
+                                 double grow_max, double* grow, double* b_out, int32_t* variant_out, double* min_clear,
+                                 int32_t device, void* hip_stream) {
+    // every argument is checked before the first HIP call: a refused call has no side effect
+    if (!ego_ok(ego) || n_obs < 1 || n_obs > OBCA_MAX_OBST || !m || N < 1 || N > (1 << 20) || B < 1 || device < 0 ||
+        n_sub < 1 || n_sub > (1 << 16) || !variant || !status || !x || !A || !b || !grow || !b_out || !variant_out ||
+        b_out == b || (certified != 0 && certified != 1) || !isfinite(target) || !(gain > 0.0 && gain <= 8.0) ||
+        !(grow_max >= 0.0 && grow_max <= 2.0))
+        return OBCA_E_INVAL;
+    TightenArgs P;
+    P.M = 0;
+    for (int i = 0; i < OBCA_MAX_OBST; ++i) {
+        P.m[i] = 0; P.off[i] = 0;
+        if (i >= n_obs) continue;
+        if (m[i] < 1 || m[i] > OBCA_MAX_EDGES) return OBCA_E_INVAL;
+        P.m[i] = m[i];
+        P.off[i] = P.M;
+        P.M += m[i];
+    }
+    P.B = B; P.N = N; P.n_obs = n_obs; P.n_sub = n_sub; P.certified = certified;
+    P.target = target; P.gain = gain; P.grow_max = grow_max;
+    for (int j = 0; j < 4; ++j) P.ego[j] = ego[j];
+    segment_of(N, &P.seg, &P.log_seg);
+    P.variant = variant; P.status = status; P.x = x; P.A = A; P.b = b;
+    P.grow = grow; P.b_out = b_out; P.variant_out = variant_out; P.min_clear = min_clear;
+    ObcaDeviceGuard guard(device);
+    if (!guard.ok) return OBCA_E_HIP;
+    const int64_t lanes = (int64_t)B * P.seg;
+    hipLaunchKernelGGL(plan_tighten_kernel, dim3((unsigned)((lanes + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0,
                        (hipStream_t)hip_stream, P);
     return hipGetLastError() == hipSuccess ? OBCA_OK : OBCA_E_HIP;
 }

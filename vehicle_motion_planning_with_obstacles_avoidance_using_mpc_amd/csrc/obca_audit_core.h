@@ -477,6 +477,71 @@ AU_FN void plan_acc_add(PlanSweepAcc& a, int s, const PlanIntervalResult& R) {
     if (R.min_val < 0.0 && (a.coll < 0 || s < a.coll)) a.coll = s;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Clearance repair (obca_plan_tighten): where a feasible plan comes closer than `target` to an obstacle between two knots,
+// grow that obstacle at the two stages next to the interval, so that a re-solve against the grown rows keeps the knots
+// further out.  Nothing here touches the solver: the caller re-solves with b_out in place of b (A unchanged).
+//
+//   d[s,i]     the n_sub + 1 samples of plan_sweep for interval s, obstacle i alone (plan_tighten_distance): their
+//              smallest, or with `certified` obstacle i's own bound over the interval, plan_sub_bound with that obstacle's
+//              plan_obstacle_move -- NaN where its rows turn.  Always against the caller's ORIGINAL rows.
+//   need[s,i]  gain (target - d[s,i]) where d[s,i] < target, else 0 (plan_tighten_need)
+//   grow[k,i]  in/out, metres: min(grow_max, grow[k,i] + max(need[k-1,i], need[k,i])) over the intervals that exist; for
+//              variant 4 the largest need[.,i] at every stage, because obca_mpc4 reads stage 0's rows only.  Never decreases.
+//   b_out[k,r] b[k,r] + grow[k,i] |a_r|, |a_r| = hypot(A[k,r,0], A[k,r,1]), for every row r of obstacle i (plan_tighten_stage)
+//
+// Why the offset rows are enough.  Let K = {q : a_r q <= b_r for all r} and K' = {q : a_r q <= b_r + g |a_r|}.  A point q
+// within g of some q0 in K has a_r q = a_r q0 + a_r (q - q0) <= b_r + |a_r| g for every r: K' contains K grown by a disc of
+// radius g (at a vertex it contains more, the mitred corner).  The car at a knot that keeps dmin from K' therefore keeps
+// dmin + g from K.  That is a statement about knots.  Between two knots nothing is guaranteed: the shortfall measured
+// there is charged to the two knots next to it (for a half-plane, a car that does not turn and gain = 1 exactly: both
+// knots pushed out by e move every interpolated pose out by e), the re-solved plan may take another way, and so the caller measures again -- always
+// against the original rows -- and repeats a few rounds.
+//
+// Passed through (grow untouched, b_out = b + grow |a| as it stood, variant_out = 0): variant 0, a status outside {0, 1}
+// -- neither is measured, min_clear = NaN -- and an instance with a measurement that is not finite (min_clear = NaN, the
+// NaN rule of plan_distance).
+template <int MAXM>
+AU_FN double plan_tighten_distance(const PlanScene& S, int i, const double* p0, const double* p1, const double* A0,
+                                   const double* b0, const double* A1, const double* b1, int n_sub, int certified,
+                                   double rmax) {
+    const int o = S.off[i], m = S.m[i];
+    const double move = certified ? plan_obstacle_move(A0 + 2 * o, b0 + o, A1 + 2 * o, b1 + o, m) : 0.0;
+    double best = INFINITY, prev = 0.0;
+    for (int j = 0; j <= n_sub; ++j) {
+        double p[3], C[4][2];
+        sample_pose(p0, p1, n_sub, j, p);
+        car_corners(p[0], p[1], p[2], S.ego, C);
+        const double d = plan_rows_distance_m<MAXM>(C, A0 + 2 * o, b0 + o, A1 + 2 * o, b1 + o, m, n_sub, j);
+        if (!certified) best = min_nan(best, d);
+        else if (j > 0) best = min_nan(best, plan_sub_bound(p0, p1, n_sub, j, rmax, move, prev, d));
+        prev = d;
+    }
+    return best;
+}
+
+AU_FN double plan_tighten_need(double d, double target, double gain) { return d < target ? gain * (target - d) : 0.0; }
+
+// true when the plan of an instance is one to measure and repair
+AU_FN bool plan_tighten_active(int variant, int status) { return variant != 0 && (status == 0 || status == 1); }
+
+// one (stage, obstacle): grow by inc where `update` (the instance is not passed through), then the obstacle's m rows of
+// b_out from the stage's own A / b.  Returns 1 if grow rose.
+AU_FN int plan_tighten_stage(const double* Ak, const double* bk, int m, double inc, double grow_max, bool update, double* grow_ki,
+                             double* bout_k) {
+    RO_EXACT
+    double g = *grow_ki;
+    int rose = 0;
+    if (update) {
+        const double gn = dmax(g, dmin_(grow_max, g + inc));
+        rose = gn > g;
+        if (rose) *grow_ki = gn;
+        g = gn;
+    }
+    for (int r = 0; r < m; ++r) bout_k[r] = bk[r] + g * hypot(Ak[2 * r], Ak[2 * r + 1]);
+    return rose;
+}
+
 }  // namespace audit
 
 // ---------------------------------------------------------------------------------------------------------------------
