@@ -525,8 +525,31 @@ int obca_moving_rows_batch(int32_t B, int32_t N, int32_t Ms, int32_t n_box, cons
                            const double* boxes, const double* Ts, double half_window, double margin, double* A, double* b,
                            int32_t device, void* hip_stream);
 
+/* ------------------------------------------------------------------------------------------------------
+ * Refinement between the two stages of the open-loop planner (obca_mpc 0.12), on the device: stage 1's free-time plans in,
+ * stage 2's reference, step and variant mask out (the reference's closedLoop.update_path with allAviable = 1, src/closed_loop.py:567-589).
+ * DEVICE pointers: x [B,3,N+1], ts [B] and status [B] are obca_solve_batch's xopt, ts_opt and status (status NULL: every
+ * instance counts as feasible).  With N2 = ratio N, per instance:
+ *   xref_out [3,N2+1]  point j < N2, i = j / ratio, q = j % ratio: (double)q * ((x[i+1] - x[i]) / (double)ratio) + x[i] in
+ *                      x and y, multiply and add rounded separately (numpy's linspace without its endpoint, word for word);
+ *                      point N2 is knot N; yaw_j = atan2(py_j+1 - py_j, px_j+1 - px_j), yaw_N2 = yaw_N2-1
+ *   ts_out             ((double)N * ts) / (double)N2
+ *   variant_out        variant_ok: what obca_solve_batch is to run for stage 2 (variant_out may be NULL)
+ * Passed through -- variant_out = 0, every point of xref_out = knot 0 of the plan (zeros where that knot is not finite),
+ * ts_out = ts / ratio where ts is finite, else 0 --: a status outside {0, 1}, a knot or a difference of neighbouring
+ * positions that is not finite, ts not finite or <= 0.  No output is ever NaN, so that the launches that follow (the
+ * rows builder, the masked solve) read numbers throughout.
+ * B >= 1, N >= 1, ratio >= 1, ratio N <= 127 (the longest horizon of obca_dims), variant_ok 4, 6 or 8; x, ts, xref_out and
+ * ts_out not NULL.  Every argument is checked before the first HIP call; a refused call (OBCA_E_INVAL) has no side
+ * effect.  Asynchronous on hip_stream. */
+int obca_plan_refine(int32_t B, int32_t N, int32_t ratio, const double* x, const double* ts,
+                     const int32_t* status /* [B] or NULL */, int32_t variant_ok,
+                     double* xref_out /* [B,3,ratio N+1] */, double* ts_out /* [B] */,
+                     int32_t* variant_out /* [B] or NULL */, int32_t device, void* hip_stream);
+
 const char* obca_strerror(int code);
-/* "obca_mpc 0.11 (gfx950)": 0.11 = clearance repair of batched plans (obca_plan_tighten);
+/* "obca_mpc 0.12 (gfx950)": 0.12 = the refinement step of the two-stage open-loop planner (obca_plan_refine);
+ * 0.11 = clearance repair of batched plans (obca_plan_tighten);
  * 0.10 = obca_astar_batch's code -4 (start or goal outside the grid), obca_rasterise_batch clips boxes to the map;
  * 0.9 = swept audit of batched plans (obca_plan_sweep);
  * 0.8 = opt-in swept, inflated rows of moving boxes (obca_rollouts_set_swept_rows, obca_moving_rows_batch);

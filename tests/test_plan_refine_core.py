@@ -1,0 +1,225 @@
+"""CPU tier of the open-loop planner's refinement step (csrc/obca_refine_core.h, obca_plan_refine's per-point work), built for
+the host from tests/native/plan_refine_host.cpp.  Yardstick: the project's mirror of the reference,
+``closedLoop.update_path(allAviable=1)`` (numpy's linspace without its endpoint + ``a_star.create_reference_path``): positions
+and the rescaled step word for word (the host build has no FMA), yaws to 1e-12.  Then the pass-through rules and the refused
+calls.  The cases and helpers are shared with tests/test_gpu_two_stage.py.
+
+Inputs: neighbouring knots are exactly equal or at least 0.05 m apart and the ratio is at most 5, so a resampled segment is
+at least 0.01 m long and a position error of 1e-12 m turns a yaw by at most 2e-10 rad; yaws are compared as wrapped
+differences."""
+import ctypes
+import math
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from vehicle_motion_planning_with_obstacles_avoidance_using_mpc_amd.closed_loop import closedLoop
+from vehicle_motion_planning_with_obstacles_avoidance_using_mpc_amd.demo_setting import problemSetting
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+SRC = os.path.join(HERE, "native", "plan_refine_host.cpp")
+OUT = os.path.join(HERE, "native", "_build", "libplan_refine_host.so")
+DEPS = [SRC, os.path.join(ROOT, "vehicle_motion_planning_with_obstacles_avoidance_using_mpc_amd", "csrc", "obca_refine_core.h")]
+E_INVAL = -22
+SHAPES = [(2, 2), (5, 1), (3, 4), (13, 5)]           # (N, ratio)
+FILL_X, FILL_I = -777.25, -777
+
+
+def _p(a):
+    return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+
+
+def load_host():
+    """the host exerciser, compiled the way tests/test_plan_tighten_core.py compiles its one"""
+    if not os.path.exists(OUT) or any(os.path.getmtime(d) > os.path.getmtime(OUT) for d in DEPS):
+        os.makedirs(os.path.dirname(OUT), exist_ok=True)
+        subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", SRC, "-o", OUT], check=True)
+    lib = ctypes.CDLL(OUT)
+    lib.plan_refine_host.restype = ctypes.c_int
+    return lib
+
+
+@pytest.fixture(scope="module")
+def host():
+    return load_host()
+
+
+def host_refine(host, x, ts, ratio, status=None, variant_ok=6, rc=0, null=()):
+    """plan_refine_host on x [B,3,N+1], ts [B]: dict of xref [B,3,ratio N+1], ts_out [B], variant_out [B] (pre-filled with
+    FILL_X / FILL_I); ``null``: names of pointers handed over as NULL"""
+    x, ts = np.ascontiguousarray(x, float), np.ascontiguousarray(ts, float)
+    B, N = x.shape[0], x.shape[2] - 1
+    st = None if status is None else np.ascontiguousarray(status, np.int32)
+    o = {"xref": np.full((B, 3, max(int(ratio), 0) * N + 1), FILL_X), "ts_out": np.full(B, FILL_X),
+         "variant_out": np.full(B, FILL_I, np.int32)}
+    a = {"x": x, "ts": ts, "status": st, **o}
+    for k in null:
+        a[k] = None
+    got = host.plan_refine_host(B, N, int(ratio), _p(a["x"]), _p(a["ts"]), _p(a["status"]), int(variant_ok), _p(a["xref"]),
+                                _p(a["ts_out"]), _p(a["variant_out"]))
+    assert got == rc
+    return o
+
+
+_cl = None
+
+
+def mirror(plan, ts, ratio):
+    """the reference's refinement on ONE plan [3,N+1] through the project's mirror: (reference [3,ratio N+1], Ts_opt)"""
+    global _cl
+    if _cl is None:
+        _cl = closedLoop(problemSetting("demo1"), solver=object())
+    N = plan.shape[1] - 1
+    _cl.N_free, _cl.N_fix, _cl.xref, _cl.Ts_opt = N, ratio * N, np.array(plan, float), float(ts)
+    ref = _cl.update_path(0, 0, 0, allAviable=1, type="")
+    assert ref.shape == (3, ratio * N + 1) and _cl.N_fix == ratio * N
+    return np.asarray(ref, float), float(_cl.Ts_opt)
+
+
+def mirror_batch(x, ts, ratio):
+    out = [mirror(x[i], ts[i], ratio) for i in range(x.shape[0])]
+    return np.stack([o[0] for o in out]), np.array([o[1] for o in out])
+
+
+def random_plans(seed, B, N):
+    """B plans of N + 1 knots inside (0, 100) m: steps of 0.06 ... 3 m in any direction, every sixth step of a plan stands
+    still (exactly equal knots); step lengths 0.05 ... 0.4 s"""
+    rng = np.random.default_rng(seed)
+    x = np.zeros((B, 3, N + 1))
+    x[:, :2, 0] = rng.uniform(30.0, 60.0, (B, 2))
+    for k in range(N):
+        ang, ln = rng.uniform(-math.pi, math.pi, B), rng.uniform(0.06, 3.0, B)
+        ln = np.where((np.arange(B) + k) % 6 == 5, 0.0, ln)
+        x[:, 0, k + 1] = np.where(ln > 0, x[:, 0, k] + ln * np.cos(ang), x[:, 0, k])
+        x[:, 1, k + 1] = np.where(ln > 0, x[:, 1, k] + ln * np.sin(ang), x[:, 1, k])
+    x[:, 2] = rng.uniform(-math.pi, math.pi, (B, N + 1))
+    d = np.hypot(np.diff(x[:, 0]), np.diff(x[:, 1]))
+    assert np.all((d == 0) | (d >= 0.05)) and x[:, :2].min() > 0 and x[:, :2].max() < 100
+    return x, rng.uniform(0.05, 0.4, B)
+
+
+def words(a):
+    return np.ascontiguousarray(a, float).view(np.uint64)
+
+
+def wrapped(a, b):
+    """|a - b| modulo 2 pi"""
+    d = np.asarray(a) - np.asarray(b)
+    return np.abs((d + math.pi) % (2 * math.pi) - math.pi)
+
+
+def expected_fill(x, ts, ratio):
+    """what a passed-through instance gets: knot 0 at every point (zeros where it is not finite), ts / ratio where finite"""
+    B, N2 = x.shape[0], ratio * (x.shape[2] - 1)
+    k0 = np.where(np.isfinite(x[:, :, 0]).all(1, keepdims=True), x[:, :, 0], 0.0)
+    with np.errstate(invalid="ignore"):
+        return np.repeat(k0[:, :, None], N2 + 1, 2), np.where(np.isfinite(ts), ts / ratio, 0.0)
+
+
+@pytest.mark.parametrize("N,ratio", SHAPES)
+def test_random_plans_match_the_mirror(host, N, ratio):
+    x, ts = random_plans(300 + N, 7, N)
+    o = host_refine(host, x, ts, ratio, status=np.array([0, 1] * 4, np.int32)[:7])
+    ref, ts_ref = mirror_batch(x, ts, ratio)
+    assert np.array_equal(words(o["xref"][:, :2]), words(ref[:, :2]))
+    assert np.array_equal(words(o["ts_out"]), words(ts_ref))
+    assert wrapped(o["xref"][:, 2], ref[:, 2]).max() <= 1e-12
+    assert np.array_equal(o["variant_out"], np.full(7, 6, np.int32))
+    assert np.array_equal(words(o["xref"][:, :2, -1]), words(x[:, :2, -1]))         # point N2 is knot N itself
+    assert np.array_equal(words(o["xref"][:, 2, -1]), words(o["xref"][:, 2, -2]))   # the last point repeats the previous yaw
+
+
+def test_status_null_counts_as_feasible_and_variant_ok_is_written(host):
+    x, ts = random_plans(311, 3, 4)
+    a = host_refine(host, x, ts, 3, status=None, variant_ok=8)
+    b = host_refine(host, x, ts, 3, status=np.zeros(3, np.int32), variant_ok=4)
+    assert np.array_equal(words(a["xref"]), words(b["xref"])) and np.array_equal(words(a["ts_out"]), words(b["ts_out"]))
+    assert list(a["variant_out"]) == [8, 8, 8] and list(b["variant_out"]) == [4, 4, 4]
+    c = host_refine(host, x, ts, 3, null=("variant_out",))                       # variant_out may be NULL
+    assert np.array_equal(words(c["xref"]), words(a["xref"])) and np.all(c["variant_out"] == FILL_I)
+
+
+def test_stationary_interval_has_yaw_zero(host):
+    """atan2(0, 0) = 0: a plan that stands still over an interval"""
+    x = np.array([[[1.0, 2.0, 2.0, 3.5], [4.0, 4.5, 4.5, 4.5], [0.3, 0.3, 0.3, 0.3]]])
+    for ratio in (1, 3):
+        o = host_refine(host, x, [0.2], ratio)
+        ref, ts_ref = mirror(x[0], 0.2, ratio)
+        assert np.array_equal(words(o["xref"][0, :2]), words(ref[:2])) and words(o["ts_out"])[0] == words([ts_ref])[0]
+        assert wrapped(o["xref"][0, 2], ref[2]).max() <= 1e-12
+        assert np.all(o["xref"][0, 2, ratio:2 * ratio] == 0.0)
+        assert np.all(o["xref"][0, 2, 2 * ratio:] == 0.0)                   # straight in +x, and the repeated last yaw
+
+
+def test_straight_run_in_minus_x_has_yaw_pi(host):
+    """dy exactly 0, dx < 0: yaw = +pi at every point"""
+    x = np.array([[[9.0, 8.5, 7.0, 6.9], [3.25, 3.25, 3.25, 3.25], [0.0, 0.0, 0.0, 0.0]]])
+    o = host_refine(host, x, [0.1], 5)
+    ref, _ = mirror(x[0], 0.1, 5)
+    assert np.array_equal(words(o["xref"][0, :2]), words(ref[:2]))
+    assert np.all(o["xref"][0, 1] == 3.25)
+    assert np.abs(o["xref"][0, 2] - math.pi).max() <= 1e-12 and wrapped(o["xref"][0, 2], ref[2]).max() <= 1e-12
+
+
+def test_last_point_repeats_the_previous_yaw(host):
+    x, ts = random_plans(317, 4, 5)
+    x[:, :, -1] = x[:, :, -2] + np.array([0.5, -0.25, 0.0])                     # a last interval that moves
+    o = host_refine(host, x, ts, 2)
+    ref, _ = mirror_batch(x, ts, 2)
+    assert np.array_equal(words(o["xref"][:, 2, -1]), words(o["xref"][:, 2, -2]))
+    assert wrapped(o["xref"][:, 2, -2:], ref[:, 2, -2:]).max() <= 1e-12
+    assert np.abs(o["xref"][:, 2, -1] - math.atan2(-0.25, 0.5)).max() <= 1e-9
+
+
+def passthrough_case(N=3, seed=331):
+    """one batch with every pass-through reason next to refined instances: (x, ts, status, passed [B] bool)"""
+    x, ts = random_plans(seed, 10, N)
+    status = np.array([0, 2, 1, -1, -5, 0, 0, 0, 0, 1], np.int32)
+    x[5, 1, 2] = np.nan                   # a NaN knot, knot 0 finite: filled with knot 0
+    x[6, 0, 0] = np.inf                   # knot 0 itself not finite: zeros
+    ts[7] = 0.0                           # ts <= 0
+    ts[8] = np.nan                        # ts not finite: ts_out 0
+    passed = np.array([0, 1, 0, 1, 1, 1, 1, 1, 1, 0], bool)
+    ts[3] = -0.2                          # (a failed status with a negative step: ts / ratio all the same)
+    return x, ts, status, passed
+
+
+@pytest.mark.parametrize("ratio", [1, 2, 5])
+def test_pass_through(host, ratio):
+    x, ts, status, passed = passthrough_case()
+    o = host_refine(host, x, ts, ratio, status=status)
+    assert np.isfinite(o["xref"]).all() and np.isfinite(o["ts_out"]).all()
+    assert np.array_equal(o["variant_out"], np.where(passed, 0, 6).astype(np.int32))
+    fill, ts_fill = expected_fill(x, ts, ratio)
+    assert np.array_equal(words(o["xref"][passed]), words(fill[passed]))
+    assert np.array_equal(words(o["ts_out"][passed]), words(ts_fill[passed]))
+    assert np.all(o["xref"][6] == 0.0) and o["ts_out"][8] == 0.0 and o["ts_out"][7] == 0.0 and o["ts_out"][3] == -0.2 / ratio
+    ref, ts_ref = mirror_batch(x[~passed], ts[~passed], ratio)                  # the neighbours are refined as if alone
+    assert np.array_equal(words(o["xref"][~passed][:, :2]), words(ref[:, :2]))
+    assert np.array_equal(words(o["ts_out"][~passed]), words(ts_ref))
+    assert wrapped(o["xref"][~passed][:, 2], ref[:, 2]).max() <= 1e-12
+
+
+def test_overflowing_difference_is_passed_through(host):
+    """two finite knots whose difference is not: 0 x inf would put a NaN into the reference"""
+    x, ts = random_plans(337, 2, 2)
+    x[1, 0, 1], x[1, 0, 2] = 1.5e308, -1.5e308
+    o = host_refine(host, x, ts, 2)
+    assert list(o["variant_out"]) == [6, 0] and np.isfinite(o["xref"]).all()
+    assert np.array_equal(words(o["xref"][1]), words(np.repeat(x[1, :, :1], 5, 1)))
+
+
+@pytest.mark.parametrize("kw", [dict(ratio=0), dict(ratio=-1), dict(variant_ok=5), dict(variant_ok=0), dict(null=("xref",)),
+                                dict(null=("ts_out",)), dict(null=("x",)), dict(null=("ts",)), dict(ratio=26)],
+                         ids=lambda k: "-".join("%s=%s" % i for i in k.items()))
+def test_refused_calls_touch_nothing(host, kw):
+    """OBCA_E_INVAL before anything is written; ratio 26 x N 5 is beyond the longest horizon a solver handle takes (127)"""
+    x, ts = random_plans(341, 3, 5)
+    kw = dict(dict(ratio=2), **kw)
+    o = host_refine(host, x, ts, rc=E_INVAL, **kw)
+    assert np.all(o["xref"] == FILL_X) and np.all(o["ts_out"] == FILL_X) and np.all(o["variant_out"] == FILL_I)
+    assert host.plan_refine_host(0, 5, 2, _p(x), _p(ts), None, 6, _p(o["xref"]), _p(o["ts_out"]), None) == E_INVAL
+    assert host.plan_refine_host(3, 0, 2, _p(x), _p(ts), None, 6, _p(o["xref"]), _p(o["ts_out"]), None) == E_INVAL
