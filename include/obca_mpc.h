@@ -423,7 +423,9 @@ int obca_rasterise_batch(const double* boxes, int32_t B, int32_t K, double resol
  * {q : A q <= b} given by their rows in edge order (one row: half-plane; two: wedge; three or more: polygon).  Signed
  * distance: Euclidean distance when separated, minus the penetration depth (separating-axis value) when overlapping.
  * Read-only: neither call writes solver or rollout state.  Every argument is checked before the first HIP call; a
- * refused call (OBCA_E_INVAL) has no side effect.  Asynchronous on hip_stream.
+ * refused call (OBCA_E_INVAL) has no side effect.  That holds for all four calls below, and so does one more refusal: a
+ * batch too large for one launch (one segment of up to 64 lanes per instance or rollout, more than 2^31 - 1 blocks of
+ * 256 lanes) returns OBCA_E_INVAL.  Asynchronous on hip_stream.
  *
  * Plan clearance of obca_solve_batch outputs.  ego and m (n_obs entries, 1..OBCA_MAX_EDGES) are HOST pointers; the
  * rest DEVICE pointers in obca_solve_batch's shapes: x [B,3,N+1], A [B,N+1,M,2], b [B,N+1,M], variant [B] or NULL.

@@ -1,6 +1,6 @@
 // CPU exercise of the collision-audit geometry core (csrc/obca_audit_core.h) -- tests only.  Same source as the device
 // kernels of csrc/obca_audit.hip; lets the distance be compared with tests/kkt_check.py without a GPU.
-#include "../../vehicle_motion_planning_with_obstacles_avoidance_using_mpc_amd/csrc/obca_audit_core.h"
+#include "../../vehicle_motion_planning_with_obstacles_avoidance_using_mpc_amd/csrc/obca_plan_batch.h"
 
 constexpr int HOST_MAXM = 8;
 
@@ -36,34 +36,28 @@ extern "C" void audit_host_box_next(const double* info, double cx, double cy, in
 }
 
 // the plan audit of one batch (obca_plan_clearance's per-instance reduction, csrc/obca_audit.hip plan_clearance_kernel)
-// run serially over stages and obstacles with the shared audit::plan_distance / audit::better: x [B,3,N+1],
+// run serially over stages and obstacles with the shared audit::plan_distance / audit::better and the batch's validation
+// and indexing (csrc/obca_plan_batch.h): x [B,3,N+1],
 // A [B,N+1,M,2], b [B,N+1,M] with M = sum(m), variant [B] or NULL (4: stage 0's rows at every stage); outputs min_clear,
 // arg_stage, arg_obst [B], stage_obst [B,N+1,n_obs]
 extern "C" int audit_host_plan_clearance(const double* ego, int n_obs, const int* m, int N, int B, const int* variant,
                                          const double* x, const double* A, const double* b, double* min_clear, int* arg_stage,
                                          int* arg_obst, double* stage_obst) {
-    if (n_obs < 1 || n_obs > OBCA_MAX_OBST || N < 1 || B < 1) return -22;
-    int off[OBCA_MAX_OBST], M = 0;
-    for (int i = 0; i < n_obs; ++i) {
-        if (m[i] < 1 || m[i] > HOST_MAXM) return -22;
-        off[i] = M;
-        M += m[i];
-    }
-    const int N1 = N + 1;
+    audit::PlanBatch P;
+    if (audit::plan_batch_init(&P, ego, n_obs, m, N, B, variant, x, A, b, (int64_t)N + 1) != OBCA_OK) return OBCA_E_INVAL;
     for (int inst = 0; inst < B; ++inst) {
-        const int v = variant ? variant[inst] : 0;
-        const double* xb = x + (size_t)inst * 3 * N1;
+        const int v = audit::plan_variant(P, inst);
+        const size_t st0 = audit::plan_first(P, inst);
         double best = INFINITY;
         int bs = 0x7fffffff, bo = 0x7fffffff;
-        for (int k = 0; k < N1; ++k) {
-            double C[4][2];
-            audit::car_corners(xb[k], xb[N1 + k], xb[2 * N1 + k], ego, C);
-            const int ks = (v == 4) ? 0 : k;
-            const double* Ak = A + ((size_t)inst * N1 + ks) * M * 2;
-            const double* bk = b + ((size_t)inst * N1 + ks) * M;
+        for (int k = 0; k <= N; ++k) {
+            double p[3], C[4][2];
+            audit::plan_pose(P, inst, k, p);
+            audit::car_corners(p[0], p[1], p[2], ego, C);
+            const audit::PlanRows R = audit::plan_rows(P, st0, k, v, 0);
             for (int i = 0; i < n_obs; ++i) {
-                const double d = audit::plan_distance<HOST_MAXM>(C, Ak + 2 * off[i], bk + off[i], m[i]);
-                stage_obst[((size_t)inst * N1 + k) * n_obs + i] = d;
+                const double d = audit::plan_distance<OBCA_MAX_EDGES>(C, R.A0 + 2 * P.off[i], R.b0 + P.off[i], P.m[i]);
+                stage_obst[(st0 + k) * n_obs + i] = d;
                 if (audit::better(d, k, i, best, bs, bo)) { best = d; bs = k; bo = i; }
             }
         }

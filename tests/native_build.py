@@ -8,7 +8,6 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 SRC = os.path.join(HERE, "native", "rollout_host.cpp")
-OUT = os.path.join(HERE, "native", "_build", "libnative_host.so")
 CSRC = os.path.join(ROOT, "vehicle_motion_planning_with_obstacles_avoidance_using_mpc_amd", "csrc")
 DEPS = [SRC, os.path.join(HERE, "native", "lpi_host.cpp"), os.path.join(CSRC, "obca_lpi_core.h"),
         os.path.join(CSRC, "obca_rollout_core.h"), os.path.join(CSRC, "obca_astar_core.h"), os.path.join(CSRC, "obca_device.h"),
@@ -17,15 +16,24 @@ DEPS = [SRC, os.path.join(HERE, "native", "lpi_host.cpp"), os.path.join(CSRC, "o
 _lib = None
 
 
+def build_shim(name, sources, deps, openmp=False):
+    """tests/native/_build/lib<name>.so from ``sources``, compiled when it is missing or older than a source or one of
+    ``deps`` (the headers and included sources), and loaded.  Without contraction: the host words are the ones numpy and the
+    device's unfused expressions are compared with."""
+    out = os.path.join(HERE, "native", "_build", "lib%s.so" % name)
+    if not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in list(sources) + list(deps)):
+        os.makedirs(os.path.dirname(out), exist_ok=True)
+        omp = ["-fopenmp", "-Wno-unknown-pragmas"] if openmp else []
+        subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off"] + omp + list(sources) + ["-o", out],
+                       check=True)
+    return ctypes.CDLL(out)
+
+
 def load():
     global _lib
     if _lib is not None:
         return _lib
-    if not os.path.exists(OUT) or any(os.path.getmtime(d) > os.path.getmtime(OUT) for d in DEPS):
-        os.makedirs(os.path.dirname(OUT), exist_ok=True)
-        subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fopenmp", "-Wno-unknown-pragmas",
-                        SRC, "-o", OUT], check=True)
-    _lib = ctypes.CDLL(OUT)
+    _lib = build_shim("native_host", [SRC], DEPS, openmp=True)
     _lib.lpi_host_solve_batch.restype = ctypes.c_int
     _lib.lpi_host_solve_batch_cert.restype = ctypes.c_int
     _lib.rollout_host_run.restype = ctypes.c_int

@@ -5,31 +5,26 @@ refuse before any HIP call and so run without a GPU."""
 import ctypes
 import math
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
-from tests import kkt_check
+from tests import kkt_check, native_build
 from vehicle_motion_planning_with_obstacles_avoidance_using_mpc_amd.model_obstacle import obstacleModel, rectangle_vertices
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 SRC = os.path.join(HERE, "native", "audit_host.cpp")
-OUT = os.path.join(HERE, "native", "_build", "libaudit_host.so")
 CSRC = os.path.join(ROOT, "vehicle_motion_planning_with_obstacles_avoidance_using_mpc_amd", "csrc")
-DEPS = [SRC, os.path.join(CSRC, "obca_audit_core.h"), os.path.join(CSRC, "obca_rollout_core.h"), os.path.join(ROOT, "include", "obca_mpc.h")]
+DEPS = [SRC, os.path.join(CSRC, "obca_plan_batch.h"), os.path.join(CSRC, "obca_audit_core.h"), os.path.join(CSRC, "obca_rollout_core.h"),
+        os.path.join(ROOT, "include", "obca_mpc.h")]
 EGO = (1.7, 0.75, 1.7, 0.75)
 MAXM = 8                    # HOST_MAXM of audit_host.cpp
 E_INVAL = -22
 
 
 def load_host():
-    """the host shim, compiled the way tests/native_build.py compiles its own"""
-    if not os.path.exists(OUT) or any(os.path.getmtime(d) > os.path.getmtime(OUT) for d in DEPS):
-        os.makedirs(os.path.dirname(OUT), exist_ok=True)
-        subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", SRC, "-o", OUT], check=True)
-    lib = ctypes.CDLL(OUT)
+    lib = native_build.build_shim("audit_host", [SRC], DEPS)
     lib.audit_host_distance.restype = ctypes.c_int
     lib.audit_host_interval.restype = ctypes.c_int
     lib.audit_host_box_next.restype = None

@@ -6,8 +6,6 @@ same core fed with the device's own history; the stop's wave reduction at n_sub 
 and lock-step, and the audit of a stopped run."""
 import copy
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -32,14 +30,7 @@ def ahost():
 
 @pytest.fixture(scope="module")
 def shost():
-    """tests/native/rollout_stop_host.cpp, compiled as tests/test_rollout_stop_core.py compiles it"""
-    if not os.path.exists(stop_core.OUT) or any(os.path.getmtime(d) > os.path.getmtime(stop_core.OUT) for d in stop_core.DEPS):
-        os.makedirs(os.path.dirname(stop_core.OUT), exist_ok=True)
-        subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fopenmp", "-Wno-unknown-pragmas",
-                        stop_core.SRC, "-o", stop_core.OUT], check=True)
-    lib = ctypes.CDLL(stop_core.OUT)
-    lib.rollout_stop_host_audit.restype = ctypes.c_int
-    return lib
+    return stop_core.load_host()
 
 
 def _np(d):
@@ -368,3 +359,92 @@ def test_stop_wave_at_every_n_sub(shost, B, n_dyn):
                 n_stopped += int((on["flags"] == _lib.DONE_COLLISION).sum())
     dr_off.close()
     assert n_stopped > 0
+
+
+# ------------------------------------------------------------------- the plan calls' batch: refusals, wrapper = C call
+PAD = 32                          # sentinel words on either side of every output
+SENT_F, SENT_I = -777.25, -777
+CLEARANCE_OUTS = (("min_clear", torch.float64), ("arg_stage", torch.int32), ("arg_obst", torch.int32), ("stage_obst", torch.float64))
+
+
+def _dev_ptr(t):
+    return None if t is None else ctypes.c_void_p(t.data_ptr())
+
+
+def _guarded_clearance(B, N1, n_obs):
+    """every output of obca_plan_clearance in the middle of a buffer of sentinels: name -> (buffer, view of the output)"""
+    out = {}
+    for name, dt in CLEARANCE_OUTS:
+        n = B * N1 * n_obs if name == "stage_obst" else B
+        buf = torch.full((n + 2 * PAD,), SENT_F if dt == torch.float64 else SENT_I, dtype=dt, device="cuda")
+        out[name] = (buf, buf[PAD:PAD + n])
+    return out
+
+
+def _sentinels(g, inner):
+    torch.cuda.synchronize()
+    for name, (buf, view) in g.items():
+        s = SENT_F if buf.dtype == torch.float64 else SENT_I
+        assert (buf[:PAD] == s).all() and (buf[-PAD:] == s).all(), name
+        assert bool((view == s).all()) if inner else not (view == s).any(), name
+
+
+def _raw_clearance(g, c, **over):
+    """obca_plan_clearance itself on the device tensors of c, outputs into the guarded buffers g; `over` replaces
+    arguments of the C call by name"""
+    from tests.test_plan_batch_core import batch_args
+    own = dict({k: _dev_ptr(v[1]) for k, v in g.items()}, device=torch.cuda.current_device())
+    own.update({k: over.pop(k) for k in list(over) if k in own})
+    return _lib.load().obca_plan_clearance(*batch_args(c, _dev_ptr, **over), *[own[k] for k, _ in CLEARANCE_OUTS], own["device"],
+                                           ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+
+
+@pytest.fixture(scope="module")
+def small():
+    from tests.test_plan_batch_core import small_batch
+    c = small_batch()
+    t = lambda a, dt=torch.float64: torch.as_tensor(np.ascontiguousarray(a), dtype=dt, device="cuda")
+    return c, dict(x=t(c["x"]), A=t(c["A"]), b=t(c["b"]), m=c["m"], variant=t(c["variant"], torch.int32))
+
+
+def _refusals():
+    from tests.test_plan_batch_core import REFUSALS
+    return REFUSALS + [dict(min_clear=None), dict(arg_stage=None), dict(arg_obst=None), dict(device=-1)]
+
+
+@pytest.mark.parametrize("bad", _refusals(), ids=lambda d: "%s=%s" % next(iter(d.items())))
+def test_refused_plan_clearance_leaves_every_output_alone(small, bad):
+    """the batch's refusal table (tests/test_plan_batch_core.py) and obca_plan_clearance's own pointers through the C ABI:
+    host-side checks only, the call returns before it touches the device"""
+    c, dev = small
+    dev = dict(dev, variant=None)
+    g = _guarded_clearance(5, 4, 3)
+    assert _raw_clearance(g, dev, **bad) == core.E_INVAL
+    _sentinels(g, inner=True)
+    assert _raw_clearance(g, dev) == 0                                         # and the same call, unchanged, runs
+    _sentinels(g, inner=False)
+
+
+@pytest.mark.parametrize("inputs", ["torch", "numpy"])
+def test_plan_wrappers_equal_the_c_calls(small, inputs):
+    """audit.plan_clearance (no variant) and audit.plan_sweep (variants 4, 6, 8, 0, 6) against the raw C calls, word for word,
+    from device tensors and from numpy arrays"""
+    from tests import test_gpu_plan_sweep as gsweep
+    from vehicle_motion_planning_with_obstacles_avoidance_using_mpc_amd.audit import plan_clearance, plan_sweep
+    c, dev = small
+    src = dev if inputs == "torch" else c
+    words = lambda t: t.contiguous().reshape(-1).view(torch.uint8).cpu()
+    g = _guarded_clearance(5, 4, 3)
+    assert _raw_clearance(g, dict(dev, variant=None)) == 0
+    _sentinels(g, inner=False)
+    got = plan_clearance(src["x"], src["A"], src["b"], c["m"], ego=core.EGO, per_stage=True)
+    assert sorted(got) == sorted(k for k, _ in CLEARANCE_OUTS)
+    for k, _ in CLEARANCE_OUTS:
+        assert torch.equal(words(got[k]), words(g[k][1])), k
+    gs = gsweep._guarded(5, 3)
+    assert gsweep.raw_call(gs, (dev["x"], dev["A"], dev["b"], dev["variant"]), c["m"], n_sub=16) == 0
+    gsweep._untouched(gs)
+    got = plan_sweep(src["x"], src["A"], src["b"], c["m"], n_sub=16, ego=core.EGO, variant=src["variant"], per_interval=True)
+    assert sorted(got) == sorted(gs)
+    for k in gs:
+        assert torch.equal(words(got[k]), words(gs[k][1])), k

@@ -10,18 +10,17 @@ differences."""
 import ctypes
 import math
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+from tests import native_build
 from vehicle_motion_planning_with_obstacles_avoidance_using_mpc_amd.closed_loop import closedLoop
 from vehicle_motion_planning_with_obstacles_avoidance_using_mpc_amd.demo_setting import problemSetting
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 SRC = os.path.join(HERE, "native", "plan_refine_host.cpp")
-OUT = os.path.join(HERE, "native", "_build", "libplan_refine_host.so")
 DEPS = [SRC, os.path.join(ROOT, "vehicle_motion_planning_with_obstacles_avoidance_using_mpc_amd", "csrc", "obca_refine_core.h")]
 E_INVAL = -22
 SHAPES = [(2, 2), (5, 1), (3, 4), (13, 5)]           # (N, ratio)
@@ -33,11 +32,7 @@ def _p(a):
 
 
 def load_host():
-    """the host exerciser, compiled the way tests/test_plan_tighten_core.py compiles its one"""
-    if not os.path.exists(OUT) or any(os.path.getmtime(d) > os.path.getmtime(OUT) for d in DEPS):
-        os.makedirs(os.path.dirname(OUT), exist_ok=True)
-        subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", SRC, "-o", OUT], check=True)
-    lib = ctypes.CDLL(OUT)
+    lib = native_build.build_shim("plan_refine_host", [SRC], DEPS)
     lib.plan_refine_host.restype = ctypes.c_int
     return lib
 

@@ -6,18 +6,16 @@ rules.  The cases are built once and shared with tests/test_gpu_plan_sweep.py.""
 import ctypes
 import math
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
-from tests import kkt_check
+from tests import kkt_check, native_build
 from tests import test_audit_core as core
 from vehicle_motion_planning_with_obstacles_avoidance_using_mpc_amd.model_obstacle import rectangle_vertices
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "native", "plan_sweep_host.cpp")
-OUT = os.path.join(HERE, "native", "_build", "libplan_sweep_host.so")
 DEPS = [SRC] + core.DEPS[1:]
 EGO = core.EGO
 TOL = 1e-9
@@ -25,11 +23,7 @@ M3 = [1, 2, 4]                    # a half-plane, a wedge and a box
 
 
 def load_host():
-    """the host exerciser, compiled the way tests/test_audit_core.py compiles its one"""
-    if not os.path.exists(OUT) or any(os.path.getmtime(d) > os.path.getmtime(OUT) for d in DEPS):
-        os.makedirs(os.path.dirname(OUT), exist_ok=True)
-        subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", SRC, "-o", OUT], check=True)
-    lib = ctypes.CDLL(OUT)
+    lib = native_build.build_shim("plan_sweep_host", [SRC], DEPS)
     lib.plan_sweep_host.restype = ctypes.c_int
     lib.plan_sweep_host_move.restype = ctypes.c_double
     return lib

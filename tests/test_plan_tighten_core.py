@@ -7,7 +7,6 @@ CPU solver.  The cases and helpers are shared with tests/test_gpu_plan_tighten.p
 import ctypes
 import math
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -18,7 +17,6 @@ from tests import test_plan_sweep_core as sweep_core
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "native", "plan_tighten_host.cpp")
-OUT = os.path.join(HERE, "native", "_build", "libplan_tighten_host.so")
 DEPS = [SRC] + core.DEPS[1:]
 EGO = core.EGO
 TOL = 1e-9
@@ -26,11 +24,7 @@ _p = core._p
 
 
 def load_host():
-    """the host exerciser, compiled the way tests/test_plan_sweep_core.py compiles its one"""
-    if not os.path.exists(OUT) or any(os.path.getmtime(d) > os.path.getmtime(OUT) for d in DEPS):
-        os.makedirs(os.path.dirname(OUT), exist_ok=True)
-        subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", SRC, "-o", OUT], check=True)
-    lib = ctypes.CDLL(OUT)
+    lib = native_build.build_shim("plan_tighten_host", [SRC], DEPS)
     lib.plan_tighten_host.restype = ctypes.c_int
     return lib
 

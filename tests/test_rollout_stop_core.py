@@ -6,7 +6,6 @@ history up to there; exact sensing hands the solver the sensed box's own rectang
 import copy
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -20,7 +19,6 @@ from vehicle_motion_planning_with_obstacles_avoidance_using_mpc_amd.scenarios im
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 SRC = os.path.join(HERE, "native", "rollout_stop_host.cpp")
-OUT = os.path.join(HERE, "native", "_build", "librollout_stop_host.so")
 CSRC = os.path.join(ROOT, "vehicle_motion_planning_with_obstacles_avoidance_using_mpc_amd", "csrc")
 DEPS = native_build.DEPS + [SRC, os.path.join(CSRC, "obca_audit_core.h")]
 EGO = (1.7, 0.75, 1.7, 0.75)
@@ -30,17 +28,17 @@ KEYS = ("x_closed", "u_closed", "T_closed", "x_openloop", "variant", "iters", "s
 COLLISION = 4
 
 
-@pytest.fixture(scope="module")
-def host():
-    """the shim in its own library, compiled the way tests/native_build.py compiles the plain one"""
-    if not os.path.exists(OUT) or any(os.path.getmtime(d) > os.path.getmtime(OUT) for d in DEPS):
-        os.makedirs(os.path.dirname(OUT), exist_ok=True)
-        subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fopenmp", "-Wno-unknown-pragmas",
-                        SRC, "-o", OUT], check=True)
-    lib = ctypes.CDLL(OUT)
+def load_host():
+    """the shim in its own library"""
+    lib = native_build.build_shim("rollout_stop_host", [SRC], DEPS, openmp=True)
     for f in ("rollout_stop_host_run", "rollout_stop_host_rows", "rollout_stop_host_audit"):
         getattr(lib, f).restype = ctypes.c_int
     return lib
+
+
+@pytest.fixture(scope="module")
+def host():
+    return load_host()
 
 
 def _p(a):

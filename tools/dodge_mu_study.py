@@ -18,9 +18,7 @@ subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=o
                 native_build.SRC, "-o", out], check=True)
 for name, lib in (("product (mu 1)", None), ("first level at mu " + mu, out)):
     if lib:
-        native_build._lib = None
-        native_build.OUT = lib
-        native_build.DEPS = []
+        native_build._lib = ctypes.CDLL(lib)
     fx = reference_report.fixture()
     gif = reference_report.gif_demo11()
     for which, st, key in (("demo11", reference_report.demo11_setting(), "figure11_demo11"), ("demo1", reference_report.demo1_setting(), "figure12_demo1")):

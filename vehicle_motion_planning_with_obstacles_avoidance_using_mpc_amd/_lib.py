@@ -160,15 +160,15 @@ def load():
     lib.obca_rollouts_set_warm_start.restype = ctypes.c_int
     lib.obca_rollouts_read.argtypes = [ctypes.c_void_p] + [vp] * 11
     lib.obca_rollouts_read.restype = ctypes.c_int
-    lib.obca_plan_clearance.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32,
-                                        ctypes.c_int32, i32p, vp, vp, vp, vp, i32p, i32p, vp, ctypes.c_int32, vp]
+    # the plan calls take one batch: ego, n_obs, m, N, B, variant, (tighten: status,) x, A, b ... device, stream
+    plan_head = [ctypes.POINTER(ctypes.c_double), ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, ctypes.c_int32, i32p]
+    plan_xAb, plan_tail = [vp, vp, vp], [ctypes.c_int32, vp]
+    lib.obca_plan_clearance.argtypes = plan_head + plan_xAb + [vp, i32p, i32p, vp] + plan_tail
     lib.obca_plan_clearance.restype = ctypes.c_int
-    lib.obca_plan_sweep.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32,
-                                    ctypes.c_int32, i32p, vp, vp, vp, ctypes.c_int32, vp, vp, i32p, i32p, i32p, vp, ctypes.c_int32, vp]
+    lib.obca_plan_sweep.argtypes = plan_head + plan_xAb + [ctypes.c_int32, vp, vp, i32p, i32p, i32p, vp] + plan_tail
     lib.obca_plan_sweep.restype = ctypes.c_int
-    lib.obca_plan_tighten.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32,
-                                      ctypes.c_int32, i32p, i32p, vp, vp, vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_double,
-                                      ctypes.c_double, ctypes.c_double, vp, vp, i32p, vp, ctypes.c_int32, vp]
+    lib.obca_plan_tighten.argtypes = plan_head + [i32p] + plan_xAb + [ctypes.c_int32, ctypes.c_int32, ctypes.c_double, ctypes.c_double,
+                                                                      ctypes.c_double, vp, vp, i32p, vp] + plan_tail
     lib.obca_plan_tighten.restype = ctypes.c_int
     lib.obca_rollouts_audit.argtypes = [ctypes.c_void_p, ctypes.c_int32, vp, vp, i32p, i32p, i32p, i32p, vp, vp]
     lib.obca_rollouts_audit.restype = ctypes.c_int
@@ -196,6 +196,23 @@ def load():
     lib.obca_version.restype = ctypes.c_char_p
     _lib = lib
     return lib
+
+
+def ptr(t):
+    """the address of tensor ``t`` as a C argument: NULL for None and for a tensor without elements (whose data_ptr() is 0)"""
+    return None if t is None or t.numel() == 0 else ctypes.c_void_p(t.data_ptr())
+
+
+def stream_ptr(dev):
+    """the current stream of torch device ``dev`` as a C argument"""
+    import torch
+    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+def device_index(dev):
+    """the ordinal of torch device ``dev``; the current device's for a bare "cuda\""""
+    import torch
+    return dev.index if dev.index is not None else torch.cuda.current_device()
 
 
 def check(code):

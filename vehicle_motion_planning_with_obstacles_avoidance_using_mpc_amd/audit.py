@@ -21,34 +21,44 @@ def _device_tensor(a, dtype, device):
     return torch.as_tensor(np.asarray(a) if not isinstance(a, torch.Tensor) else a, dtype=dtype, device=device).contiguous()
 
 
+def _plan_batch(x, A, b, m, ego, variant, device, status=None, tighten=False):
+    """The batch the three plan calls share, on the device: resolves the device (``device``, else x's if x is a device
+    tensor, else the current one), moves and reshapes x, A, b, variant (None: NULL unless ``tighten``) and, for
+    ``tighten``, status.  Returns (dev, B, N1, m, keep, head, tail): head = the leading arguments of the C call up to b,
+    tail = its device and stream, keep = the tensors head points into, to be held until the call is made."""
+    import torch
+    dev = torch.device(device) if device is not None else (x.device if isinstance(x, torch.Tensor) and x.is_cuda else
+                                                           torch.device("cuda", torch.cuda.current_device()))
+    m = [int(v) for v in m]
+    x = _device_tensor(x, torch.float64, dev)
+    B, N1, M = int(x.shape[0]), int(x.shape[2]), sum(m)
+    x = x.reshape(B, 3, N1)
+    A = _device_tensor(A, torch.float64, dev).reshape(B, N1, M, 2)
+    b = _device_tensor(b, torch.float64, dev).reshape(B, N1, M)
+    ints = [None if variant is None and not tighten else _device_tensor(variant, torch.int32, dev).reshape(B)]
+    if tighten:
+        ints.append(_device_tensor(status, torch.int32, dev).reshape(B))
+    ego_c = (ctypes.c_double * 4)(*[float(v) for v in ego])
+    m_c = (ctypes.c_int32 * max(len(m), 1))(*m)
+    keep = ints + [x, A, b]
+    head = [ego_c, len(m), m_c, N1 - 1, B] + [_lib.ptr(t) for t in keep]
+    return dev, B, N1, m, keep, head, [_lib.device_index(dev), _lib.stream_ptr(dev)]
+
+
 def plan_clearance(x, A, b, m, ego=DEFAULT_EGO, variant=None, per_stage=False, device=None):
     """x [B,3,N+1], A [B,N+1,M,2], b [B,N+1,M] (torch tensors or numpy arrays), m: rows per obstacle; variant [B] or None
     (4: every stage against stage 0's rows, as obca_mpc4 reads them).  Returns a dict of device tensors on the current
     stream: min_clear [B], arg_stage [B], arg_obst [B] and, with per_stage, stage_obst [B,N+1,n_obs]."""
     import torch
-    dev = torch.device(device) if device is not None else (x.device if isinstance(x, torch.Tensor) and x.is_cuda else
-                                                           torch.device("cuda", torch.cuda.current_device()))
-    lib = _lib.load()
-    m = [int(v) for v in m]
-    x = _device_tensor(x, torch.float64, dev)
-    B, N1 = int(x.shape[0]), int(x.shape[2])
-    M = sum(m)
-    x = x.reshape(B, 3, N1)
-    A = _device_tensor(A, torch.float64, dev).reshape(B, N1, M, 2)
-    b = _device_tensor(b, torch.float64, dev).reshape(B, N1, M)
-    var = None if variant is None else _device_tensor(variant, torch.int32, dev).reshape(B)
+    dev, B, N1, m, keep, head, tail = _plan_batch(x, A, b, m, ego, variant, device)
     out = {"min_clear": torch.empty(B, dtype=torch.float64, device=dev),
            "arg_stage": torch.empty(B, dtype=torch.int32, device=dev),
            "arg_obst": torch.empty(B, dtype=torch.int32, device=dev)}
     if per_stage:
         out["stage_obst"] = torch.empty(B, N1, len(m), dtype=torch.float64, device=dev)
-    p = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
-    ego_c = (ctypes.c_double * 4)(*[float(v) for v in ego])
-    m_c = (ctypes.c_int32 * max(len(m), 1))(*m)
-    stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    _lib.check(lib.obca_plan_clearance(ego_c, len(m), m_c, N1 - 1, B, p(var), p(x), p(A), p(b), p(out["min_clear"]),
-                                       p(out["arg_stage"]), p(out["arg_obst"]), p(out.get("stage_obst")),
-                                       dev.index if dev.index is not None else torch.cuda.current_device(), stream))
+    p = _lib.ptr
+    _lib.check(_lib.load().obca_plan_clearance(*head, p(out["min_clear"]), p(out["arg_stage"]), p(out["arg_obst"]),
+                                               p(out.get("stage_obst")), *tail))
     return out
 
 
@@ -58,17 +68,7 @@ def plan_sweep(x, A, b, m, n_sub=16, ego=DEFAULT_EGO, variant=None, per_interval
     min_clear, lower_bound (certified for translating obstacles, else NaN), arg_interval, arg_obst, first_collision [B]
     and, with per_interval, interval_min [B,N]."""
     import torch
-    dev = torch.device(device) if device is not None else (x.device if isinstance(x, torch.Tensor) and x.is_cuda else
-                                                           torch.device("cuda", torch.cuda.current_device()))
-    lib = _lib.load()
-    m = [int(v) for v in m]
-    x = _device_tensor(x, torch.float64, dev)
-    B, N1 = int(x.shape[0]), int(x.shape[2])
-    M = sum(m)
-    x = x.reshape(B, 3, N1)
-    A = _device_tensor(A, torch.float64, dev).reshape(B, N1, M, 2)
-    b = _device_tensor(b, torch.float64, dev).reshape(B, N1, M)
-    var = None if variant is None else _device_tensor(variant, torch.int32, dev).reshape(B)
+    dev, B, N1, m, keep, head, tail = _plan_batch(x, A, b, m, ego, variant, device)
     out = {"min_clear": torch.empty(B, dtype=torch.float64, device=dev),
            "lower_bound": torch.empty(B, dtype=torch.float64, device=dev),
            "arg_interval": torch.empty(B, dtype=torch.int32, device=dev),
@@ -76,14 +76,9 @@ def plan_sweep(x, A, b, m, n_sub=16, ego=DEFAULT_EGO, variant=None, per_interval
            "first_collision": torch.empty(B, dtype=torch.int32, device=dev)}
     if per_interval:
         out["interval_min"] = torch.empty(B, max(N1 - 1, 0), dtype=torch.float64, device=dev)
-    p = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
-    ego_c = (ctypes.c_double * 4)(*[float(v) for v in ego])
-    m_c = (ctypes.c_int32 * max(len(m), 1))(*m)
-    stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    _lib.check(lib.obca_plan_sweep(ego_c, len(m), m_c, N1 - 1, B, p(var), p(x), p(A), p(b), int(n_sub), p(out["min_clear"]),
-                                   p(out["lower_bound"]), p(out["arg_interval"]), p(out["arg_obst"]), p(out["first_collision"]),
-                                   p(out.get("interval_min")), dev.index if dev.index is not None else torch.cuda.current_device(),
-                                   stream))
+    p = _lib.ptr
+    _lib.check(_lib.load().obca_plan_sweep(*head, int(n_sub), p(out["min_clear"]), p(out["lower_bound"]), p(out["arg_interval"]),
+                                           p(out["arg_obst"]), p(out["first_collision"]), p(out.get("interval_min")), *tail))
     return out
 
 
@@ -97,18 +92,8 @@ def plan_tighten(x, A, b, m, variant, status, grow=None, b_out=None, n_sub=16, c
     b_out if given, which must not be b), variant_out [B] (variant where grow rose, else 0: the variant argument of the
     next solve) and min_clear [B] (NaN: not measured, or not finite)."""
     import torch
-    dev = torch.device(device) if device is not None else (x.device if isinstance(x, torch.Tensor) and x.is_cuda else
-                                                           torch.device("cuda", torch.cuda.current_device()))
-    lib = _lib.load()
-    m = [int(v) for v in m]
-    x = _device_tensor(x, torch.float64, dev)
-    B, N1 = int(x.shape[0]), int(x.shape[2])
+    dev, B, N1, m, keep, head, tail = _plan_batch(x, A, b, m, ego, variant, device, status, tighten=True)
     M = sum(m)
-    x = x.reshape(B, 3, N1)
-    A = _device_tensor(A, torch.float64, dev).reshape(B, N1, M, 2)
-    b = _device_tensor(b, torch.float64, dev).reshape(B, N1, M)
-    var = _device_tensor(variant, torch.int32, dev).reshape(B)
-    st = _device_tensor(status, torch.int32, dev).reshape(B)
     if grow is None:
         grow = torch.zeros(B, N1, len(m), dtype=torch.float64, device=dev)
     if b_out is None:
@@ -119,14 +104,9 @@ def plan_tighten(x, A, b, m, variant, status, grow=None, b_out=None, n_sub=16, c
             raise ValueError("grow / b_out: expected a contiguous float64 device tensor of shape %s" % (shape,))
     out = {"grow": grow, "b_out": b_out, "variant_out": torch.empty(B, dtype=torch.int32, device=dev),
            "min_clear": torch.empty(B, dtype=torch.float64, device=dev)}
-    p = lambda t: ctypes.c_void_p(t.data_ptr())
-    ego_c = (ctypes.c_double * 4)(*[float(v) for v in ego])
-    m_c = (ctypes.c_int32 * max(len(m), 1))(*m)
-    stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    _lib.check(lib.obca_plan_tighten(ego_c, len(m), m_c, N1 - 1, B, p(var), p(st), p(x), p(A), p(b), int(n_sub), int(bool(certified)),
-                                     float(target), float(gain), float(grow_max), p(grow), p(b_out), p(out["variant_out"]),
-                                     p(out["min_clear"]), dev.index if dev.index is not None else torch.cuda.current_device(),
-                                     stream))
+    p = _lib.ptr
+    _lib.check(_lib.load().obca_plan_tighten(*head, int(n_sub), int(bool(certified)), float(target), float(gain), float(grow_max),
+                                             p(grow), p(b_out), p(out["variant_out"]), p(out["min_clear"]), *tail))
     return out
 
 

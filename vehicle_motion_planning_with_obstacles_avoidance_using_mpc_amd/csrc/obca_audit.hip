@@ -6,11 +6,16 @@
 // Layout: the lanes of a wavefront are cut into segments of seg = next power of two >= the items of one instance (plan:
 // its N + 1 stages, plan sweep: its N intervals, rollout: its max_steps intervals; at most 64), one instance per segment;
 // a lane walks the items sub, sub + seg, ... of its instance (for an interval: its samples in order, both ends of every
-// sub-interval in registers), then the segment reduces min / arg-min with xor shuffles that never leave it.
+// sub-interval in registers), then the segment reduces min / arg-min with xor shuffles that never leave it (seg_reduce).
+//
+// The three plan calls take the same batch: audit::PlanBatch of csrc/obca_plan_batch.h, which validates it once
+// (plan_batch_init) and is the only code that indexes x / A / b -- for the kernels here and for the host shims of
+// tests/native alike.  Every entry point is: its own checks, the batch's (plan calls), its own fields, launch_segments.
+// Every check comes before the first HIP call, so a refused call has no side effect.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include "obca_device.h"
-#include "obca_audit_core.h"
+#include "obca_plan_batch.h"
 
 // defined in obca_rollout.hip (internal, not part of the C ABI): the handle's device-state descriptor, its shape and the
 // parameters of its last obca_rollouts_reset; OBCA_E_INVAL when the handle has not been reset
@@ -21,38 +26,28 @@ namespace {
 constexpr int WAVE = 64;
 constexpr int BLOCK = 256;
 
+using audit::PlanBatch;
+
 struct PlanArgs {
-    int32_t B, N, n_obs, M;
-    int32_t m[OBCA_MAX_OBST], off[OBCA_MAX_OBST];
-    double ego[4];
-    int32_t seg, log_seg;
-    const int32_t* variant;
-    const double *x, *A, *b;
+    PlanBatch P;
     double* min_clear;
     int32_t *arg_stage, *arg_obst;
     double* stage_obst;
 };
 
 struct SweepArgs {
-    int32_t B, N, n_obs, M;
-    int32_t m[OBCA_MAX_OBST], off[OBCA_MAX_OBST];
-    double ego[4];
-    int32_t seg, log_seg, n_sub;
-    const int32_t* variant;
-    const double *x, *A, *b;
+    PlanBatch P;
+    int32_t n_sub;
     double *min_clear, *lower_bound;
     int32_t *arg_interval, *arg_obst, *first_collision;
     double* interval_min;
 };
 
 struct TightenArgs {
-    int32_t B, N, n_obs, M;
-    int32_t m[OBCA_MAX_OBST], off[OBCA_MAX_OBST];
-    double ego[4];
-    int32_t seg, log_seg, n_sub, certified;
+    PlanBatch P;
+    int32_t n_sub, certified;
     double target, gain, grow_max;
-    const int32_t *variant, *status;
-    const double *x, *A, *b;
+    const int32_t* status;
     double *grow, *b_out;
     int32_t* variant_out;
     double* min_clear;
@@ -80,96 +75,93 @@ __device__ inline void seg_argmin(double& v, int& s, int& o, int seg) {
     }
 }
 
-__device__ inline double seg_min(double v, int seg) {
-    for (int w = seg >> 1; w > 0; w >>= 1) v = fmin(v, __shfl_xor(v, w, WAVE));
+// v op its partner's v, halving the distance until every lane of the segment holds the segment's value
+template <class T, class Op>
+__device__ inline T seg_reduce(T v, int seg, Op op) {
+    for (int w = seg >> 1; w > 0; w >>= 1) v = op(v, __shfl_xor(v, w, WAVE));
     return v;
 }
 
-__device__ inline double seg_min_nan(double v, int seg) {      // a NaN in the segment wins (audit::min_nan)
-    for (int w = seg >> 1; w > 0; w >>= 1) v = audit::min_nan(v, __shfl_xor(v, w, WAVE));
-    return v;
+__device__ inline double seg_min(double v, int seg) { return seg_reduce(v, seg, [](double a, double b) { return fmin(a, b); }); }
+__device__ inline double seg_max(double v, int seg) { return seg_reduce(v, seg, [](double a, double b) { return fmax(a, b); }); }
+// a NaN in the segment wins
+__device__ inline double seg_min_nan(double v, int seg) { return seg_reduce(v, seg, [](double a, double b) { return audit::min_nan(a, b); }); }
+// smallest index >= 0, -1 if none: as unsigned, -1 is the largest
+__device__ inline int seg_min_nonneg(int v, int seg) { return (int)seg_reduce((unsigned)v, seg, [](unsigned a, unsigned b) { return b < a ? b : a; }); }
+__device__ inline int seg_or(int v, int seg) { return seg_reduce(v, seg, [](int a, int b) { return a | b; }); }
+
+// the instance of this lane's segment and the lane's place in it.  Whole segments are live (inst < B) or not, so the
+// shuffles of a reduction stay uniform.
+struct Lane {
+    int64_t inst;
+    int sub;
+};
+
+__device__ inline Lane lane_of(const PlanBatch& P) {
+    const int64_t gl = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    return {gl >> P.log_seg, (int)(gl & (P.seg - 1))};
 }
 
-__device__ inline int seg_min_nonneg(int v, int seg) {        // smallest index >= 0, -1 if none
-    unsigned u = (unsigned)v;                                    // -1 -> UINT_MAX
-    for (int w = seg >> 1; w > 0; w >>= 1) {
-        const unsigned u2 = (unsigned)__shfl_xor((int)u, w, WAVE);
-        u = u2 < u ? u2 : u;
-    }
-    return (int)u;
-}
-
-__global__ void __launch_bounds__(BLOCK) plan_clearance_kernel(PlanArgs P) {
-    const int gl = blockIdx.x * blockDim.x + threadIdx.x;
-    const int inst = gl >> P.log_seg, sub = gl & (P.seg - 1);
-    const bool live = inst < P.B;                               // whole segments are live or not: the shuffles stay uniform
-    const int N1 = P.N + 1;
+__global__ void __launch_bounds__(BLOCK) plan_clearance_kernel(PlanArgs G) {
+    const PlanBatch& P = G.P;
+    const auto [inst, sub] = lane_of(P);
+    const bool live = inst < P.B;
     double best = INFINITY;
     int bs = 0x7fffffff, bo = 0x7fffffff;
     if (live) {
-        const int v = P.variant ? P.variant[inst] : 0;
-        for (int k = sub; k < N1; k += P.seg) {
-            const double* xb = P.x + (size_t)inst * 3 * N1;
-            double C[4][2];
-            audit::car_corners(xb[k], xb[N1 + k], xb[2 * N1 + k], P.ego, C);
-            const int ks = (v == 4) ? 0 : k;                       // obca_mpc4 reads stage 0's rows at every stage (q5)
-            const double* Ak = P.A + ((size_t)inst * N1 + ks) * P.M * 2;
-            const double* bk = P.b + ((size_t)inst * N1 + ks) * P.M;
+        const int v = audit::plan_variant(P, inst);
+        const size_t st0 = audit::plan_first(P, inst);
+        for (int k = sub; k <= P.N; k += P.seg) {
+            double p[3], C[4][2];
+            audit::plan_pose(P, inst, k, p);
+            audit::car_corners(p[0], p[1], p[2], P.ego, C);
+            const audit::PlanRows R = audit::plan_rows(P, st0, k, v, 0);
             for (int i = 0; i < P.n_obs; ++i) {
-                const double d = audit::plan_distance<OBCA_MAX_EDGES>(C, Ak + 2 * P.off[i], bk + P.off[i], P.m[i]);
-                if (P.stage_obst) P.stage_obst[((size_t)inst * N1 + k) * P.n_obs + i] = d;
+                const double d = audit::plan_distance<OBCA_MAX_EDGES>(C, R.A0 + 2 * P.off[i], R.b0 + P.off[i], P.m[i]);
+                if (G.stage_obst) G.stage_obst[(st0 + k) * P.n_obs + i] = d;
                 if (better(d, k, i, best, bs, bo)) { best = d; bs = k; bo = i; }
             }
         }
     }
     seg_argmin(best, bs, bo, P.seg);
     if (live && sub == 0) {
-        P.min_clear[inst] = best;
-        P.arg_stage[inst] = bs;
-        P.arg_obst[inst] = bo;
+        G.min_clear[inst] = best;
+        G.arg_stage[inst] = bs;
+        G.arg_obst[inst] = bo;
     }
 }
 
 // one lane per (instance, interval): audit::plan_interval on the plan's own arrays, the rows of both stages read in place
-__global__ void __launch_bounds__(BLOCK) plan_sweep_kernel(SweepArgs P) {
-    const int64_t gl = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t inst = gl >> P.log_seg;
-    const int sub = (int)(gl & (P.seg - 1));
-    const bool live = inst < P.B;                               // whole segments are live or not: the shuffles stay uniform
-    const int N1 = P.N + 1;
+__global__ void __launch_bounds__(BLOCK) plan_sweep_kernel(SweepArgs G) {
+    const PlanBatch& P = G.P;
+    const auto [inst, sub] = lane_of(P);
+    const bool live = inst < P.B;
     audit::PlanSweepAcc acc;
     audit::plan_acc_init(acc);
     if (live) {
-        const int v = P.variant ? P.variant[inst] : 0;
-        audit::PlanScene sc;
-        sc.ego = P.ego; sc.n_obs = P.n_obs; sc.m = P.m; sc.off = P.off;
-        const double* xb = P.x + (size_t)inst * 3 * N1;
+        const int v = audit::plan_variant(P, inst);
+        const audit::PlanScene sc = audit::plan_scene(P);
+        const size_t st0 = audit::plan_first(P, inst);
         for (int s = sub; s < P.N; s += P.seg) {
-            const double p0[3] = {xb[s], xb[N1 + s], xb[2 * N1 + s]};
-            const double p1[3] = {xb[s + 1], xb[N1 + s + 1], xb[2 * N1 + s + 1]};
-            const size_t k0 = (size_t)inst * N1 + ((v == 4) ? 0 : s);       // obca_mpc4 reads stage 0's rows at every stage
-            const size_t k1 = (v == 4) ? k0 : k0 + 1;
-            const audit::PlanIntervalResult R = audit::plan_interval<OBCA_MAX_EDGES>(
-                sc, p0, p1, P.A + k0 * P.M * 2, P.b + k0 * P.M, P.A + k1 * P.M * 2, P.b + k1 * P.M, P.n_sub);
-            if (P.interval_min) P.interval_min[(size_t)inst * P.N + s] = R.min_val;
-            audit::plan_acc_add(acc, s, R);
+            double p0[3], p1[3];
+            audit::plan_pose(P, inst, s, p0);
+            audit::plan_pose(P, inst, s + 1, p1);
+            const audit::PlanRows R = audit::plan_rows(P, st0, s, v);
+            const audit::PlanIntervalResult I = audit::plan_interval<OBCA_MAX_EDGES>(sc, p0, p1, R.A0, R.b0, R.A1, R.b1, G.n_sub);
+            if (G.interval_min) G.interval_min[(size_t)inst * P.N + s] = I.min_val;
+            audit::plan_acc_add(acc, s, I);
         }
     }
     seg_argmin(acc.best, acc.bs, acc.bo, P.seg);
     acc.lower = seg_min_nan(acc.lower, P.seg);
     acc.coll = seg_min_nonneg(acc.coll, P.seg);
     if (live && sub == 0) {
-        P.min_clear[inst] = acc.best;
-        P.lower_bound[inst] = acc.lower;
-        P.arg_interval[inst] = acc.bs;
-        P.arg_obst[inst] = acc.bo;
-        P.first_collision[inst] = acc.coll;
+        G.min_clear[inst] = acc.best;
+        G.lower_bound[inst] = acc.lower;
+        G.arg_interval[inst] = acc.bs;
+        G.arg_obst[inst] = acc.bo;
+        G.first_collision[inst] = acc.coll;
     }
-}
-
-__device__ inline double seg_max(double v, int seg) {
-    for (int w = seg >> 1; w > 0; w >>= 1) v = fmax(v, __shfl_xor(v, w, WAVE));
-    return v;
 }
 
 // Clearance repair (audit::plan_tighten_* of csrc/obca_audit_core.h).  plan_sweep_kernel's layout: lane `sub` of a segment
@@ -183,31 +175,28 @@ __device__ inline double seg_max(double v, int seg) {
 //      segment, in which the last lane sends its carry and every other lane its current need.
 // Every shuffle sits outside the per-instance conditions and the pass loops have the same trip count in every lane, so
 // all 64 lanes reach each one.
-__global__ void __launch_bounds__(BLOCK) plan_tighten_kernel(TightenArgs P) {
-    const int64_t gl = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t inst = gl >> P.log_seg;
-    const int sub = (int)(gl & (P.seg - 1));
-    const bool live = inst < P.B;                               // whole segments are live or not: the shuffles stay uniform
-    const int N1 = P.N + 1, N = P.N, seg = P.seg;
-    const int v = live ? P.variant[inst] : 0;
-    const bool active = live && audit::plan_tighten_active(v, P.status[inst]);
-    const size_t st0 = live ? (size_t)inst * N1 : 0;             // first stage of the instance
-    audit::PlanScene sc;
-    sc.ego = P.ego; sc.n_obs = P.n_obs; sc.m = P.m; sc.off = P.off;
+__global__ void __launch_bounds__(BLOCK) plan_tighten_kernel(TightenArgs G) {
+    const PlanBatch& P = G.P;
+    const auto [inst, sub] = lane_of(P);
+    const bool live = inst < P.B;
+    const int N = P.N, seg = P.seg;
+    const int v = live ? audit::plan_variant(P, inst) : 0;
+    const bool v4 = audit::plan_reads_stage0(v);                 // its need is the largest over all intervals, at every stage
+    const bool active = live && audit::plan_tighten_active(v, G.status[inst]);
+    const size_t st0 = live ? audit::plan_first(P, inst) : 0;
+    const audit::PlanScene sc = audit::plan_scene(P);
     double mc = active ? INFINITY : NAN;
     if (active) {
         const double rmax = audit::car_radius(P.ego);
-        const double* xb = P.x + (size_t)inst * 3 * N1;
         for (int s = sub; s < N; s += seg) {
-            const double p0[3] = {xb[s], xb[N1 + s], xb[2 * N1 + s]};
-            const double p1[3] = {xb[s + 1], xb[N1 + s + 1], xb[2 * N1 + s + 1]};
-            const size_t k0 = st0 + ((v == 4) ? 0 : s);                     // obca_mpc4 reads stage 0's rows at every stage
-            const size_t k1 = (v == 4) ? k0 : k0 + 1;
+            double p0[3], p1[3];
+            audit::plan_pose(P, inst, s, p0);
+            audit::plan_pose(P, inst, s + 1, p1);
+            const audit::PlanRows R = audit::plan_rows(P, st0, s, v);
             for (int i = 0; i < P.n_obs; ++i) {
-                const double d = audit::plan_tighten_distance<OBCA_MAX_EDGES>(sc, i, p0, p1, P.A + k0 * P.M * 2, P.b + k0 * P.M,
-                                                                              P.A + k1 * P.M * 2, P.b + k1 * P.M, P.n_sub,
-                                                                              P.certified, rmax);
-                P.b_out[(st0 + s) * P.M + P.off[i]] = d;
+                const double d = audit::plan_tighten_distance<OBCA_MAX_EDGES>(sc, i, p0, p1, R.A0, R.b0, R.A1, R.b1, G.n_sub,
+                                                                              G.certified, rmax);
+                G.b_out[(st0 + s) * P.M + P.off[i]] = d;
                 mc = audit::min_nan(mc, d);
             }
         }
@@ -220,30 +209,30 @@ __global__ void __launch_bounds__(BLOCK) plan_tighten_kernel(TightenArgs P) {
         double nmax = 0.0;
         if (ok)
             for (int s = sub; s < N; s += seg)
-                nmax = fmax(nmax, audit::plan_tighten_need(P.b_out[(st0 + s) * P.M + o], P.target, P.gain));
+                nmax = fmax(nmax, audit::plan_tighten_need(G.b_out[(st0 + s) * P.M + o], G.target, G.gain));
         nmax = seg_max(nmax, seg);
         double carry = 0.0;
         for (int s0 = 0; s0 < N; s0 += seg) {
             const int s = s0 + sub;
             const bool has = live && s < N;
-            const double nd = (ok && has) ? audit::plan_tighten_need(P.b_out[(st0 + s) * P.M + o], P.target, P.gain) : 0.0;
+            const double nd = (ok && has) ? audit::plan_tighten_need(G.b_out[(st0 + s) * P.M + o], G.target, G.gain) : 0.0;
             const double left = __shfl(sub == seg - 1 ? carry : nd, (sub - 1) & (seg - 1), seg);
             carry = nd;
             if (has) {
                 const size_t k = st0 + s;
-                rose |= audit::plan_tighten_stage(P.A + (k * P.M + o) * 2, P.b + k * P.M + o, P.m[i], v == 4 ? nmax : fmax(left, nd),
-                                                  P.grow_max, ok, P.grow + k * P.n_obs + i, P.b_out + k * P.M + o);
+                const audit::PlanRows own = audit::plan_rows(P, st0, s, 0);          // variant 0: stage s's and s + 1's own rows
+                rose |= audit::plan_tighten_stage(own.A0 + 2 * o, own.b0 + o, P.m[i], v4 ? nmax : fmax(left, nd), G.grow_max, ok,
+                                                  G.grow + k * P.n_obs + i, G.b_out + k * P.M + o);
                 if (s == N - 1)
-                    rose |= audit::plan_tighten_stage(P.A + ((k + 1) * P.M + o) * 2, P.b + (k + 1) * P.M + o, P.m[i],
-                                                      v == 4 ? nmax : nd, P.grow_max, ok, P.grow + (k + 1) * P.n_obs + i,
-                                                      P.b_out + (k + 1) * P.M + o);
+                    rose |= audit::plan_tighten_stage(own.A1 + 2 * o, own.b1 + o, P.m[i], v4 ? nmax : nd, G.grow_max, ok,
+                                                      G.grow + (k + 1) * P.n_obs + i, G.b_out + (k + 1) * P.M + o);
             }
         }
     }
-    for (int w = seg >> 1; w > 0; w >>= 1) rose |= __shfl_xor(rose, w, WAVE);
+    rose = seg_or(rose, seg);
     if (live && sub == 0) {
-        P.variant_out[inst] = rose ? v : 0;
-        if (P.min_clear) P.min_clear[inst] = mc;
+        G.variant_out[inst] = rose ? v : 0;
+        if (G.min_clear) G.min_clear[inst] = mc;
     }
 }
 
@@ -327,17 +316,15 @@ __global__ void __launch_bounds__(BLOCK) rollouts_audit_kernel(AuditArgs G) {
     }
 }
 
-void segment_of(int items, int32_t* seg, int32_t* log_seg) {
-    int s = 1, l = 0;
-    while (s < items && s < WAVE) { s <<= 1; ++l; }
-    *seg = s; *log_seg = l;
-}
-
-bool ego_ok(const double* ego) {
-    if (!ego) return false;
-    for (int j = 0; j < 4; ++j)
-        if (!isfinite(ego[j])) return false;
-    return ego[0] + ego[2] > 0.0 && ego[1] + ego[3] > 0.0;
+// one segment of seg lanes per instance; OBCA_E_INVAL (before any HIP call) when that is more blocks than one launch takes
+template <class Args>
+int launch_segments(void (*kernel)(Args), const Args& args, int64_t instances, int seg, int device, void* hip_stream) {
+    const int64_t blocks = (instances * seg + BLOCK - 1) / BLOCK;
+    if (blocks > 0x7fffffff) return OBCA_E_INVAL;
+    ObcaDeviceGuard guard(device);
+    if (!guard.ok) return OBCA_E_HIP;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(BLOCK), 0, (hipStream_t)hip_stream, args);
+    return hipGetLastError() == hipSuccess ? OBCA_OK : OBCA_E_HIP;
 }
 
 }  // namespace
@@ -346,62 +333,26 @@ extern "C" int obca_plan_clearance(const double ego[4], int32_t n_obs, const int
                                    const int32_t* variant, const double* x, const double* A, const double* b,
                                    double* min_clear, int32_t* arg_stage, int32_t* arg_obst, double* stage_obst,
                                    int32_t device, void* hip_stream) {
-    // every argument is checked before the first HIP call: a refused call has no side effect
-    if (!ego_ok(ego) || n_obs < 1 || n_obs > OBCA_MAX_OBST || !m || N < 1 || N > (1 << 20) || B < 1 || device < 0 ||
-        !x || !A || !b || !min_clear || !arg_stage || !arg_obst)
+    PlanArgs G;
+    if (device < 0 || !min_clear || !arg_stage || !arg_obst ||
+        audit::plan_batch_init(&G.P, ego, n_obs, m, N, B, variant, x, A, b, (int64_t)N + 1) != OBCA_OK)
         return OBCA_E_INVAL;
-    PlanArgs P;
-    P.M = 0;
-    for (int i = 0; i < n_obs; ++i) {
-        if (m[i] < 1 || m[i] > OBCA_MAX_EDGES) return OBCA_E_INVAL;
-        P.m[i] = m[i];
-        P.off[i] = P.M;
-        P.M += m[i];
-    }
-    P.B = B; P.N = N; P.n_obs = n_obs;
-    for (int j = 0; j < 4; ++j) P.ego[j] = ego[j];
-    segment_of(N + 1, &P.seg, &P.log_seg);
-    P.variant = variant; P.x = x; P.A = A; P.b = b;
-    P.min_clear = min_clear; P.arg_stage = arg_stage; P.arg_obst = arg_obst; P.stage_obst = stage_obst;
-    ObcaDeviceGuard guard(device);
-    if (!guard.ok) return OBCA_E_HIP;
-    const int64_t lanes = (int64_t)B * P.seg;
-    hipLaunchKernelGGL(plan_clearance_kernel, dim3((unsigned)((lanes + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0,
-                       (hipStream_t)hip_stream, P);
-    return hipGetLastError() == hipSuccess ? OBCA_OK : OBCA_E_HIP;
+    G.min_clear = min_clear; G.arg_stage = arg_stage; G.arg_obst = arg_obst; G.stage_obst = stage_obst;
+    return launch_segments(plan_clearance_kernel, G, B, G.P.seg, device, hip_stream);
 }
 
 extern "C" int obca_plan_sweep(const double ego[4], int32_t n_obs, const int32_t* m, int32_t N, int32_t B,
                                const int32_t* variant, const double* x, const double* A, const double* b, int32_t n_sub,
                                double* min_clear, double* lower_bound, int32_t* arg_interval, int32_t* arg_obst,
                                int32_t* first_collision, double* interval_min, int32_t device, void* hip_stream) {
-    // every argument is checked before the first HIP call: a refused call has no side effect
-    if (!ego_ok(ego) || n_obs < 1 || n_obs > OBCA_MAX_OBST || !m || N < 1 || N > (1 << 20) || B < 1 || device < 0 ||
-        n_sub < 1 || n_sub > (1 << 16) || !x || !A || !b || !min_clear || !lower_bound || !arg_interval || !arg_obst ||
-        !first_collision)
+    SweepArgs G;
+    if (device < 0 || n_sub < 1 || n_sub > (1 << 16) || !min_clear || !lower_bound || !arg_interval || !arg_obst ||
+        !first_collision || audit::plan_batch_init(&G.P, ego, n_obs, m, N, B, variant, x, A, b, N) != OBCA_OK)
         return OBCA_E_INVAL;
-    SweepArgs P;
-    P.M = 0;
-    for (int i = 0; i < OBCA_MAX_OBST; ++i) {
-        P.m[i] = 0; P.off[i] = 0;
-        if (i >= n_obs) continue;
-        if (m[i] < 1 || m[i] > OBCA_MAX_EDGES) return OBCA_E_INVAL;
-        P.m[i] = m[i];
-        P.off[i] = P.M;
-        P.M += m[i];
-    }
-    P.B = B; P.N = N; P.n_obs = n_obs; P.n_sub = n_sub;
-    for (int j = 0; j < 4; ++j) P.ego[j] = ego[j];
-    segment_of(N, &P.seg, &P.log_seg);
-    P.variant = variant; P.x = x; P.A = A; P.b = b;
-    P.min_clear = min_clear; P.lower_bound = lower_bound; P.arg_interval = arg_interval; P.arg_obst = arg_obst;
-    P.first_collision = first_collision; P.interval_min = interval_min;
-    ObcaDeviceGuard guard(device);
-    if (!guard.ok) return OBCA_E_HIP;
-    const int64_t lanes = (int64_t)B * P.seg;
-    hipLaunchKernelGGL(plan_sweep_kernel, dim3((unsigned)((lanes + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0,
-                       (hipStream_t)hip_stream, P);
-    return hipGetLastError() == hipSuccess ? OBCA_OK : OBCA_E_HIP;
+    G.n_sub = n_sub;
+    G.min_clear = min_clear; G.lower_bound = lower_bound; G.arg_interval = arg_interval; G.arg_obst = arg_obst;
+    G.first_collision = first_collision; G.interval_min = interval_min;
+    return launch_segments(plan_sweep_kernel, G, B, G.P.seg, device, hip_stream);
 }
 
 extern "C" int obca_plan_tighten(const double ego[4], int32_t n_obs, const int32_t* m, int32_t N, int32_t B,
@@ -409,34 +360,16 @@ extern "C" int obca_plan_tighten(const double ego[4], int32_t n_obs, const int32
                                  const double* b, int32_t n_sub, int32_t certified, double target, double gain,
                                  double grow_max, double* grow, double* b_out, int32_t* variant_out, double* min_clear,
                                  int32_t device, void* hip_stream) {
-    // every argument is checked before the first HIP call: a refused call has no side effect
-    if (!ego_ok(ego) || n_obs < 1 || n_obs > OBCA_MAX_OBST || !m || N < 1 || N > (1 << 20) || B < 1 || device < 0 ||
-        n_sub < 1 || n_sub > (1 << 16) || !variant || !status || !x || !A || !b || !grow || !b_out || !variant_out ||
-        b_out == b || (certified != 0 && certified != 1) || !isfinite(target) || !(gain > 0.0 && gain <= 8.0) ||
-        !(grow_max >= 0.0 && grow_max <= 2.0))
+    TightenArgs G;
+    if (device < 0 || n_sub < 1 || n_sub > (1 << 16) || !variant || !status || !grow || !b_out || !variant_out || b_out == b ||
+        (certified != 0 && certified != 1) || !isfinite(target) || !(gain > 0.0 && gain <= 8.0) ||
+        !(grow_max >= 0.0 && grow_max <= 2.0) || audit::plan_batch_init(&G.P, ego, n_obs, m, N, B, variant, x, A, b, N) != OBCA_OK)
         return OBCA_E_INVAL;
-    TightenArgs P;
-    P.M = 0;
-    for (int i = 0; i < OBCA_MAX_OBST; ++i) {
-        P.m[i] = 0; P.off[i] = 0;
-        if (i >= n_obs) continue;
-        if (m[i] < 1 || m[i] > OBCA_MAX_EDGES) return OBCA_E_INVAL;
-        P.m[i] = m[i];
-        P.off[i] = P.M;
-        P.M += m[i];
-    }
-    P.B = B; P.N = N; P.n_obs = n_obs; P.n_sub = n_sub; P.certified = certified;
-    P.target = target; P.gain = gain; P.grow_max = grow_max;
-    for (int j = 0; j < 4; ++j) P.ego[j] = ego[j];
-    segment_of(N, &P.seg, &P.log_seg);
-    P.variant = variant; P.status = status; P.x = x; P.A = A; P.b = b;
-    P.grow = grow; P.b_out = b_out; P.variant_out = variant_out; P.min_clear = min_clear;
-    ObcaDeviceGuard guard(device);
-    if (!guard.ok) return OBCA_E_HIP;
-    const int64_t lanes = (int64_t)B * P.seg;
-    hipLaunchKernelGGL(plan_tighten_kernel, dim3((unsigned)((lanes + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0,
-                       (hipStream_t)hip_stream, P);
-    return hipGetLastError() == hipSuccess ? OBCA_OK : OBCA_E_HIP;
+    G.n_sub = n_sub; G.certified = certified;
+    G.target = target; G.gain = gain; G.grow_max = grow_max;
+    G.status = status;
+    G.grow = grow; G.b_out = b_out; G.variant_out = variant_out; G.min_clear = min_clear;
+    return launch_segments(plan_tighten_kernel, G, B, G.P.seg, device, hip_stream);
 }
 
 extern "C" int obca_rollouts_audit(obca_rollouts* r, int32_t n_sub, double* min_clear, double* lower_bound,
@@ -450,19 +383,14 @@ extern "C" int obca_rollouts_audit(obca_rollouts* r, int32_t n_sub, double* min_
     obca_params prm;
     const int rc = obca_internal_rollouts_view(r, &G.D, &dims, &prm);       // host-side copy; no HIP call
     if (rc != OBCA_OK) return rc;
-    if (!ego_ok(prm.ego) || !(prm.dmin == prm.dmin)) return OBCA_E_INVAL;
+    if (!audit::ego_ok(prm.ego) || !(prm.dmin == prm.dmin)) return OBCA_E_INVAL;
     G.n_static = dims.n_static;
     for (int i = 0; i < OBCA_MAX_OBST; ++i) G.m[i] = i < dims.n_static ? dims.m_static[i] : 0;
     for (int j = 0; j < 4; ++j) G.ego[j] = prm.ego[j];
     G.dmin = prm.dmin;
     G.n_sub = n_sub;
-    segment_of(G.D.S, &G.seg, &G.log_seg);
+    audit::segment_of(G.D.S, &G.seg, &G.log_seg);
     G.min_clear = min_clear; G.lower_bound = lower_bound; G.arg_step = arg_step; G.arg_obst = arg_obst;
     G.first_collision = first_collision; G.first_violation = first_violation; G.step_min = step_min;
-    ObcaDeviceGuard guard(dims.device);
-    if (!guard.ok) return OBCA_E_HIP;
-    const int64_t lanes = (int64_t)G.D.B * G.seg;
-    hipLaunchKernelGGL(rollouts_audit_kernel, dim3((unsigned)((lanes + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0,
-                       (hipStream_t)hip_stream, G);
-    return hipGetLastError() == hipSuccess ? OBCA_OK : OBCA_E_HIP;
+    return launch_segments(rollouts_audit_kernel, G, G.D.B, G.seg, dims.device, hip_stream);
 }

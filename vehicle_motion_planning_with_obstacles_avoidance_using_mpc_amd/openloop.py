@@ -12,7 +12,6 @@ Everything runs on the current stream without host synchronisation, the way ``cl
 stage 2 solves, and which of them ``obca_mpc8`` answers, is decided by variant masks built on the device.
 """
 import copy
-import ctypes
 
 import numpy as np
 
@@ -46,10 +45,9 @@ def refine(x, ts, ratio, status=None, variant_ok=6, device=None):
     xref = torch.empty(B, 3, max(ratio, 0) * N + 1, dtype=torch.float64, device=dev)
     ts_out = torch.empty(B, dtype=torch.float64, device=dev)
     variant_out = torch.empty(B, dtype=torch.int32, device=dev)
-    ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
+    ptr = _lib.ptr
     _lib.check(lib.obca_plan_refine(B, N, ratio, ptr(x), ptr(ts), ptr(status), int(variant_ok), ptr(xref), ptr(ts_out),
-                                    ptr(variant_out), dev.index if dev.index is not None else torch.cuda.current_device(),
-                                    ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+                                    ptr(variant_out), _lib.device_index(dev), _lib.stream_ptr(dev)))
     return xref, ts_out, variant_out
 
 

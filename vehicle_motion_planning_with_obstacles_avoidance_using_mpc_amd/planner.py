@@ -44,9 +44,9 @@ def plan_batch(grids, starts, goals, path_max=None, device=None):
         raise ValueError("grid too large for the planner (rows*cols <= 65535)")
     work = torch.empty(need, dtype=torch.uint8, device=dev)
     yaw = (ctypes.c_double * 9)(*yaw_table().tolist())
-    ptr = lambda t: ctypes.c_void_p(t.data_ptr())
+    ptr = _lib.ptr
     _lib.check(lib.obca_astar_batch(ptr(g), B, rows, cols, ptr(st), ptr(go), yaw, P, ptr(path), ptr(plen), ptr(work),
-                                    need, ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+                                    need, _lib.stream_ptr(dev)))
     # the launch is asynchronous: the tensors it reads must outlive it.  They are tied to the RESULT (a second call
     # before the stream drains must not free the first call's workspace), and the caching allocator keeps a freed block
     # out of other streams' hands until this stream has passed the free point.
@@ -76,7 +76,6 @@ def rasterise_batch(obstacle_lists, map_size, resolution=1.0, device=None):
     cols = int((map_size[0] - 1) / resolution) + 1
     bx = torch.as_tensor(boxes, device=dev)
     grid = torch.empty(B, rows, cols, dtype=torch.uint8, device=dev)
-    _lib.check(lib.obca_rasterise_batch(ctypes.c_void_p(bx.data_ptr()), B, K, float(resolution), rows, cols,
-                                        ctypes.c_void_p(grid.data_ptr()), ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+    _lib.check(lib.obca_rasterise_batch(_lib.ptr(bx), B, K, float(resolution), rows, cols, _lib.ptr(grid), _lib.stream_ptr(dev)))
     bx.record_stream(torch.cuda.current_stream(dev))
     return grid

@@ -231,8 +231,7 @@ class DeviceRollouts:
         self.N, self.max_steps, self.Ts0 = int(N), int(max_steps), float(Ts0)
         self.N_fix = self.N if N_fix is None else int(N_fix)
         self.params = params or SolverParams(xL=getattr(self.w, "xL", (0.0, 0.0)), xU=getattr(self.w, "xU", (39.0, 10.0)))
-        dev_index = self.device.index if self.device.index is not None else torch.cuda.current_device()
-        self._dims = rollout_dims(self.w, N, max_steps, dev_index, self.N_fix)
+        self._dims = rollout_dims(self.w, N, max_steps, _lib.device_index(self.device), self.N_fix)
         h = ctypes.c_void_p()
         _lib.check(self.lib.obca_rollouts_create(ctypes.byref(self._dims), ctypes.byref(h)))
         self._h = h
@@ -251,7 +250,7 @@ class DeviceRollouts:
         self.reset()
 
     def _stream(self):
-        return ctypes.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
+        return _lib.stream_ptr(self.device)
 
     def reset(self):
         t, w = self.torch, self.w
@@ -260,7 +259,7 @@ class DeviceRollouts:
                         dev(w.path_len, t.int32), dev(w.static_A, t.float64), dev(w.static_b, t.float64),
                         dev(w.dyn if w.n_dyn else np.zeros((w.batch, 1, 13)), t.float64)]
         self._cparams = self.params.to_c()
-        ptrs = [ctypes.c_void_p(x.data_ptr()) for x in self._inputs]
+        ptrs = [_lib.ptr(x) for x in self._inputs]
         _lib.check(self.lib.obca_rollouts_reset(self._h, *ptrs, self.Ts0, w.sense_dis, ctypes.byref(self._cparams),
                                                 self._stream()))
         self.steps_enqueued = 0
@@ -292,11 +291,11 @@ class DeviceRollouts:
         out = {"x_closed": f(B, S + 1, 3), "u_closed": f(B, S, 2), "T_closed": f(B, S), "x_openloop": f(B, S, 3, N1),
                "variant": i(B, S), "iters": i(B, S), "status": i(B, S), "dyn": f(B, S, nd, 4) if nd else t.zeros(B, S, 1, 4, dtype=t.float64, device=self.device), "steps": i(B), "flags": i(B)}
         order = ("x_closed", "u_closed", "T_closed", "x_openloop", "variant", "iters", "status", "dyn", "steps", "flags")
-        ptrs = [ctypes.c_void_p(out[k].data_ptr()) if (k != "dyn" or nd) else None for k in order]
+        ptrs = [_lib.ptr(out[k]) if (k != "dyn" or nd) else None for k in order]
         _lib.check(self.lib.obca_rollouts_read(self._h, *ptrs, self._stream()))
         if self.collision_stop is not None:
             out["clearance"] = f(B, S)
-            _lib.check(self.lib.obca_rollouts_read_clearance(self._h, ctypes.c_void_p(out["clearance"].data_ptr()), self._stream()))
+            _lib.check(self.lib.obca_rollouts_read_clearance(self._h, _lib.ptr(out["clearance"]), self._stream()))
         return out
 
     def audit(self, n_sub=8, per_step=False):
@@ -311,7 +310,7 @@ class DeviceRollouts:
         if per_step:
             out["step_min"] = f(B, self.max_steps)
         order = ("min_clear", "lower_bound", "arg_step", "arg_obst", "first_collision", "first_violation", "step_min")
-        ptrs = [ctypes.c_void_p(out[k].data_ptr()) if k in out else None for k in order]
+        ptrs = [_lib.ptr(out.get(k)) for k in order]
         _lib.check(self.lib.obca_rollouts_audit(self._h, int(n_sub), *ptrs, self._stream()))
         return out
 

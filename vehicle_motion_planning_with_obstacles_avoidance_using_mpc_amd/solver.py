@@ -102,7 +102,7 @@ class BatchSolver:
         self.max_batch = int(max_batch)
         d = _lib.ObcaDims()
         d.N, d.n_obs, d.max_batch = self.N, self.n_obs, self.max_batch
-        d.device = self.device.index if self.device.index is not None else torch.cuda.current_device()
+        d.device = _lib.device_index(self.device)
         for i, v in enumerate(self.m):
             d.m[i] = v
         self._dims = d
@@ -144,8 +144,7 @@ class BatchSolver:
             ny = int(self.lib.obca_dual_size(ctypes.byref(self._dims)))
             self.cert_z = torch.zeros(self.max_batch, nz, dtype=torch.float64, device=self.device)
             self.cert_y = torch.zeros(self.max_batch, ny, dtype=torch.float64, device=self.device)
-            _lib.check(self.lib.obca_set_certificate_buffers(self._h, ctypes.c_void_p(self.cert_z.data_ptr()),
-                                                             ctypes.c_void_p(self.cert_y.data_ptr())))
+            _lib.check(self.lib.obca_set_certificate_buffers(self._h, _lib.ptr(self.cert_z), _lib.ptr(self.cert_y)))
         else:
             _lib.check(self.lib.obca_set_certificate_buffers(self._h, None, None))
             self.cert_z = self.cert_y = None
@@ -192,12 +191,11 @@ class BatchSolver:
             out.iters = torch.empty(B, dtype=torch.int32, device=self.device)
             out.info = torch.empty(B, 4, dtype=torch.float64, device=self.device) if want_info else None
         cp = params.to_c() if isinstance(params, SolverParams) else params
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
+        ptr = _lib.ptr
         _lib.check(self.lib.obca_solve_batch(self._h, ptr(variant), B, ptr(x0), ptr(u0), ptr(xref), ptr(A), ptr(b),
                                              ptr(Ts), ptr(term), ctypes.byref(cp), ptr(out.xopt), ptr(out.uopt),
                                              ptr(out.ts_opt), ptr(out.status), ptr(out.iters), ptr(out.info),
-                                             ctypes.c_void_p(stream)))
+                                             _lib.stream_ptr(self.device)))
         self._keep = (variant, x0, u0, xref, A, b, Ts, term)     # alive until the stream has consumed them
         return out
 
@@ -226,11 +224,10 @@ def moving_rows(static_A, static_b, boxes, Ts, N, half_window=0.0, margin=0.0, d
     M = Ms + 4 * n_box
     A = torch.empty(B, int(N) + 1, M, 2, dtype=torch.float64, device=dev)
     b = torch.empty(B, int(N) + 1, M, dtype=torch.float64, device=dev)
-    ptr = lambda x: ctypes.c_void_p(x.data_ptr()) if x.numel() else None
+    ptr = _lib.ptr
     _lib.check(lib.obca_moving_rows_batch(B, int(N), Ms, n_box, ptr(static_A), ptr(static_b), ptr(boxes), ptr(Ts),
-                                          float(half_window), float(margin), ptr(A), ptr(b),
-                                          dev.index if dev.index is not None else torch.cuda.current_device(),
-                                          ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+                                          float(half_window), float(margin), ptr(A), ptr(b), _lib.device_index(dev),
+                                          _lib.stream_ptr(dev)))
     return A, b
 
 
