@@ -549,8 +549,48 @@ int obca_plan_refine(int32_t B, int32_t N, int32_t ratio, const double* x, const
                      double* xref_out /* [B,3,ratio N+1] */, double* ts_out /* [B] */,
                      int32_t* variant_out /* [B] or NULL */, int32_t device, void* hip_stream);
 
+/* ------------------------------------------------------------------------------------------------------
+ * From a route to the reference of a fixed-horizon solve (obca_mpc 0.13), on the device: the two steps around
+ * obca_astar_batch that make the open-loop planner hierarchical -- map, dilated map, route, reference.
+ *
+ * Disk dilation of B occupancy grids (the reference's mapModel.dilate_map, src/model_map.py:103-107).  DEVICE pointers
+ * grid and out, [B,rows,cols] uint8:
+ *   out[b,r,c] = 1 iff some cell (r + dy, c + dx) inside the grid with dy^2 + dx^2 <= level^2 is non-zero in grid[b], else 0.
+ * Cells outside the grid count as free; any non-zero input byte counts as occupied; level 0 copies (a non-zero byte becomes
+ * 1).  The output is what obca_astar_batch takes.  B, rows, cols >= 1, rows*cols <= 65535 (obca_astar_batch's bound),
+ * 0 <= level <= 16 (a lane reads at most (2 level + 1)^2 = 1089 bytes; a car of the reference is under 4 cells long),
+ * grid and out not NULL and not overlapping (grid == out included).  Every argument is checked before the first HIP call;
+ * a refused call (OBCA_E_INVAL) has no side effect.  Asynchronous on hip_stream. */
+int obca_grid_dilate_batch(const uint8_t* grid, int32_t B, int32_t rows, int32_t cols, int32_t level, uint8_t* out,
+                           int32_t device, void* hip_stream);
+
+/* Routes resampled to N + 1 knots equally spaced in arc length.  DEVICE pointers: path [B,3,path_max] and path_len [B] as
+ * obca_astar_batch writes them (negative codes included; the yaw row is read only for the fill below), start [B,3] and
+ * goal [B,3] poses to pin the ends to (either may be NULL); outputs xref_out [B,3,N+1] (obca_solve_batch's xref) and
+ * ok_out [B].  For an instance with L = path_len >= 2 points p_i, every operation rounded on its own (no FMA):
+ *   d_i = sqrt(dx_i dx_i + dy_i dy_i), i = 0 .. L-2;  S_0 = 0, S_i+1 = S_i + d_i in index order;  S = S_L-1
+ *   knot k < N  s_k = ((double)k S) / (double)N; its segment is the first i with d_i > 0 and S_i+1 >= s_k;
+ *               t = (s_k - S_i) / d_i;  p = p_i + t (p_i+1 - p_i) per coordinate
+ *   knot N      the last route point itself
+ *   pins        the position of knot 0 becomes start[0..1], that of knot N goal[0..1], where given
+ *   yaw_k       atan2(y_k+1 - y_k, x_k+1 - x_k) on these final positions for k < N, yaw_N = yaw_N-1 (the rule of
+ *               create_reference_path, src/a_star.py:189-200); then yaw_0 = start[2], yaw_N = goal[2] where given
+ *   ok_out      1
+ * Not resampled, ok_out = 0: path_len < 2 or > path_max, a point (x, y or yaw) among the first path_len that is not finite
+ * (points beyond path_len are never read), S zero or not finite, a given start or goal pose that is not finite (it is
+ * dropped for that instance).  Such an instance gets, where start and goal are both given and finite, start at knot 0 and
+ * goal at knots 1 .. N, all three components (the start/goal-only reference); otherwise point 0 of its path at every knot,
+ * or zeros where that point is not finite.  No output is ever NaN.
+ * B >= 1, path_max >= 1, 1 <= N <= 127 (the longest horizon of obca_dims); path, path_len, xref_out and ok_out not NULL.
+ * Every argument is checked before the first HIP call; a refused call (OBCA_E_INVAL) has no side effect.  Asynchronous on
+ * hip_stream. */
+int obca_route_resample(int32_t B, int32_t path_max, int32_t N, const double* path, const int32_t* path_len,
+                        const double* start /* [B,3] or NULL */, const double* goal /* [B,3] or NULL */,
+                        double* xref_out /* [B,3,N+1] */, int32_t* ok_out /* [B] */, int32_t device, void* hip_stream);
+
 const char* obca_strerror(int code);
-/* "obca_mpc 0.12 (gfx950)": 0.12 = the refinement step of the two-stage open-loop planner (obca_plan_refine);
+/* "obca_mpc 0.13 (gfx950)": 0.13 = route-seeded open-loop planning (obca_grid_dilate_batch, obca_route_resample);
+ * 0.12 = the refinement step of the two-stage open-loop planner (obca_plan_refine);
  * 0.11 = clearance repair of batched plans (obca_plan_tighten);
  * 0.10 = obca_astar_batch's code -4 (start or goal outside the grid), obca_rasterise_batch clips boxes to the map;
  * 0.9 = swept audit of batched plans (obca_plan_sweep);

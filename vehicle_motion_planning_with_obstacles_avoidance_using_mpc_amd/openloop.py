@@ -2,7 +2,9 @@
 ``closedLoop.mpc_openLoop_freeTime`` then ``mpc_openLoop_fixTime``) for B worlds at once, with no host round trip between
 the stages.
 
-Stage 1 is a free-time ``obca_mpc4`` plan from a start/goal-only reference.  ``refine`` (obca_plan_refine, csrc/obca_refine.hip
+Stage 1 is a free-time ``obca_mpc4`` plan from a start/goal-only reference, or from a route: ``route_references`` dilates
+the occupancy grids, runs the batched A* and resamples each route to the N_free + 1 knots stage 1 tracks (obca_grid_dilate_batch
+and obca_route_resample, csrc/obca_route.hip on csrc/obca_route_core.h), and ``plan(..., xref_free=...)`` takes the result.  ``refine`` (obca_plan_refine, csrc/obca_refine.hip
 on csrc/obca_refine_core.h) resamples it to ``ratio x N_free`` knots, recomputes the yaws and rescales the step -- the
 reference's ``update_path(allAviable=1)``.  Stage 2 is ``obca_mpc6`` against the moving boxes predicted at the new step
 (``solver.moving_rows``) with the setting's terminal set; ``obca_mpc8`` answers where ``obca_mpc6`` fails.  The per-instance
@@ -51,6 +53,69 @@ def refine(x, ts, ratio, status=None, variant_ok=6, device=None):
     return xref, ts_out, variant_out
 
 
+def route_reference(path, path_len, N, start=None, goal=None, device=None):
+    """Routes -> references of a horizon-N solve (obca_route_resample): path [B,3,path_max] and path_len [B] are
+    ``planner.plan_batch``'s outputs, negative codes included; start / goal [B,3] (either may be None) pin the poses of knot 0
+    and knot N.  Returns device tensors (xref [B,3,N+1], ok [B] int32): N + 1 knots equally spaced along the route's arc
+    length with ``create_reference_path``'s yaws and ok = 1 -- or, for an instance without a usable route (path_len < 2, a
+    point not finite, zero length), ok = 0 and the start/goal-only reference where both pins are given, else point 0 of the
+    path at every knot (zeros where it is not finite).  On the current stream, no host synchronisation."""
+    import torch
+    if not torch.cuda.is_available():
+        raise RuntimeError("route_reference needs a ROCm GPU; there is no CPU fallback on the product path")
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    lib = _lib.load()
+    path = torch.as_tensor(path, dtype=torch.float64, device=dev).contiguous()
+    if path.dim() != 3 or path.shape[1] != 3:
+        raise ValueError("expected path [B,3,path_max], got %s" % (tuple(path.shape),))
+    B, P, N = int(path.shape[0]), int(path.shape[2]), int(N)
+    path_len = torch.as_tensor(path_len, dtype=torch.int32, device=dev).contiguous()
+    if tuple(path_len.shape) != (B,):
+        raise ValueError("expected path_len [B], got %s" % (tuple(path_len.shape),))
+    pins = []
+    for name, v in (("start", start), ("goal", goal)):
+        if v is not None:
+            v = torch.as_tensor(v, dtype=torch.float64, device=dev).contiguous()
+            if tuple(v.shape) != (B, 3):
+                raise ValueError("expected %s [B,3], got %s" % (name, tuple(v.shape)))
+        pins.append(v)
+    xref = torch.empty(B, 3, max(N, 0) + 1, dtype=torch.float64, device=dev)
+    ok = torch.empty(B, dtype=torch.int32, device=dev)
+    ptr = _lib.ptr
+    _lib.check(lib.obca_route_resample(B, P, N, ptr(path), ptr(path_len), ptr(pins[0]), ptr(pins[1]), ptr(xref), ptr(ok),
+                                       _lib.device_index(dev), _lib.stream_ptr(dev)))
+    # the launch is asynchronous: the tensors it reads are tied to the result and to the stream (see planner.plan_batch)
+    xref._obca_keep = (path, path_len, pins[0], pins[1])
+    for t in xref._obca_keep:
+        if t is not None:
+            t.record_stream(torch.cuda.current_stream(dev))
+    return xref, ok
+
+
+def route_references(grids, start_cells, goal_cells, N, start=None, goal=None, dilation=0, path_max=None, device=None):
+    """Map -> dilated map -> route -> reference for B worlds on the current stream, no host round trip: grids [B,rows,cols]
+    (non-zero = occupied), start_cells / goal_cells [B,2] as (row, col) -- ``planner.plan_batch``'s arguments --, start /
+    goal [B,3] the poses ``route_reference`` pins.  With dilation > 0 the search runs on ``planner.dilate_batch``'s grid AND on
+    the plain one; an instance takes the dilated route where that search found one (path_len >= 2) and the plain route
+    otherwise, chosen by ``torch.where`` on the device.  Returns (xref [B,3,N+1], ok [B] int32, source [B] int32): 2 = the
+    dilated route, 1 = the plain route, 0 = neither (``route_reference``'s fill)."""
+    import torch
+    from .planner import dilate_batch, plan_batch
+    if not isinstance(grids, torch.Tensor):                  # one upload for both searches
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        grids = torch.as_tensor(np.ascontiguousarray(grids), device=dev)
+    path, plen = plan_batch(grids, start_cells, goal_cells, path_max=path_max, device=device)
+    src = torch.ones_like(plen)
+    if int(dilation) > 0:
+        path_d, plen_d = plan_batch(dilate_batch(grids, dilation, device=device), start_cells, goal_cells, path_max=path_max,
+                                    device=device)
+        use_d = plen_d >= 2
+        path, plen = torch.where(use_d[:, None, None], path_d, path), torch.where(use_d, plen_d, plen)
+        src = torch.where(use_d, 2, 1).to(torch.int32)
+    xref, ok = route_reference(path, plen, N, start, goal, device=device)
+    return xref, ok, torch.where(ok == 1, src, 0).to(torch.int32)
+
+
 class TwoStagePlan:
     """What ``TwoStagePlanner.plan`` returns (device tensors): ``free`` / ``fix`` -- the ``BatchResult`` of stage 1 and of
     stage 2 (``iters`` summed over the obca_mpc6 and the obca_mpc8 launch; status OBCA_STATUS_SKIPPED and zero outputs where
@@ -92,13 +157,16 @@ class TwoStagePlanner:
             if s is not None:
                 s.close()
 
-    def plan(self, start, goal, static_A, static_b, boxes, term, Ts=0.1, u0=None, params=None, half_window=0.0, margin=0.0):
+    def plan(self, start, goal, static_A, static_b, boxes, term, Ts=0.1, u0=None, params=None, half_window=0.0, margin=0.0,
+             xref_free=None):
         """start [B,3], goal [B,3], static_A [B,Ms,2], static_b [B,Ms], boxes [B,n_box,13] (``solver.moving_rows``' tuple),
         term [B,3] (the terminal set as ``BatchSolver.solve`` takes it), Ts: stage 1's nominal step, u0 [B,2] (None: zeros),
         params: ``SolverParams`` for both stages -- stage 1 runs them with start_order "x0" unless another order is set (its
         reference is start and goal only, no trajectory a solve could start from), stage 2's obca_mpc6 with the first start of
         the ladder only, because obca_mpc8 follows a failure.  half_window / margin: ``solver.moving_rows``' swept, inflated
-        boxes for stage 2.  Returns a ``TwoStagePlan``."""
+        boxes for stage 2.  xref_free [B,3,N_free+1] (None: the start/goal-only reference): the reference stage 1 tracks, e.g.
+        ``route_references``'; with it stage 1 keeps the caller's start_order -- there is a trajectory to start from.
+        Returns a ``TwoStagePlan``."""
         import torch
         dev, Nf, N2 = self.device, self.N_free, self.N_fix
         params = params or SolverParams()
@@ -112,12 +180,16 @@ class TwoStagePlanner:
         Ts = t(Ts.expand(B) if Ts.dim() == 0 else Ts, (B,))
 
         # stage 1: obca_mpc4, reference = the start pose, then the goal pose N_free times; the static rows at every stage
-        xref = torch.cat([start[:, :, None], goal[:, :, None].expand(B, 3, Nf)], 2)
+        # (or the caller's reference, under the caller's start order)
         A1 = static_A[:, None].expand(B, Nf + 1, Ms, 2)
         b1 = static_b[:, None].expand(B, Nf + 1, Ms)
         p1 = copy.copy(params)
-        if p1.start_order == _lib.START_DEFAULT:
-            p1.start_order = _lib.START_X0_FIRST
+        if xref_free is None:
+            xref = torch.cat([start[:, :, None], goal[:, :, None].expand(B, 3, Nf)], 2)
+            if p1.start_order == _lib.START_DEFAULT:
+                p1.start_order = _lib.START_X0_FIRST
+        else:
+            xref = t(xref_free, (B, 3, Nf + 1))
         free = self.free_solver.solve(4, start, u0, xref, A1, b1, Ts, None, p1)
 
         # refinement and stage 2's rows, from stage 1's outputs where they lie
@@ -170,3 +242,13 @@ def from_settings(settings):
     a.term = np.array([(v[0, 0], v[1, 0], v[1, 1]) for v in ts])
     a.params = SolverParams(xL=w.xL, xU=w.xU)
     return a
+
+
+def route_arguments(settings):
+    """B ``problemSetting`` objects of one map shape -> (grids [B,rows,cols] uint8, start_cells [B,2], goal_cells [B,2]) for
+    ``route_references``, read from a setting the way ``rollouts.device_reference_paths`` reads them: ``org_gridMap`` and
+    (row, col) = (pose_y, pose_x) of ``startPose`` / ``goalPose``."""
+    settings = list(settings)
+    grids = np.stack([np.asarray(s.org_gridMap) for s in settings]).astype(np.uint8)
+    cells = lambda name: np.array([(getattr(s, name)[1], getattr(s, name)[0]) for s in settings]).astype(np.int32)
+    return grids, cells("startPose"), cells("goalPose")

@@ -79,3 +79,28 @@ def rasterise_batch(obstacle_lists, map_size, resolution=1.0, device=None):
     _lib.check(lib.obca_rasterise_batch(_lib.ptr(bx), B, K, float(resolution), rows, cols, _lib.ptr(grid), _lib.stream_ptr(dev)))
     bx.record_stream(torch.cuda.current_stream(dev))
     return grid
+
+
+def dilate_batch(grids, level, device=None):
+    """Disk dilation of B occupancy grids in one launch (obca_grid_dilate_batch; reference ``mapModel.dilate_map``,
+    src/model_map.py:103-107; host mirror ``model_map.mapModel.dilate_map``).  grids [B,rows,cols] (non-zero = occupied; a
+    device tensor, e.g. ``rasterise_batch``'s, stays on the device), 0 <= level <= 16.  Returns a device tensor
+    [B,rows,cols] uint8 of 0 / 1, which ``plan_batch`` takes."""
+    import torch
+    if not torch.cuda.is_available():
+        raise RuntimeError("dilate_batch needs a ROCm GPU; there is no CPU fallback on the product path")
+    lib = _lib.load()
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    if isinstance(grids, torch.Tensor):
+        g = grids.to(device=dev, dtype=torch.uint8).contiguous()
+    else:
+        g = torch.as_tensor(np.ascontiguousarray(grids), device=dev).to(torch.uint8).contiguous()
+    if g.dim() != 3:
+        raise ValueError("expected grids [B,rows,cols], got %s" % (tuple(g.shape),))
+    B, rows, cols = g.shape
+    out = torch.empty(B, rows, cols, dtype=torch.uint8, device=dev)
+    _lib.check(lib.obca_grid_dilate_batch(_lib.ptr(g), B, rows, cols, int(level), _lib.ptr(out), _lib.device_index(dev),
+                                          _lib.stream_ptr(dev)))
+    out._obca_keep = (g,)                                    # the launch is asynchronous: see plan_batch
+    g.record_stream(torch.cuda.current_stream(dev))
+    return out
