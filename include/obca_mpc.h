@@ -228,8 +228,10 @@ int obca_set_certificate_buffers(obca_handle* h, double* z, double* y);
  * there: the stage-serial sweep dominates and four times as many instances are in flight), shapes with more obstacles four
  * wavefronts per instance while the working set still fits the LDS (<= 1280 rows, e.g. N = 20 with five obstacles); else four
  * wavefronts per instance with the row state and every O(rows) array in the HBM workspace and only the O(N) blocks of the
- * stage-serial Riccati sweep in LDS (long horizons: N = 74 with five obstacles has 3976 rows); else (N > ~150) the
- * lane-per-instance kernel.  The choice is a function of the shape only.
+ * stage-serial Riccati sweep in LDS (long horizons: N = 74 with five obstacles has 3976 rows; every shape obca_create accepts,
+ * N <= 127, fits there); the lane-per-instance kernel only where the runtime refuses those kernels their LDS.  The choice is a
+ * function of the shape and the mode, never of the batch size -- and, once the handle's HBM workspace could not be allocated,
+ * of that fact: auto mode then stays with the LDS-resident kernels where they hold the shape (csrc/obca_select.h: plan).
  * 1 = one wavefront per instance; 2 = lane-per-instance (64 instances per wavefront, working set in an HBM workspace
  * owned by the handle; any shape); 3 = four wavefronts per instance, LDS resident; 4 = four wavefronts per instance, HBM
  * workspace; 5 = one wavefront per instance, HBM workspace.  Returns OBCA_E_LDS if mode 1 / 3 / 4 / 5 cannot hold the shape. */
@@ -259,9 +261,12 @@ int obca_set_two_sided_sweep(obca_handle* h, int on);
  * Only builds compiled with -DOBCA_PROFILE write to it; NULL (the default) disables it. */
 void obca_set_profile_buffer(obca_handle* h, double* prof);
 
-/* bytes of LDS one instance needs in the wave-per-instance kernels (> 163840: only the lane kernel runs it); the
+/* bytes of LDS one instance needs in the wave-per-instance kernels (> 163840: they cannot run it); the
  * four-wavefront kernels ask for 8 * (36 * ((N + 1) / 2) + 42) bytes more (forward half of their two-sided Riccati sweep),
- * beyond 768 rows another 8 * (15 * (max(rows - 1024, 0) + 1) + 1025) (fifth row slot and row values, csrc/obca_device.h) */
+ * beyond 768 rows another 8 * (15 * (max(rows - 1024, 0) + 1) + 1025) (fifth row slot and row values, csrc/obca_device.h).
+ * A launch additionally asks for the scratch of the second-order correction (8 * even(variables + 2 rows + 2 (N + 1) n_obs)
+ * bytes) where that lives in LDS: where it costs the one-wavefront kernels no occupancy, and where the four-wavefront
+ * kernels' total stays within one CU's 160 KiB (csrc/obca_device.h: obca_soc_lds_wave / _mw). */
 int64_t obca_lds_bytes(const obca_dims* dims);
 
 /* ------------------------------------------------------------------------------------------------------

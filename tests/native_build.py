@@ -10,7 +10,7 @@ ROOT = os.path.dirname(HERE)
 SRC = os.path.join(HERE, "native", "rollout_host.cpp")
 CSRC = os.path.join(ROOT, "vehicle_motion_planning_with_obstacles_avoidance_using_mpc_amd", "csrc")
 DEPS = [SRC, os.path.join(HERE, "native", "lpi_host.cpp"), os.path.join(CSRC, "obca_lpi_core.h"),
-        os.path.join(CSRC, "obca_rollout_core.h"), os.path.join(CSRC, "obca_astar_core.h"), os.path.join(CSRC, "obca_device.h"),
+        os.path.join(CSRC, "obca_rollout_core.h"), os.path.join(CSRC, "obca_astar_core.h"), os.path.join(CSRC, "obca_device.h"), os.path.join(CSRC, "obca_select.h"),
         os.path.join(ROOT, "include", "obca_mpc.h")]
 
 _lib = None

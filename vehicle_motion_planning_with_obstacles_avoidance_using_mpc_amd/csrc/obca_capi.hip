@@ -8,6 +8,7 @@
 #include <stdlib.h>
 #include "obca_device.h"
 #include "obca_lpi_core.h"
+#include "obca_select.h"
 
 extern "C" __global__ void obca_ipm_kernel_r4(ObcaLaunch A, ObcaLaunch A2, ObcaLaunch A3);
 extern "C" __global__ void obca_ipm_kernel_r5(ObcaLaunch A, ObcaLaunch A2, ObcaLaunch A3);
@@ -24,26 +25,18 @@ OBCA_MW_SHAPES(OBCA_DECLARE_MW_SHAPE_KERNEL)
 typedef void (*obca_wave_kernel_t)(ObcaLaunch, ObcaLaunch, ObcaLaunch);
 extern "C" __global__ void obca_lpi_kernel(ObcaLaunch A, double* ws, unsigned long long stride, const int* offm, int ipw);
 
+namespace sel = obca_select;
+
 struct obca_handle {
     obca_dims dims;
-    int32_t M, n_max, R_max, inst_off;
+    int32_t M;
     int32_t offm[OBCA_MAX_OBST + 1];
-    int two_sided;                     // -1: where only the four-wavefront kernels fit (default), 0: never, 1: always
-    int64_t lds_pad;          // dev knob OBCA_LDS_PAD: bytes added to the one-wavefront kernels' LDS request (occupancy experiments)
-    int64_t lds_bytes, lds_bytes_mw;   // one-wavefront kernels; four-wavefront kernels (+ the two-sided sweep's storage) -- both incl. the SOC scratch where it lives in LDS
-    int32_t soc_lds, soc_lds_mw;       // its offset there (doubles), 0 = in HBM (csrc/obca_device.h: obca_soc_lds_wave / _mw)
-    int64_t lds_bytes_gm, gm_doubles;  // obca_ipm_kernel_gm: its LDS (O(N) blocks only) and its HBM workspace per workgroup
-    int32_t inst_off_gm;
-    bool gm_ok;
-    double* gm_ws;                     // allocated on first use: max_batch slices
-    bool gm_ws_failed;                 // ... and that allocation failed once: auto mode stops choosing the workspace kernels for this handle
+    sel::Caps cap;            /* what the shape alone decides: sizes, LDS requests, which kernel families hold it */
+    sel::Knobs knobs;         /* mode, specialise, two_sided, lds_pad (dev knob OBCA_LDS_PAD: occupancy experiments), gm_ws_failed */
+    unsigned refused;         /* sel::Refused: families whose LDS request the runtime refused */
+    obca_wave_kernel_t kernel[sel::K_COUNT];   /* id -> function; K_WAVE_SHAPE / K_MW_SHAPE: the instantiation for exactly this shape, or nullptr */
+    double* gm_ws;            /* HBM workspace of the gm kernels, allocated on first use: max_batch slices of cap.gm_doubles */
     double* prof;
-    int mode;                 /* 0 auto, 1 wave-per-instance (LDS), 2 lane-per-instance (HBM workspace), 3 four waves per instance */
-    obca_wave_kernel_t shape_kernel;   /* instantiation of the one-wavefront kernel for exactly this shape, or nullptr */
-    obca_wave_kernel_t shape_kernel_mw; /* likewise of the four-wavefront LDS kernel */
-    bool specialise;          /* use it (default; OBCA_SPECIALISE=0 / obca_set_shape_specialisation(h, 0): the generic kernels) */
-    bool wave_ok;             /* the one-wavefront LDS kernel can hold this shape */
-    bool mw_ok;               /* the four-wavefront LDS kernel can hold this shape */
     double* warm_z;           /* obca_set_warm_start */
     const int32_t* warm_use;
     double warm_mu;
@@ -57,8 +50,6 @@ struct obca_handle {
 
 namespace {
 
-constexpr int MW = OBCA_MAX_EDGES + 6;
-
 bool dims_ok(const obca_dims* d) {
     if (!d) return false;
     if (d->N < 1 || d->N > 127) return false;     // the wave kernel only ever sees N < 64 (rows / LDS), the lane kernel any
@@ -68,66 +59,17 @@ bool dims_ok(const obca_dims* d) {
     return true;
 }
 
-// Auto mode, shapes beyond the one-wavefront LDS kernel (> 384 rows): ONE wavefront per instance with the row state in the HBM
-// workspace (obca_ipm_kernel_gm1) where an instance has at most three obstacles, the four-wavefront LDS kernel otherwise.  Measured
-// (round 5, tools/gpu_gm1_shapes.py, 8192 instances of the C3 generator): three obstacles / 6 rows per stage N = 12 / 16 / 20 / 26:
-// 114.6 / 151.6 / 178.7 / 255.5 ms against 152.9 / 182.8 / 194.0 / 270.7 ms on four wavefronts (with few rows per stage the stage-serial
-// sweep dominates, and four times as many instances in flight hide its latency); five obstacles / 14 rows per stage N = 8 ... 14:
-// 187 ... 276 ms against 131 ... 214 ms (the local blocks of five obstacles keep four wavefronts busy); four obstacles / 10 rows per stage,
-// obca_mpc6 / 8, N = 10 ... 20: 140 ... 302 ms against 107 ... 179 ms; three obstacles with the fixed-time variants gain like the free-time
-// one (tools/gpu_gm1_four.py).  Same words as the
-// four-wavefront kernels with the one-sided sweep.  A function of the SHAPE only -- and only of the MEASURED region (round 6, advisor):
-// horizons up to N = 26 that the four-wavefront LDS kernel could run as well.  Longer horizons and shapes beyond the LDS keep the
-// kernels they had before gm1 existed (four wavefronts: LDS resident where it fits, HBM workspace otherwise) until someone measures
-// them; and a handle whose workspace cannot be allocated falls back to the LDS-resident kernel, which needs none.
-#define OBCA_GM1_MAX_N 26
-bool auto_gm1(const obca_handle* h) { return h->mode == 0 && !h->wave_ok && h->mw_ok && h->gm_ok && h->dims.n_obs <= 3 && h->dims.N <= OBCA_GM1_MAX_N && !h->gm_ws_failed; }
-
-// (the carve-up itself: csrc/obca_device.h: obca_shape_sizes, shared with the kernels)
-int64_t lds_doubles(int N, int nO, int M, int& n_max, int& R_max, int& inst_off) {
-    const ObcaShapeSizes z = obca_shape_sizes(N, nO, M);
-    n_max = z.n_max; R_max = z.R_max; inst_off = z.inst_off;
-    return z.lds_doubles;
-}
-
-// the same for obca_ipm_kernel_gm (GM branch of the carve-up): LDS doubles, offset of the instance block, workspace doubles
-int64_t gm_doubles(int N, int nO, int M, int n_max, int R_max, int& inst_off, int64_t& ws) {
-    const int N1 = N + 1, np = N1 * nO;
-    int64_t t = 0, g = 0;
-    auto take = [&](int64_t c) { t += (c + 1) & ~int64_t(1); };
-    auto takeG = [&](int64_t c) { g += (c + 1) & ~int64_t(1); };
-    takeG(n_max); takeG(n_max > 120 ? n_max : 120); take(5 * N1 + 1); takeG(n_max);
-    for (int i = 0; i < 5; ++i) takeG(R_max);
-    take(3 * N1 + 3);
-    take(N1); take(N1); takeG(2 * np); take(N1); take(N1); takeG(2 * np);
-    takeG(2 * np); takeG(2 * np); takeG(2 * np);
-    takeG(N1 * M * 2); takeG(N1 * M); take(3 * N1);
-    take(36 * N1); take(8 * N1);
-    {
-        const int64_t nx = (n_max + 1) & ~1, nr = (R_max + 1) & ~1, ny = (int64_t)MW * 4 * np;
-        takeG(ny > nx + nr ? ny : nx + nr);
-    }
-    take(36 * N1); takeG(12 * np);
-    take(6 * N1); take(12 * N1); take(2 * N1); take(9 * (N1 + 1));
-    take(120);               // FG / Mall / mall
-    take(32); take(8);
-    take(3 * N1 + 3); take(3 * N1 + 3); take(2 * N1 + 2);      // mirrors of the soft rows' E^-1, ghat; inputs + time scale
-    const int64_t rs = (int64_t)((R_max + 255) / 256) * 256;
-    for (int i = 0; i < 15; ++i) takeG(rs);                    // row state (OBCA_ROW_FIELDS)
-    inst_off = (int)t;
-    take(OBCA_INST_DOUBLES);
-    ws = g;
-    return t;
+int rows_per_stage(const obca_dims* d) {          // M: half-space rows of all obstacles
+    int M = 0;
+    for (int i = 0; i < d->n_obs; ++i) M += d->m[i];
+    return M;
 }
 
 }  // namespace
 
 extern "C" int64_t obca_lds_bytes(const obca_dims* d) {
     if (!dims_ok(d)) return -1;
-    int M = 0;
-    for (int i = 0; i < d->n_obs; ++i) M += d->m[i];
-    int n_max, R_max, io;
-    return 8 * lds_doubles(d->N, d->n_obs, M, n_max, R_max, io);
+    return 8 * obca_shape_sizes(d->N, d->n_obs, rows_per_stage(d)).lds_doubles;
 }
 
 extern "C" int obca_create(const obca_dims* d, obca_handle** out) {
@@ -137,82 +79,59 @@ extern "C" int obca_create(const obca_dims* d, obca_handle** out) {
     obca_handle* h = new (std::nothrow) obca_handle;
     if (!h) return OBCA_E_NOMEM;
     h->dims = *d;
-    h->M = 0;
+    h->M = rows_per_stage(d);
     h->offm[0] = 0;
-    for (int i = 0; i < OBCA_MAX_OBST; ++i) {
-        if (i < d->n_obs) h->M += d->m[i];
-        h->offm[i + 1] = h->M;
-    }
-    h->lds_bytes = 8 * lds_doubles(d->N, d->n_obs, h->M, h->n_max, h->R_max, h->inst_off);
-    h->lds_bytes_mw = h->lds_bytes + 8 * (OBCA_ZK_DOUBLES(d->N) + OBCA_HYB_DOUBLES(h->R_max));
-    h->wave_ok = !(h->lds_bytes + OBCA_LDS_STATIC_BYTES > OBCA_LDS_CU_BYTES || h->R_max > 384);     // rows live in registers: <= 6 per lane
-    h->mw_ok = !(h->lds_bytes_mw + OBCA_LDS_STATIC_BYTES > OBCA_LDS_CU_BYTES || h->R_max > 1280);   // 256 threads x 3 or 5 rows; up to 64 B of static LDS
-    // the second-order correction's scratch joins the LDS request where that costs no occupancy (csrc/obca_device.h)
-    h->soc_lds = h->wave_ok ? obca_soc_lds_wave(d->N, d->n_obs, h->M) : 0;
-    h->soc_lds_mw = h->mw_ok ? obca_soc_lds_mw(d->N, d->n_obs, h->M) : 0;
-    if (h->soc_lds) h->lds_bytes += 8 * obca_soc_doubles(d->N, d->n_obs, h->M);
-    if (h->soc_lds_mw) h->lds_bytes_mw += 8 * obca_soc_doubles(d->N, d->n_obs, h->M);
-    h->lds_bytes_gm = 8 * (gm_doubles(d->N, d->n_obs, h->M, h->n_max, h->R_max, h->inst_off_gm, h->gm_doubles) + OBCA_ZK_DOUBLES(d->N));
-    h->gm_ok = h->lds_bytes_gm + OBCA_LDS_STATIC_BYTES <= OBCA_LDS_CU_BYTES;
-    h->gm_ws = nullptr; h->gm_ws_failed = false;
+    for (int i = 0; i < OBCA_MAX_OBST; ++i) h->offm[i + 1] = h->offm[i] + (i < d->n_obs ? d->m[i] : 0);
+    h->cap = sel::caps(d->N, d->n_obs, h->M);
+    h->gm_ws = nullptr;
     ObcaDeviceGuard guard(d->device);
     if (!guard.ok) { delete h; return OBCA_E_HIP; }
-    // a kernel whose LDS request the runtime refuses is simply not offered (the lane kernel serves every shape)
-    if (h->gm_ok && h->lds_bytes_gm > 64 * 1024 &&
-        (hipFuncSetAttribute(reinterpret_cast<const void*>(obca_ipm_kernel_gm), hipFuncAttributeMaxDynamicSharedMemorySize,
-                             (int)h->lds_bytes_gm) != hipSuccess ||
-         hipFuncSetAttribute(reinterpret_cast<const void*>(obca_ipm_kernel_gm1), hipFuncAttributeMaxDynamicSharedMemorySize,
-                             (int)h->lds_bytes_gm) != hipSuccess)) {
-        (void)hipGetLastError();
-        h->gm_ok = false;
-    }
-    if (h->mw_ok && h->lds_bytes_mw > 64 * 1024 &&
-        hipFuncSetAttribute(h->R_max <= 768 ? reinterpret_cast<const void*>(obca_ipm_kernel_mw_r3)
-                                            : reinterpret_cast<const void*>(obca_ipm_kernel_mw_r5),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes_mw) != hipSuccess) {
-        (void)hipGetLastError();
-        h->mw_ok = false;
-    }
-    if (h->wave_ok && h->lds_bytes > 64 * 1024) {
-        const void* fn = h->R_max <= 256   ? reinterpret_cast<const void*>(obca_ipm_kernel_r4)
-                         : h->R_max <= 320 ? reinterpret_cast<const void*>(obca_ipm_kernel_r5)
-                                           : reinterpret_cast<const void*>(obca_ipm_kernel_r6);
-        if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes) != hipSuccess) {
+    for (int k = 0; k < sel::K_COUNT; ++k) h->kernel[k] = nullptr;          // (K_LANE stays empty: other arguments, its own launch)
+    h->kernel[sel::K_WAVE_R4] = obca_ipm_kernel_r4; h->kernel[sel::K_WAVE_R5] = obca_ipm_kernel_r5; h->kernel[sel::K_WAVE_R6] = obca_ipm_kernel_r6;
+    h->kernel[sel::K_MW_R3] = obca_ipm_kernel_mw_r3; h->kernel[sel::K_MW_R5] = obca_ipm_kernel_mw_r5;
+    h->kernel[sel::K_GM] = obca_ipm_kernel_gm; h->kernel[sel::K_GM1] = obca_ipm_kernel_gm1;
+#define OBCA_MATCH_MW_SHAPE_KERNEL(N_, O_, M_) if (d->N == N_ && d->n_obs == O_ && h->M == M_) h->kernel[sel::K_MW_SHAPE] = obca_ipm_kernel_mw_s##N_##_##O_##_##M_;
+    OBCA_MW_SHAPES(OBCA_MATCH_MW_SHAPE_KERNEL)
+#define OBCA_MATCH_SHAPE_KERNEL(N_, O_, M_) if (d->N == N_ && d->n_obs == O_ && h->M == M_) h->kernel[sel::K_WAVE_SHAPE] = obca_ipm_kernel_s##N_##_##O_##_##M_;
+    OBCA_SHAPES(OBCA_MATCH_SHAPE_KERNEL)
+    // every kernel this shape can be planned onto may ask for its LDS; one whose request the runtime refuses is simply not
+    // offered (the lane kernel serves every shape) -- of the four-wavefront family, a refused instantiation alone is dropped.
+    // (The one-wavefront instantiations are in the loop on purpose: every listed one stays below 64 KiB today, so none asks; one
+    // that did and was refused would take the family with it, as the generic kernel of the same LDS request would.)
+    h->refused = 0;
+    for (int k = 0; k < sel::K_COUNT; ++k) {
+        const int64_t lds = sel::kernel_lds(h->cap, (sel::Kernel)k);
+        const unsigned family = sel::refusal_of((sel::Kernel)k);
+        if (!h->kernel[k] || lds <= 64 * 1024 || (h->refused & (family | (k == sel::K_MW_SHAPE ? sel::REFUSED_MW : 0u)))) continue;
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(h->kernel[k]), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
             (void)hipGetLastError();
-            h->wave_ok = false;
+            h->refused |= family;
         }
     }
-    h->mode = 0;
-    h->shape_kernel = nullptr;
-    h->shape_kernel_mw = nullptr;
-    h->specialise = true;
-#define OBCA_MATCH_MW_SHAPE_KERNEL(N_, O_, M_) if (d->N == N_ && d->n_obs == O_ && h->M == M_) h->shape_kernel_mw = obca_ipm_kernel_mw_s##N_##_##O_##_##M_;
-    OBCA_MW_SHAPES(OBCA_MATCH_MW_SHAPE_KERNEL)
-    if (h->shape_kernel_mw && h->mw_ok && h->lds_bytes_mw > 64 * 1024 &&
-        hipFuncSetAttribute(reinterpret_cast<const void*>(h->shape_kernel_mw), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes_mw) != hipSuccess) {
-        (void)hipGetLastError();
-        h->shape_kernel_mw = nullptr;
-    }
-#define OBCA_MATCH_SHAPE_KERNEL(N_, O_, M_) if (d->N == N_ && d->n_obs == O_ && h->M == M_) h->shape_kernel = obca_ipm_kernel_s##N_##_##O_##_##M_;
-    OBCA_SHAPES(OBCA_MATCH_SHAPE_KERNEL)
-    if (const char* e = getenv("OBCA_SPECIALISE")) h->specialise = atoi(e) != 0;
-    h->lds_pad = 0;
-    if (const char* e = getenv("OBCA_LDS_PAD")) { const long v = atol(e); if (v > 0 && h->lds_bytes + v <= 64 * 1024) h->lds_pad = v; }
-    h->two_sided = -1;
-    if (const char* e = getenv("OBCA_TWO_SIDED")) { const int v = atoi(e); if (v >= -1 && v <= 1) h->two_sided = v; }
+    sel::Knobs& kn = h->knobs;
+    kn.mode = 0;
+    kn.has_wave_shape = h->kernel[sel::K_WAVE_SHAPE] != nullptr;
+    kn.has_mw_shape = h->kernel[sel::K_MW_SHAPE] != nullptr;
+    kn.gm_ws_failed = false;
+    kn.specialise = true;
+    if (const char* e = getenv("OBCA_SPECIALISE")) kn.specialise = atoi(e) != 0;
+    kn.lds_pad = 0;
+    if (const char* e = getenv("OBCA_LDS_PAD")) { const long v = atol(e); if (v > 0 && h->cap.lds_bytes + v <= 64 * 1024) kn.lds_pad = v; }
+    kn.two_sided = -1;
+    if (const char* e = getenv("OBCA_TWO_SIDED")) { const int v = atoi(e); if (v >= -1 && v <= 1) kn.two_sided = v; }
     if (const char* e = getenv("OBCA_MODE")) {
         const int m = atoi(e);                                     // out of range or not available for this shape: auto
-        if (m >= 0 && m <= 5 && !(m == 1 && !h->wave_ok) && !(m == 3 && !h->mw_ok) && !((m == 4 || m == 5) && !h->gm_ok)) h->mode = m;
+        if (sel::mode_available(h->cap, h->refused, m)) kn.mode = m;
     }
     h->ws = nullptr; h->d_offm = nullptr;
     h->ws_stride = ((size_t)d->max_batch + 63) / 64 * 64;
-    h->ws_doubles = lpi::carve(d->N, d->n_obs, h->M, h->n_max, h->R_max).total;
+    h->ws_doubles = lpi::carve(d->N, d->n_obs, h->M, h->cap.n_max, h->cap.R_max).total;
     h->prof = nullptr;
     h->warm_z = nullptr; h->warm_use = nullptr; h->warm_mu = 0.0;
     h->cert_z = nullptr; h->cert_y = nullptr;
     h->soc_ws = nullptr;
-    if (h->wave_ok || h->mw_ok || h->gm_ok) {
-        const size_t stride = (size_t)h->n_max + 2 * (size_t)h->R_max + 2 * (size_t)(d->N + 1) * d->n_obs;
+    if (sel::wave_offered(h->cap, h->refused) || sel::mw_offered(h->cap, h->refused) || sel::gm_offered(h->cap, h->refused)) {
+        const size_t stride = (size_t)h->cap.n_max + 2 * (size_t)h->cap.R_max + 2 * (size_t)(d->N + 1) * d->n_obs;
         if (hipMalloc(&h->soc_ws, sizeof(double) * stride * (size_t)d->max_batch) != hipSuccess) { h->soc_ws = nullptr; delete h; return OBCA_E_NOMEM; }
     }
     *out = h;
@@ -231,18 +150,14 @@ extern "C" void obca_destroy(obca_handle* h) {
 
 extern "C" int obca_set_mode(obca_handle* h, int mode) {
     if (!h || mode < 0 || mode > 5) return OBCA_E_INVAL;
-    if ((mode == 4 || mode == 5) && !h->gm_ok) return OBCA_E_LDS;
-    if (mode == 1 && !h->wave_ok) return OBCA_E_LDS;
-    if (mode == 3 && !h->mw_ok) return OBCA_E_LDS;
-    h->mode = mode;
+    if (!sel::mode_available(h->cap, h->refused, mode)) return OBCA_E_LDS;
+    h->knobs.mode = mode;
     return OBCA_OK;
 }
 
 extern "C" int64_t obca_primal_size(const obca_dims* d) {
     if (!dims_ok(d)) return -1;
-    int M = 0;
-    for (int i = 0; i < d->n_obs; ++i) M += d->m[i];
-    return (int64_t)(d->N + 1) * (3 + M + 4 * d->n_obs) + 2 * d->N + 1;
+    return (int64_t)(d->N + 1) * (3 + rows_per_stage(d) + 4 * d->n_obs) + 2 * d->N + 1;
 }
 
 extern "C" int obca_set_warm_start(obca_handle* h, double* z, const int32_t* use, double mu_init) {
@@ -253,11 +168,7 @@ extern "C" int obca_set_warm_start(obca_handle* h, double* z, const int32_t* use
 
 extern "C" int64_t obca_dual_size(const obca_dims* d) {
     if (!dims_ok(d)) return -1;
-    int M = 0;
-    for (int i = 0; i < d->n_obs; ++i) M += d->m[i];
-    int n_max, R_max, io;
-    (void)lds_doubles(d->N, d->n_obs, M, n_max, R_max, io);
-    return (int64_t)R_max + 2 * (int64_t)(d->N + 1) * d->n_obs;
+    return (int64_t)obca_shape_sizes(d->N, d->n_obs, rows_per_stage(d)).R_max + 2 * (int64_t)(d->N + 1) * d->n_obs;
 }
 
 extern "C" int obca_set_certificate_buffers(obca_handle* h, double* z, double* y) {
@@ -268,20 +179,18 @@ extern "C" int obca_set_certificate_buffers(obca_handle* h, double* z, double* y
 
 extern "C" int obca_set_shape_specialisation(obca_handle* h, int on) {
     if (!h || on < 0 || on > 1) return OBCA_E_INVAL;
-    h->specialise = on != 0;
+    h->knobs.specialise = on != 0;
     return OBCA_OK;
 }
 
 extern "C" int obca_shape_is_specialised(const obca_handle* h) {
     if (!h) return OBCA_E_INVAL;
-    if (!h->specialise || h->mode == 2 || h->mode == 4 || h->mode == 5 || auto_gm1(h)) return 0;
-    const bool mw = h->mode == 3 || (h->mode == 0 && !h->wave_ok && h->mw_ok);
-    return mw ? (h->shape_kernel_mw ? 1 : 0) : (h->wave_ok && h->shape_kernel ? 1 : 0);
+    return sel::plan(h->cap, h->knobs, h->refused).specialised ? 1 : 0;
 }
 
 extern "C" int obca_set_two_sided_sweep(obca_handle* h, int on) {
     if (!h || on < -1 || on > 1) return OBCA_E_INVAL;
-    h->two_sided = on;
+    h->knobs.two_sided = on;
     return OBCA_OK;
 }
 
@@ -300,14 +209,14 @@ int obca_internal_fill_launch(obca_handle* h, const int32_t* variant, int32_t B,
     if (p->struct_size != (uint32_t)sizeof(obca_params)) return OBCA_E_INVAL;      // another layout, or never initialised (obca_params_init)
     ObcaLaunch& L = *out;
     memset(&L, 0, sizeof(L));
-    L.B = B; L.N = h->dims.N; L.nO = h->dims.n_obs; L.M = h->M; L.n_max = h->n_max; L.R_max = h->R_max; L.inst_off = h->inst_off;
-    L.two_sided = h->two_sided < 0 ? (h->wave_ok ? 0 : 1) : h->two_sided;
+    L.B = B; L.N = h->dims.N; L.nO = h->dims.n_obs; L.M = h->M; L.n_max = h->cap.n_max; L.R_max = h->cap.R_max; L.inst_off = h->cap.inst_off;
+    L.two_sided = sel::sweep_word(h->cap, h->knobs, h->refused);
     for (int i = 0; i <= OBCA_MAX_OBST; ++i) L.offm[i] = h->offm[i];
     L.variant = variant; L.x0 = x0; L.u0 = u0; L.xref = xref; L.A = A; L.b = b; L.Ts = Ts; L.term = term;
     L.xopt = xopt; L.uopt = uopt; L.ts_opt = ts_opt; L.status = status; L.iters = iters; L.info = info; L.prof = h->prof;
     L.warm_z = h->warm_z; L.warm_use = h->warm_use; L.warm_mu = h->warm_mu;
     L.cert_z = h->cert_z; L.cert_y = h->cert_y;
-    L.soc_ws = h->soc_ws; L.soc_lds = h->soc_lds;
+    L.soc_ws = h->soc_ws; L.soc_lds = h->cap.soc_lds;
     auto cpw = [](ObcaWeightsDev& d, const obca_weights& s) {
         // the reference's double loops use Q[i,j] for every (i,j): only the symmetric part matters
         for (int a = 0; a < 3; ++a)
@@ -335,8 +244,8 @@ int obca_internal_fill_launch(obca_handle* h, const int32_t* variant, int32_t B,
     L.prm.opt.max_iter_fixed = p->max_iter_fixed > 0 ? p->max_iter_fixed : 1000;
     L.prm.opt.max_soc = p->max_soc == 0 ? OBCA_MAX_SOC : (p->max_soc < 0 ? 0 : p->max_soc);
     if (!obca_resolve_starts(&L.prm.opt, p->start_order, p->single_start, p->patience, p->retry_iter, h->dims.N, p->dodge, p->terminal_screen)) return OBCA_E_INVAL;
-    if (lds_bytes) *lds_bytes = h->lds_bytes;
-    if (wave_ok) *wave_ok = h->wave_ok ? 1 : 0;
+    if (lds_bytes) *lds_bytes = h->cap.lds_bytes;
+    if (wave_ok) *wave_ok = sel::wave_offered(h->cap, h->refused) ? 1 : 0;
     return OBCA_OK;
 }
 
@@ -353,57 +262,29 @@ extern "C" int obca_solve_batch(obca_handle* h, const int32_t* variant, int32_t 
     if (B == 0) return OBCA_OK;
     ObcaDeviceGuard guard(h->dims.device);
     if (!guard.ok) return OBCA_E_HIP;
-    // wave kernel (working set in LDS) whenever the shape fits one CU; the lane kernel (working set in an HBM
-    // workspace, one instance per lane) takes the shapes beyond the LDS -- measured on MI355X it is latency bound
-    // (every access is an L2/HBM round trip at one wave per SIMD) and 4-10x slower where both run
-    if (h->mode == 1 && !h->wave_ok) return OBCA_E_LDS;
-    if (h->mode == 3 && !h->mw_ok) return OBCA_E_LDS;
-    if (h->mode == 4 || h->mode == 5 || auto_gm1(h) || (h->mode == 0 && !h->wave_ok && !h->mw_ok && h->gm_ok)) {
-        // shapes beyond the LDS: four wavefronts per instance, rows and O(rows) arrays in the handle's HBM workspace
-        if (!h->gm_ok) return OBCA_E_LDS;
-        // (OBCA_FAIL_WORKSPACE_ALLOC in the environment: the allocation is treated as failed -- the only way to exercise the branch below
-        // on a 288 GB device; tests/test_gpu_edge_cases.py)
-        if (!h->gm_ws && (getenv("OBCA_FAIL_WORKSPACE_ALLOC") != nullptr ||
-                          hipMalloc(&h->gm_ws, sizeof(double) * (size_t)h->gm_doubles * (size_t)h->dims.max_batch) != hipSuccess)) {
-            (void)hipGetLastError();
-            h->gm_ws = nullptr;
-            // auto mode with an LDS-resident alternative: run that instead of failing the call (it needs no workspace); an explicit
-            // mode 4 / 5 and shapes only the workspace kernels hold report the failure
-            if (!(h->mode == 0 && h->mw_ok)) return OBCA_E_NOMEM;
-            h->gm_ws_failed = true;
-            return obca_solve_batch(h, variant, B, x0, u0, xref, A, b, Ts, term, p, xopt, uopt, ts_opt, status, iters, info, hip_stream);
-        }
-        L.inst_off = h->inst_off_gm; L.soc_lds = 0;
-        L.gm_ws = h->gm_ws; L.gm_stride = h->gm_doubles;
-        ObcaLaunch L2 = L;
-        if (h->mode == 5 || auto_gm1(h)) { L.two_sided = 0; L2.two_sided = 0; hipLaunchKernelGGL(obca_ipm_kernel_gm1, dim3(B), dim3(64), (size_t)h->lds_bytes_gm, (hipStream_t)hip_stream, L, L2, L2); }
-        else hipLaunchKernelGGL(obca_ipm_kernel_gm, dim3(B), dim3(256), (size_t)h->lds_bytes_gm, (hipStream_t)hip_stream, L, L2, L2);
-        return hipGetLastError() == hipSuccess ? OBCA_OK : OBCA_E_HIP;
+    // which kernel, with what: a function of the shape, the mode and the knobs -- never of the batch size -- and, after a failed
+    // workspace allocation, of that fact (csrc/obca_select.h: plan)
+    sel::Plan plan = sel::plan(h->cap, h->knobs, h->refused);
+    if (plan.rc != OBCA_OK) return plan.rc;
+    // (OBCA_FAIL_WORKSPACE_ALLOC in the environment: the allocation is treated as failed -- the only way to exercise the branch below
+    // on a 288 GB device; tests/test_gpu_edge_cases.py)
+    if (plan.needs_ws && !h->gm_ws &&
+        (getenv("OBCA_FAIL_WORKSPACE_ALLOC") != nullptr ||
+         hipMalloc(&h->gm_ws, sizeof(double) * (size_t)h->cap.gm_doubles * (size_t)h->dims.max_batch) != hipSuccess)) {
+        (void)hipGetLastError();
+        h->gm_ws = nullptr;
+        // auto mode with an LDS-resident alternative: run that instead of failing the call (it needs no workspace); an explicit
+        // mode 4 / 5 and shapes only the workspace kernels hold report the failure
+        if (!(h->knobs.mode == 0 && sel::mw_offered(h->cap, h->refused))) return OBCA_E_NOMEM;
+        h->knobs.gm_ws_failed = true;
+        plan = sel::plan(h->cap, h->knobs, h->refused);       // (mode 0 is always available: the second plan cannot fail)
     }
-    // one wavefront per instance where the rows fit its registers; four wavefronts (one CU) per instance for bigger
-    // shapes that still fit the LDS; the lane kernel for everything else
-    // (the choice depends on the SHAPE only, never on the batch size: the answer to an instance must not depend on how many
-    // neighbours it was submitted with.  Measured: four wavefronts per instance would shorten launches of B <= 256 by 10-12 %,
-    // measured with OBCA_MODE=3 at batch sizes <= 256 -- callers that want that latency ask for it, as the obca() class does)
-    const bool mw = h->mode == 3 || (h->mode == 0 && !h->wave_ok && h->mw_ok);
-    const bool lane = !mw && (h->mode == 2 || !h->wave_ok);
-    if (mw || !lane) {
+    L.inst_off = plan.inst_off; L.soc_lds = plan.soc_lds; L.two_sided = plan.two_sided;
+    if (plan.kernel != sel::K_LANE) {
+        if (plan.needs_ws) { L.gm_ws = h->gm_ws; L.gm_stride = h->cap.gm_doubles; }
         // the kernels run the further passes of the start ladder (penalty escalation, next starts) themselves, from their own copy of the descriptor
-        if (mw) L.soc_lds = h->soc_lds_mw;
         ObcaLaunch L2 = L;
-        if (mw && h->shape_kernel_mw && h->specialise)
-            hipLaunchKernelGGL(h->shape_kernel_mw, dim3(B), dim3(256), (size_t)h->lds_bytes_mw, (hipStream_t)hip_stream, L, L2, L2);
-        else if (mw)
-            hipLaunchKernelGGL(h->R_max <= 768 ? obca_ipm_kernel_mw_r3 : obca_ipm_kernel_mw_r5, dim3(B), dim3(256),
-                               (size_t)h->lds_bytes_mw, (hipStream_t)hip_stream, L, L2, L2);
-        else if (h->shape_kernel && h->specialise)
-            hipLaunchKernelGGL(h->shape_kernel, dim3(B), dim3(64), (size_t)(h->lds_bytes + h->lds_pad), (hipStream_t)hip_stream, L, L2, L2);
-        else if (h->R_max <= 256)
-            hipLaunchKernelGGL(obca_ipm_kernel_r4, dim3(B), dim3(64), (size_t)(h->lds_bytes + h->lds_pad), (hipStream_t)hip_stream, L, L2, L2);
-        else if (h->R_max <= 320)
-            hipLaunchKernelGGL(obca_ipm_kernel_r5, dim3(B), dim3(64), (size_t)(h->lds_bytes + h->lds_pad), (hipStream_t)hip_stream, L, L2, L2);
-        else
-            hipLaunchKernelGGL(obca_ipm_kernel_r6, dim3(B), dim3(64), (size_t)(h->lds_bytes + h->lds_pad), (hipStream_t)hip_stream, L, L2, L2);
+        hipLaunchKernelGGL(h->kernel[plan.kernel], dim3(B), dim3(plan.threads), (size_t)plan.lds, (hipStream_t)hip_stream, L, L2, L2);
     } else {
         if (!h->ws || !h->d_offm) {
             if (!h->ws && hipMalloc(&h->ws, sizeof(double) * (size_t)h->ws_doubles * h->ws_stride) != hipSuccess) { h->ws = nullptr; return OBCA_E_NOMEM; }

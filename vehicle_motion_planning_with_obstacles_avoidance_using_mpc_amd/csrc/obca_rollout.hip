@@ -8,6 +8,7 @@
 #include "obca_device.h"
 #include "obca_rollout_core.h"
 #include "obca_audit_core.h"
+#include "obca_select.h"
 
 extern "C" __global__ void obca_rollout_fused_kernel_r4(const rollout::Dev* Dp, const ObcaLaunch* launches, int n_steps, int* sched, int qmode);
 extern "C" __global__ void obca_rollout_fused_kernel_r5(const rollout::Dev* Dp, const ObcaLaunch* launches, int n_steps, int* sched, int qmode);
@@ -72,6 +73,21 @@ struct obca_rollouts {
 };
 
 namespace {
+
+// the fused kernel whose row slots hold the largest group (the limits: csrc/obca_select.h)
+decltype(&obca_rollout_fused_kernel_r4) fused_kernel(int rows_max) {
+    const int slots = obca_select::wave_row_slots(rows_max);
+    return slots == 4 ? obca_rollout_fused_kernel_r4 : slots == 5 ? obca_rollout_fused_kernel_r5 : obca_rollout_fused_kernel_r6;
+}
+
+// shape of the solver of group g: the static obstacles and g sensed boxes of four rows; group 0 over the free-time horizon, the others over N_fix
+obca_dims group_dims(const obca_rollout_dims& d, int g) {
+    obca_dims sd = {};
+    sd.N = g == 0 || d.N_fix <= 0 ? d.N : d.N_fix; sd.n_obs = d.n_static + g; sd.max_batch = d.batch; sd.device = d.device;
+    for (int i = 0; i < d.n_static; ++i) sd.m[i] = d.m_static[i];
+    for (int i = 0; i < g; ++i) sd.m[d.n_static + i] = 4;
+    return sd;
+}
 
 template <class T>
 bool dev_alloc(obca_rollouts* r, T*& p, size_t count) {
@@ -144,11 +160,7 @@ extern "C" int obca_rollouts_create(const obca_rollout_dims* d, obca_rollouts** 
              dev_alloc(r, D.ts[g], B) && dev_alloc(r, D.status[g], B) && dev_alloc(r, D.iters[g], B) &&
              dev_alloc(r, D.status8[g], B) && dev_alloc(r, D.iters8[g], B);
         if (!ok) { rc = OBCA_E_NOMEM; break; }
-        obca_dims sd;
-        memset(&sd, 0, sizeof(sd));
-        sd.N = (int32_t)Ng; sd.n_obs = d->n_static + g; sd.max_batch = d->batch; sd.device = d->device;
-        for (int i = 0; i < d->n_static; ++i) sd.m[i] = d->m_static[i];
-        for (int i = 0; i < g; ++i) sd.m[d->n_static + i] = 4;
+        const obca_dims sd = group_dims(*d, g);
         rc = obca_create(&sd, &r->solver[g]);
         if (rc == OBCA_OK && g > 0 &&
             (hipStreamCreateWithFlags(&r->gstream[g], hipStreamNonBlocking) != hipSuccess ||
@@ -258,10 +270,7 @@ extern "C" int obca_rollouts_reset(obca_rollouts* r, const double* start, const 
         hipMemcpyAsync(r->dL, r->hL, sizeof(r->hL), hipMemcpyHostToDevice, s) != hipSuccess)
         return OBCA_E_HIP;
     if (r->fused_ok && r->lds_max > 64 * 1024 &&
-        hipFuncSetAttribute(r->rows_max <= 256   ? reinterpret_cast<const void*>(obca_rollout_fused_kernel_r4)
-                            : r->rows_max <= 320 ? reinterpret_cast<const void*>(obca_rollout_fused_kernel_r5)
-                                                 : reinterpret_cast<const void*>(obca_rollout_fused_kernel_r6),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)r->lds_max) != hipSuccess)
+        hipFuncSetAttribute(reinterpret_cast<const void*>(fused_kernel(r->rows_max)), hipFuncAttributeMaxDynamicSharedMemorySize, (int)r->lds_max) != hipSuccess)
         return OBCA_E_HIP;
     r->ready = true;
     return OBCA_OK;
@@ -346,11 +355,7 @@ extern "C" int obca_rollouts_set_warm_start(obca_rollouts* r, int enable, double
     rollout::Dev& D = r->D;
     if (enable && !D.wz[0]) {
         for (int g = 0; g <= D.n_dyn; ++g) {
-            obca_dims sd;
-            memset(&sd, 0, sizeof(sd));
-            sd.N = g == 0 ? D.N : D.Nf; sd.n_obs = D.n_static + g; sd.max_batch = D.B; sd.device = r->dims.device;
-            for (int i = 0; i < D.n_static; ++i) sd.m[i] = r->dims.m_static[i];
-            for (int i = 0; i < g; ++i) sd.m[D.n_static + i] = 4;
+            const obca_dims sd = group_dims(r->dims, g);
             const int64_t n = obca_primal_size(&sd);
             if (n < 0) return OBCA_E_INVAL;
             if (!dev_alloc(r, D.wz[g], (size_t)D.B * (size_t)n) || !dev_alloc(r, D.wuse[g], (size_t)D.B)) return OBCA_E_NOMEM;
@@ -428,15 +433,8 @@ extern "C" int obca_rollouts_run(obca_rollouts* r, int32_t n_steps, void* hip_st
         if (const char* e = getenv("OBCA_ROLLOUT_LOCAL_STEPS")) { const int v = atoi(e) / OBCA_RO_BLOCK * OBCA_RO_BLOCK; if (v > 0 && v < local_steps) local_steps = v; }
         for (int qmode = queue ? r->sched_mode : 0; ; qmode = 1) {
             const int steps_now = qmode == 2 ? local_steps : (int)n_steps;
-            if (r->rows_max <= 256)
-                hipLaunchKernelGGL(obca_rollout_fused_kernel_r4, dim3(grid), dim3(64), (size_t)r->lds_max, (hipStream_t)hip_stream,
-                                   (const rollout::Dev*)r->dD, (const ObcaLaunch*)r->dL, steps_now, sched, qmode);
-            else if (r->rows_max <= 320)
-                hipLaunchKernelGGL(obca_rollout_fused_kernel_r5, dim3(grid), dim3(64), (size_t)r->lds_max, (hipStream_t)hip_stream,
-                                   (const rollout::Dev*)r->dD, (const ObcaLaunch*)r->dL, steps_now, sched, qmode);
-            else
-                hipLaunchKernelGGL(obca_rollout_fused_kernel_r6, dim3(grid), dim3(64), (size_t)r->lds_max, (hipStream_t)hip_stream,
-                                   (const rollout::Dev*)r->dD, (const ObcaLaunch*)r->dL, steps_now, sched, qmode);
+            hipLaunchKernelGGL(fused_kernel(r->rows_max), dim3(grid), dim3(64), (size_t)r->lds_max, (hipStream_t)hip_stream,
+                               (const rollout::Dev*)r->dD, (const ObcaLaunch*)r->dL, steps_now, sched, qmode);
             if (qmode != 2) break;
         }
         return hipGetLastError() == hipSuccess ? OBCA_OK : OBCA_E_HIP;
