@@ -593,8 +593,52 @@ int obca_route_resample(int32_t B, int32_t path_max, int32_t N, const double* pa
                         const double* start /* [B,3] or NULL */, const double* goal /* [B,3] or NULL */,
                         double* xref_out /* [B,3,N+1] */, int32_t* ok_out /* [B] */, int32_t device, void* hip_stream);
 
+/* ------------------------------------------------------------------------------------------------------
+ * Scene pools (obca_mpc 0.14), on the device: which obstacles of a pool of up to 64 a solve sees.  OBCA_MAX_OBST bounds what
+ * one solve reads, not what a world holds: this call scores every obstacle of a pool by its distance to a set of poses, takes
+ * the n_sel nearest and gathers their rows for obca_solve_batch; called again with the plans solved against that selection it
+ * keeps a running minimum per obstacle, so that an obstacle left out which a plan comes close to is taken in.
+ * ego is a HOST pointer, the rest DEVICE pointers.  One pool per instance: K convex obstacles of exactly E rows each,
+ *   pool_A [B,K,E,2], pool_b [B,K,E], pool_v [B,K,2] in m/s or NULL (nothing moves), Ts [B] (may be NULL when pool_v is).
+ * Obstacle i at horizon stage kk has the rows A and b_kk[r] = b[r] + (kk * Ts) * (A[r,0] v_x + A[r,1] v_y), every product and
+ * sum rounded on its own (no FMA) -- exact for a set that translates at constant velocity, the fact obca_plan_sweep rests on.
+ * Poses: x [B,3,N+1] (a reference window, later obca_solve_batch's xopt) and x0 [B,3] or NULL (one more sample, against
+ * stage 0's rows: the car's pose is not knot 0 of a window).  The score of obstacle i is the smallest signed distance
+ * between the car footprint and the obstacle (the distance of obca_plan_clearance) over the samples: x0, and per interval
+ * stage s -> s + 1 the n_sub + 1 samples of obca_plan_sweep (n_sub = 1: the knots only; pose and b interpolated linearly),
+ * stage kk's pose against stage kk's rows; where variant[b] == 4 every sample against stage 0's rows (what obca_mpc4 reads).
+ * A sample whose pose is not finite is skipped.  variant [B] or NULL (every instance 6), status [B] or NULL (every instance 0).
+ *   accumulate = 0   score [B,K] is written from the samples; every usable instance counts as changed
+ *   accumulate = 1   score is in/out and becomes min(score, this call's samples); sel is in/out.  Only instances with
+ *                    variant != 0 and status 0 or 1 (obca_solve_batch's) are measured; the others keep score and selection
+ *   min_clear        [B] or NULL: THIS call's smallest distance over all K obstacles (no running minimum); NaN where the
+ *                    instance was not measured
+ *   sel [B,n_sel]    the n_sel obstacles with the smallest score, ties to the lower pool index, listed in ascending pool
+ *                    index (slots do not flip when two scores cross; comparing selections is an element-wise compare)
+ *   variant_out [B]  variant[b] where the selection differs from the one passed in (always with accumulate = 0), else 0:
+ *                    as obca_solve_batch's variant it re-solves exactly the instances whose rows changed (obca_plan_tighten's idiom)
+ *   A_out, b_out     [B,N+1,n_sel E,2] and [B,N+1,n_sel E]: obca_solve_batch's rows for a handle with m = E, n_sel times;
+ *                    written for every instance, changed or not
+ *   ok_out [B]       1, or 0 for an unusable instance: a pool row, a velocity or a Ts it needs that is not finite, a pool
+ *                    row a = (0, 0), no sample pose that is finite, a distance that is no number (overflow), or (accumulate,
+ *                    not measured) a selection passed in that is not an ascending list of pool indices.  Such an instance gets
+ *                    variant_out 0, sel = 0 .. n_sel-1, score untouched, min_clear NaN and every output row a = (1, 0),
+ *                    b = -1e6.  No row, score or selection written is ever NaN: masked launches downstream read numbers.
+ * B >= 1, 1 <= K <= 64 (one lane per obstacle), 1 <= E <= OBCA_MAX_EDGES, 1 <= N <= 127, 1 <= n_sel <= min(K, OBCA_MAX_OBST),
+ * 1 <= n_sub <= 256, accumulate 0 or 1, ego finite; Ts not NULL where pool_v is given; A_out 16-byte aligned (hipMalloc's
+ * are); ego, pool_A, pool_b, x, score, sel, A_out, b_out, variant_out and ok_out not NULL.  Every argument is checked before
+ * the first HIP call; a refused call (OBCA_E_INVAL) has no side effect.  Asynchronous on hip_stream. */
+int obca_scene_select(const double ego[4], int32_t B, int32_t K, int32_t E, int32_t N, int32_t n_sel, int32_t n_sub,
+                      int32_t accumulate, const double* pool_A, const double* pool_b, const double* pool_v /* or NULL */,
+                      const double* Ts /* [B] */, const double* x, const double* x0 /* [B,3] or NULL */,
+                      const int32_t* variant /* [B] or NULL */, const int32_t* status /* [B] or NULL */,
+                      double* score /* [B,K] */, int32_t* sel /* [B,n_sel] */, double* A_out, double* b_out,
+                      int32_t* variant_out /* [B] */, int32_t* ok_out /* [B] */, double* min_clear /* [B] or NULL */,
+                      int32_t device, void* hip_stream);
+
 const char* obca_strerror(int code);
-/* "obca_mpc 0.13 (gfx950)": 0.13 = route-seeded open-loop planning (obca_grid_dilate_batch, obca_route_resample);
+/* "obca_mpc 0.14 (gfx950)": 0.14 = scene pools (obca_scene_select);
+ * 0.13 = route-seeded open-loop planning (obca_grid_dilate_batch, obca_route_resample);
  * 0.12 = the refinement step of the two-stage open-loop planner (obca_plan_refine);
  * 0.11 = clearance repair of batched plans (obca_plan_tighten);
  * 0.10 = obca_astar_batch's code -4 (start or goal outside the grid), obca_rasterise_batch clips boxes to the map;

@@ -204,6 +204,39 @@ def make_batch(B, N=5, seed0=SEED0, three_boxes=False, first=0, procs=1):
     return out
 
 
+def make_pool_batch(B, n_distract, N=5, seed=11, first=0):
+    """Scene pools (scene.solve_scene) on the headline workload: ``make_batch(B, N, three_boxes=True)`` -- two walls and
+    one box of 4 rows each -- plus ``n_distract`` unit squares per instance that a short window mostly does not touch.
+    One generator ``default_rng(seed)`` for the whole batch, per distractor centre x in [x0.x - 3, xref_N.x + 6], y in [2, 8];
+    a square is redrawn while it is closer than 0.6 m to the car footprint at x0 or at the last reference knot, or closer
+    than 0.2 m to the instance's own box.  Returns make_batch's dict (A, b, m are the three own obstacles) with pool_A
+    [B,K,4,2] and pool_b [B,K,4], K = 3 + n_distract: the own obstacles first, then the squares."""
+    ins = [make_instance(first + i, N, SEED0, True) for i in range(B)]
+    rng = np.random.default_rng(seed)
+    om = obstacleModel()
+    K = 3 + int(n_distract)
+    pool_A, pool_b = np.zeros((B, K, 4, 2)), np.zeros((B, K, 4))
+    for i, q in enumerate(ins):
+        pool_A[i, :3], pool_b[i, :3] = q["A"].reshape(3, 4, 2), q["b"].reshape(3, 4)
+        own = np.array(rectangle_vertices(q["box"][0], q["box"][1], 0.0, q["box"][2], q["box"][3])[:4])
+        cars = [_car_corners(q["x0"]), _car_corners(q["xref"][:, N])]
+        for k in range(3, K):
+            while True:
+                cx, cy = rng.uniform(q["x0"][0] - 3.0, q["xref"][0, N] + 6.0), rng.uniform(2.0, 8.0)
+                rect = rectangle_vertices(cx, cy, 0.0, 1.0, 1.0)
+                sq = np.array(rect[:4])
+                if min(_poly_distance(c, sq) for c in cars) >= 0.6 and _poly_distance(own, sq) >= 0.2:
+                    break
+            A, b = om.obstacle_H_Represent(1, [5], [rect])
+            pool_A[i, k], pool_b[i, k] = A, b[:, 0]
+    M = 12
+    return dict(m=[4, 4, 4], variant=np.full(B, 4, dtype=np.int32), x0=np.stack([q["x0"] for q in ins]),
+                u0=np.stack([q["u0"] for q in ins]), xref=np.stack([q["xref"] for q in ins]),
+                A=np.stack([np.broadcast_to(q["A"], (N + 1, M, 2)) for q in ins]).copy(),
+                b=np.stack([np.broadcast_to(q["b"], (N + 1, M)) for q in ins]).copy(),
+                Ts=np.full(B, TS), term=np.zeros((B, 3)), pool_A=pool_A, pool_b=pool_b)
+
+
 # ---------------------------------------------------------------------------------------------------------------
 # Config C3 (SURVEY.md 8d): N = 20, walls + one static box + two moving 3x3 boxes crossing the corridor, lidar
 # gated -- gated instances are fixed-time solves (obca_mpc6, fallback obca_mpc8) with time-varying obstacle rows,
