@@ -636,8 +636,44 @@ int obca_scene_select(const double ego[4], int32_t B, int32_t K, int32_t E, int3
                       int32_t* variant_out /* [B] */, int32_t* ok_out /* [B] */, double* min_clear /* [B] or NULL */,
                       int32_t device, void* hip_stream);
 
+/* ------------------------------------------------------------------------------------------------------
+ * Occupancy grids to scene pools (obca_mpc 0.15), on the device: the inverse of obca_rasterise_batch.  Every grid
+ * [rows,cols] of bytes (non-zero = occupied) is covered by disjoint axis-parallel rectangles of cells, and every rectangle
+ * becomes one pool obstacle of 4 rows for obca_scene_select: pool_A [B,K,4,2], pool_b [B,K,4].  All pointers are DEVICE pointers.
+ * Cover (greedy right-then-down; csrc/obca_gridpool_core.h holds the serial definition the kernel reproduces exactly):
+ *   work = occupied cells; n = 0
+ *   for r = 0 .. rows-1, for c = 0 .. cols-1 (row-major): if (r, c) in work:
+ *       c1 = last column of the unbroken run of work cells (r, c), (r, c+1), ...
+ *       r1 = last row such that every cell of rows r .. r1, columns c .. c1 is in work
+ *       remove rows r..r1 x columns c..c1 from work;  if n < K: rect[n] = (r, c, r1, c1);  n = n + 1
+ *   count = n                      (the true number, also where it exceeds K)
+ * The rectangles are disjoint, their union is the occupied set, they are listed in strictly ascending (r0, c0).  No
+ * minimum-count cover.
+ * Rows of rectangle (r0, c0, r1, c1): xlo = c0 resolution - pad, xhi = c1 resolution + pad, ylo = r0 resolution - pad,
+ * yhi = r1 resolution + pad, every product and difference rounded on its own (no FMA); E = 4 rows in the order
+ * (0, 1 | yhi), (1, 0 | xhi), (0, -1 | -ylo), (-1, 0 | -xlo) -- for a rectangle with area what obstacle_H_Represent gives
+ * for the clockwise polygon [[xlo,yhi],[xhi,yhi],[xhi,ylo],[xlo,ylo],[xlo,yhi]].  pad = 0: a cell is a lattice point (the
+ * reference's convention; the boxes rasterise back to exactly these cells at the same resolution); pad = resolution / 2: a
+ * cell is a square centred on its lattice point, so that neighbouring rectangles touch.
+ *   rect [B,K,4]     or NULL: (r0, c0, r1, c1) of slot k, (-1,-1,-1,-1) for a spare slot
+ *   count [B]        the number of rectangles of the cover, also where it exceeds K
+ *   ok [B]           1 if count <= K, else 0: the first K rectangles are written and valid, the map is not covered
+ *   spare slots      k >= count: the rows of the unit square [-far-1, -far]^2 in the same row order.  far is the caller's
+ *                    choice because a spare that is selected becomes rows of a solve: 100 or 1000 leave the structured solver's
+ *                    plans as they are, 1e6 (the fill of obca_scene_select) makes it fail (csrc/obca_gridpool_core.h)
+ * Nothing written is ever NaN.
+ * B >= 1, 1 <= K <= 64, rows >= 1, cols >= 1, rows * ceil(cols / 64) <= 4096 (the bit-packed grid in 32 KB of LDS: 11 x 40,
+ * 255 x 255 and 1024 x 256 fit), resolution > 0, pad >= 0 and far > 0, all finite; grid, pool_A, pool_b, count and ok not
+ * NULL; pool_A 16-byte aligned (hipMalloc's are); device >= 0.  Every argument is checked before the first HIP call; a refused
+ * call (OBCA_E_INVAL) has no side effect.  Asynchronous on hip_stream. */
+int obca_grid_pool(const uint8_t* grid /* [B,rows,cols] */, int32_t B, int32_t rows, int32_t cols, int32_t K,
+                   double resolution, double pad, double far,
+                   double* pool_A /* [B,K,4,2] */, double* pool_b /* [B,K,4] */, int32_t* rect /* [B,K,4] or NULL */,
+                   int32_t* count /* [B] */, int32_t* ok /* [B] */, int32_t device, void* hip_stream);
+
 const char* obca_strerror(int code);
-/* "obca_mpc 0.14 (gfx950)": 0.14 = scene pools (obca_scene_select);
+/* "obca_mpc 0.15 (gfx950)": 0.15 = occupancy grids to scene pools (obca_grid_pool);
+ * 0.14 = scene pools (obca_scene_select);
  * 0.13 = route-seeded open-loop planning (obca_grid_dilate_batch, obca_route_resample);
  * 0.12 = the refinement step of the two-stage open-loop planner (obca_plan_refine);
  * 0.11 = clearance repair of batched plans (obca_plan_tighten);

@@ -59,7 +59,7 @@ EXPORTS = ("obca_create", "obca_destroy", "obca_solve_batch", "obca_lds_bytes", 
            "obca_rollouts_set_warm_start", "obca_dual_size", "obca_set_certificate_buffers", "obca_rasterise_batch",
            "obca_plan_clearance", "obca_plan_sweep", "obca_plan_tighten", "obca_rollouts_audit", "obca_rollouts_set_collision_stop", "obca_rollouts_set_exact_sensing",
            "obca_rollouts_read_clearance", "obca_rollouts_set_swept_rows", "obca_moving_rows_batch", "obca_plan_refine",
-           "obca_grid_dilate_batch", "obca_route_resample", "obca_scene_select")
+           "obca_grid_dilate_batch", "obca_route_resample", "obca_scene_select", "obca_grid_pool")
 
 OBCA_MAX_DYN = 4
 RUN, DONE_GOAL, DONE_CAP, DONE_FAILED, DONE_COLLISION = 0, 1, 2, 3, 4
@@ -194,6 +194,8 @@ def load():
     lib.obca_scene_select.argtypes = [ctypes.POINTER(ctypes.c_double)] + [ctypes.c_int32] * 7 + [vp, vp, vp, vp, vp, vp, i32p, i32p, vp, i32p,
                                                                                                  vp, vp, i32p, i32p, vp, ctypes.c_int32, vp]
     lib.obca_scene_select.restype = ctypes.c_int
+    lib.obca_grid_pool.argtypes = [vp] + [ctypes.c_int32] * 4 + [ctypes.c_double] * 3 + [vp, vp, i32p, i32p, i32p, ctypes.c_int32, vp]
+    lib.obca_grid_pool.restype = ctypes.c_int
     lib.obca_lds_bytes.argtypes = [ctypes.POINTER(ObcaDims)]
     lib.obca_lds_bytes.restype = ctypes.c_int64
     lib.obca_strerror.argtypes = [ctypes.c_int]

@@ -7,6 +7,11 @@ instances' selections changed.  ``pool_clearance`` is the same measurement as an
 one that is not bound to OBCA_MAX_OBST obstacles.  ``solve_scene`` is the loop: select from the reference, solve, measure
 the plans against the whole pool, re-select, solve again where the selection changed.  No solver kernel is involved beyond
 being called with other rows.
+
+``grid_pool`` (obca_grid_pool, arithmetic in csrc/obca_gridpool_core.h) is the producer of pools on the device: it covers
+every occupancy grid of a batch with disjoint axis-parallel rectangles, one pool obstacle each.  ``solve_maps`` composes it
+with ``openloop.route_references`` and ``solve_scene``: B maps and B start/goal pairs in, B plans out, each measured against
+its whole map.
 """
 import ctypes
 
@@ -170,3 +175,80 @@ def solve_scene(solver, variant, x0, u0, xref, pool_A, pool_b, Ts, pool_v=None, 
     held.iters.copy_(iters)
     return held, {"clear": min_clear >= float(target), "min_clear": min_clear, "min_clear_first": first,
                   "rounds_used": rounds_used, "sel": sel_held, "A_used": A_held, "b_used": b_held}
+
+
+def grid_pool(grids, K, resolution=1.0, pad=None, far=100.0, device=None):
+    """Occupancy grids -> scene pools (obca_grid_pool): grids [B,rows,cols] (non-zero = occupied; a device tensor, e.g.
+    ``planner.rasterise_batch``'s, stays on the device), K <= 64 slots per pool.  Every grid is covered greedily (right, then
+    down, in row-major order) by disjoint rectangles of cells; rectangle (r0, c0, r1, c1) becomes the box
+    [c0 res - pad, c1 res + pad] x [r0 res - pad, r1 res + pad] as 4 rows.  pad=None means resolution / 2 (a cell is a square
+    centred on its lattice point, neighbouring rectangles touch); pad=0 is the reference's convention (a cell is a lattice
+    point: ``planner.rasterise_batch`` of the boxes gives the grid back).  Spare slots hold the unit square
+    [-far-1, -far]^2: far enough never to be near a plan, near enough for a solve that selects it (1e6 is not).
+
+    Returns a dict of device tensors on the current stream, no host synchronisation: pool_A [B,K,4,2], pool_b [B,K,4]
+    (``select``'s pool arguments), rect [B,K,4] int32 ((-1,-1,-1,-1) for a spare slot), count [B] int32 (the true number of
+    rectangles, also beyond K) and ok [B] int32 (0: count > K, the first K rectangles are written, the map is not covered)."""
+    import numpy as np
+    import torch
+    if not torch.cuda.is_available():
+        raise RuntimeError("scene.grid_pool needs a ROCm GPU; there is no CPU fallback on the product path")
+    dev = _dev_of(device, grids)
+    if isinstance(grids, torch.Tensor):
+        g = grids.to(device=dev, dtype=torch.uint8).contiguous()
+    else:
+        g = torch.as_tensor(np.ascontiguousarray(grids), device=dev).to(torch.uint8).contiguous()
+    if g.dim() != 3:
+        raise ValueError("expected grids [B,rows,cols], got %s" % (tuple(g.shape),))
+    B, rows, cols = (int(v) for v in g.shape)
+    K, resolution = int(K), float(resolution)
+    pad = resolution / 2 if pad is None else float(pad)
+    k = max(K, 0)
+    out = {"pool_A": torch.empty(B, k, 4, 2, dtype=torch.float64, device=dev),
+           "pool_b": torch.empty(B, k, 4, dtype=torch.float64, device=dev),
+           "rect": torch.empty(B, k, 4, dtype=torch.int32, device=dev),
+           "count": torch.empty(B, dtype=torch.int32, device=dev),
+           "ok": torch.empty(B, dtype=torch.int32, device=dev)}
+    p = _lib.ptr
+    _lib.check(_lib.load().obca_grid_pool(p(g), B, rows, cols, K, resolution, pad, float(far), p(out["pool_A"]), p(out["pool_b"]),
+                                          p(out["rect"]), p(out["count"]), p(out["ok"]), _lib.device_index(dev),
+                                          _lib.stream_ptr(dev)))
+    out["pool_A"]._obca_keep = (g,)                          # the launch is asynchronous: see planner.dilate_batch
+    g.record_stream(torch.cuda.current_stream(dev))
+    return out
+
+
+def solve_maps(solver, grids, start_cells, goal_cells, start, goal, Ts, K, pad=None, far=100.0, dilation=1, variant=4, u0=None,
+               term=None, params=None, rounds=2, n_sub=16, target=0.0, ego=DEFAULT_EGO):
+    """B occupancy grids and B start/goal pairs -> B plans, each measured against its whole map, on the current stream without
+    host synchronisation: ``grid_pool(grids, K, pad=pad, far=far)`` gives the pools, ``openloop.route_references(grids,
+    start_cells, goal_cells, solver.N, start=start, goal=goal, dilation=dilation)`` the references, ``solve_scene(solver,
+    variant, x0=start, ...)`` the plans.  grids [B,rows,cols], start_cells / goal_cells [B,2] as (row, col), start / goal
+    [B,3] poses, Ts [B] or a float, u0 [B,2] (None: zeros); ``solver`` must have m == [4] * n_sel, n_sel <= K.
+
+    Resolution 1 only, and no ``resolution`` argument: the planner's routes are in cells, so a cell is a metre here.
+
+    An instance whose pool is incomplete (grid_pool's ok == 0) or that has no route (route_references' source == 0) is
+    masked -- variant 0, made on the device with ``torch.where`` -- and reported, never raised on.  Returns (result, info)
+    exactly as ``solve_scene`` does; ``info`` also carries ``pool`` (grid_pool's dict), ``xref`` [B,3,N+1], ``pool_ok`` [B]
+    and ``source`` [B] (2 = the dilated route, 1 = the plain route, 0 = none)."""
+    import torch
+    from .openloop import route_references
+    dev = solver.device
+    if not isinstance(grids, torch.Tensor):                  # one upload for the cover and both searches
+        import numpy as np
+        grids = torch.as_tensor(np.ascontiguousarray(grids), device=dev)
+    pool = grid_pool(grids, K, resolution=1.0, pad=pad, far=far, device=dev)
+    xref, _, source = route_references(grids, start_cells, goal_cells, solver.N, start=start, goal=goal, dilation=dilation,
+                                       device=dev)
+    B = int(source.shape[0])
+    if isinstance(variant, int):
+        variant = torch.full((B,), variant, dtype=torch.int32, device=dev)
+    variant = solver._dev(variant, (B,), torch.int32)
+    variant = torch.where((pool["ok"] != 0) & (source != 0), variant, 0).to(torch.int32)
+    if u0 is None:
+        u0 = torch.zeros(B, 2, dtype=torch.float64, device=dev)
+    result, info = solve_scene(solver, variant, start, u0, xref, pool["pool_A"], pool["pool_b"], Ts, term=term, params=params,
+                               rounds=rounds, n_sub=n_sub, target=target, ego=ego)
+    info.update(pool=pool, xref=xref, pool_ok=pool["ok"], source=source)
+    return result, info
