@@ -1,0 +1,91 @@
+"""The Riccati sweep at the lane and shape edges its load batching touches (csrc/obca_kernel.hip: riccati(): every phase loads
+unconditionally with clamped indices, selects in registers and stores through a selected address), against the dense C oracle.
+
+Rule of tests/test_gpu_parity.py: the feasibility class is the oracle's on every instance; where the iteration counts agree
+the plans agree to 1e-9, otherwise to 1e-5.  The number of instances allowed the looser bound is a cap, not a knob: it is the
+count measured per case with the kernels as they were BEFORE the loads were batched (PARENT_LOOSE below; the rewrite moves loads
+and stores only and every output word stayed the same, so its own counts are the same).  The batches are the generators' first
+seeds: the oracle converges on every instance of every case (checked on the host), which the test asserts again.  Every case must also contain an instance with more factorisations than iterations: an attempt that ended at
+a wrong-sign pivot (the sweep's early exit) and was repeated with a larger regularisation."""
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import c_oracle
+from vehicle_motion_planning_with_obstacles_avoidance_using_mpc_amd import scenarios as sc
+from vehicle_motion_planning_with_obstacles_avoidance_using_mpc_amd.solver import BatchSolver, SolverParams
+
+pytestmark = pytest.mark.gpu
+
+
+def _two_walls(B, N):
+    """the C2 generator without its box: two obstacles of one row each -- the fewest (stage, obstacle) pairs a kernel is built for"""
+    b = sc.make_batch(B, N)
+    return dict(b, m=[1, 1], A=np.ascontiguousarray(b["A"][:, :, [0, 5]]), b=np.ascontiguousarray(b["b"][:, :, [0, 5]]))
+
+
+# name -> (batch, N, variant or None (the generator's own), solver mode, two-sided sweep, specialised kernel expected)
+CASES = {
+    "s5_2_2_free_time": lambda: (_two_walls(32, 5), 5, 4, None, None, True),
+    "s5_2_2_fixed_time": lambda: (_two_walls(32, 5), 5, 8, None, None, True),
+    "s6_5_14_terminal_set": lambda: (sc.make_batch_c3(32, 6, gated=True), 6, 6, None, None, True),
+    "generic_three_boxes": lambda: (sc.make_batch(16, 5, three_boxes=True), 5, None, None, None, False),
+    "four_wavefronts_two_sided": lambda: (sc.make_batch_c3(16, 8, gated=True), 8, None, "multiwave", True, None),
+    "hbm_workspace_free_time": lambda: (sc.make_batch_c3(16, 12, gated=False), 12, None, "global1", None, None),
+}
+# instances whose iteration count differs from the oracle's, per case, measured with the kernels before the rewrite
+# (MI355X: none in any case -- every instance follows the oracle's iterate sequence; largest deviations 4e-15 ... 2.4e-11)
+PARENT_LOOSE = {"s5_2_2_free_time": 0, "s5_2_2_fixed_time": 0, "s6_5_14_terminal_set": 0, "generic_three_boxes": 0,
+                "four_wavefronts_two_sided": 0, "hbm_workspace_free_time": 0}
+
+_oracle_cache = {}
+
+
+def oracle(name):
+    """the dense C oracle on the case's batch, computed once"""
+    if name not in _oracle_cache:
+        b, N, variant, _, _, _ = CASES[name]()
+        v = b["variant"] if variant is None else np.full(len(b["variant"]), variant, np.int32)
+        ref = c_oracle.solve_batch(v, N, b["m"], b["x0"], b["u0"], b["xref"], b["A"], b["b"], b["Ts"], b["term"],
+                                   threads=min(len(v), os.cpu_count() or 1))
+        _oracle_cache[name] = (b, N, v, ref)
+    return _oracle_cache[name]
+
+
+def solve(name):
+    b, N, v, ref = oracle(name)
+    _, _, _, mode, two_sided, specialised = CASES[name]()
+    s = BatchSolver(N, b["m"], max_batch=len(v), mode=mode)
+    s.set_two_sided_sweep(two_sided)
+    assert specialised is None or bool(s.specialised) == specialised
+    o = s.solve(v, b["x0"], b["u0"], b["xref"], b["A"], b["b"], b["Ts"], b["term"], SolverParams())
+    torch.cuda.synchronize()
+    got = {k: getattr(o, k).cpu().numpy().copy() for k in ("xopt", "uopt", "ts_opt", "status", "iters", "info")}
+    s.close()
+    return got, ref
+
+
+def compare(got, ref):
+    """(instances at the looser bound, largest deviation among the tight ones, among the loose ones, instances with a repeated factorisation)"""
+    ok_ref, ok = np.isin(ref["status"], (0, 1)), np.isin(got["status"], (0, 1))
+    assert ok_ref.all()                                     # the seeds are chosen so
+    assert np.array_equal(ok, ok_ref)
+    dev = np.array([max(np.abs(got["xopt"][i] - ref["xopt"][i]).max(), np.abs(got["uopt"][i] - ref["uopt"][i]).max(),
+                        abs(got["ts_opt"][i] - ref["ts_opt"][i])) for i in range(len(ok))])
+    same = got["iters"] == ref["iters"]
+    refact = int((got["info"][:, 3] > got["iters"]).sum())
+    return int((~same).sum()), float(dev[same].max(initial=0.0)), float(dev[~same].max(initial=0.0)), refact
+
+
+@pytest.mark.parametrize("name", sorted(CASES))
+def test_sweep_matches_the_dense_oracle(name):
+    got, ref = solve(name)
+    loose, dev_tight, dev_loose, refact = compare(got, ref)
+    print("%s: %d of %d at the looser bound (before the rewrite: %s), max deviation %.2e / %.2e, %d with a repeated factorisation"
+          % (name, loose, len(got["iters"]), PARENT_LOOSE[name], dev_tight, dev_loose, refact))
+    assert dev_tight <= 1e-9
+    assert dev_loose <= 1e-5
+    assert loose <= PARENT_LOOSE[name]
+    assert refact >= 1

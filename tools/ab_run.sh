@@ -1,14 +1,18 @@
 # dev tool: A/B of library builds on the GPU.  usage: bash tools/ab_run.sh "libA.so libB.so" "c2 c3g5" [cmp]
+# Every step runs under its own time limit, and the first one that fails ends the run: nothing more is started on the card.
+set -u -o pipefail
 LIBS=${1:-"libobca_mpc_base.so libobca_mpc.so"}
 WL=${2:-"c2 c2m12 c3g5 c3f c3g"}
+CMP=${3:-}
+step() { timeout -k 10 600 "$@" 2>&1 | { grep -v amdgpu.ids || true; }; }
 for lib in $LIBS; do
   for w in $WL; do
-    if [ "$w" = "c5" ]; then OBCA_LIB=$lib OBCA_QUEUE_MODES=2,2 python tools/gpu_c5_modes.py 2>&1 | grep -v amdgpu.ids | tail -1 | sed "s/^/$lib c5 /"
-    else OBCA_LIB=$lib python tools/gpu_variant_bench.py $w 2>&1 | grep -v amdgpu.ids; fi
+    if [ "$w" = "c5" ]; then step env OBCA_LIB=$lib OBCA_QUEUE_MODES=2,2 python tools/gpu_c5_modes.py | tail -1 | sed "s/^/$lib c5 /" || exit 1
+    else step env OBCA_LIB=$lib python tools/gpu_variant_bench.py $w || exit 1; fi
   done
-  if [ -n "$3" ]; then OBCA_LIB=$lib python tools/gpu_cmp_builds.py /tmp/cmp_$lib.npz 2>&1 | grep -v amdgpu.ids; fi
+  if [ -n "$CMP" ]; then step env OBCA_LIB=$lib python tools/gpu_cmp_builds.py /tmp/cmp_$lib.npz || exit 1; fi
 done
-if [ -n "$3" ]; then python - $LIBS <<'PY'
+if [ -n "$CMP" ]; then python - $LIBS <<'PY'
 import sys, numpy as np
 ref = np.load("/tmp/cmp_%s.npz" % sys.argv[1])
 for lib in sys.argv[2:]:

@@ -1,9 +1,9 @@
 """dev tool: per-phase shader-clock shares of the solver (library built by tools/build_variant.sh prof -DOBCA_PROFILE):
-python tools/gpu_prof.py B c2|c3|c3free N"""
-import sys, ctypes, numpy as np, torch
+python tools/gpu_prof.py B c2|c3|c3free N     (OBCA_LIB=<file name inside the package>: another instrumented build, e.g. the parent's)"""
+import os, sys, ctypes, numpy as np, torch
 sys.path.insert(0, '.')
 from vehicle_motion_planning_with_obstacles_avoidance_using_mpc_amd import _lib, scenarios as sc
-_lib.LIB_PATH = _lib.LIB_PATH.replace('libobca_mpc.so', 'libobca_mpc_prof.so')
+_lib.LIB_PATH = os.path.join(_lib.HERE, os.environ.get('OBCA_LIB', 'libobca_mpc_prof.so'))
 from vehicle_motion_planning_with_obstacles_avoidance_using_mpc_amd.solver import BatchSolver, SolverParams
 B=int(sys.argv[1]) if len(sys.argv)>1 else 768
 N=int(sys.argv[3]) if len(sys.argv)>3 else 5

@@ -1000,10 +1000,20 @@ __device__ __forceinline__ void lu3_solve(const Lu3& f, double r0, double r1, do
 // entry e = 8 a + b of the stage's [F G] = d xi_{k+1} / d (xi_k, du_k), xi = (dp, du_prev, dT): rows 0-2 the pose
 // update p + h (v cos, v sin, w) (column 5: its T-derivative), rows 3-4 pick du_k, row 5 carries dT.  Only ONE
 // stage's 6 x 8 block is kept in LDS: stage k-1's is written while phase B of stage k runs.
-__device__ __forceinline__ double fg_entry(const Lay& L, const Sh& S, const Inst& in, const double* xv, double h, int k, int e) {
+// The stage's four operands are loaded apart from the selection of the entry (fg_load: unconditional, the same on every
+// lane), so that the caller can make them part of a batch of loads: read where the nested ifs below use them, each got
+// a round trip of its own.
+struct FgOps { double cs, sn, u0, u1; };
+__device__ __forceinline__ FgOps fg_load(const Lay& L, const Sh& S, int k) {
+    FgOps f;
+    f.cs = S.ct[k]; f.sn = S.st[k];
+    f.u0 = S.uv[L.uvs * k + L.uvo]; f.u1 = S.uv[L.uvs * k + L.uvo + 1];
+    return f;
+}
+__device__ __forceinline__ double fg_select(const Lay& L, const Inst& in, const FgOps& f, double h, int e) {
     const int a = e >> 3, b = e & 7;
-    const double cs = S.ct[k], sn = S.st[k];
-    const double* u = S.uv + L.uvs * k + L.uvo;
+    const double cs = f.cs, sn = f.sn;
+    const double u[2] = {f.u0, f.u1};
     double v = 0.0;
     if (a < 3) {
         if (b < 3) v = (a == b) ? 1.0 : 0.0;
@@ -1207,7 +1217,6 @@ __device__ __forceinline__ int riccati(const Lay& L, const Sh& S, const Inst& in
 #ifdef NO_RICCATI
     return 0;
 #endif
-    const double* xv = S.x;
     const double T = L.free_T ? *S.Tv : 1.0;
     const double h = T * in.Ts;
     int bad = 0;
@@ -1220,17 +1229,17 @@ __device__ __forceinline__ int riccati(const Lay& L, const Sh& S, const Inst& in
     constexpr int m = 0;
 #endif
     // [F G] of the first stage of the sweep, and the terminal value function
-    for (int t = lane; t < 48; t += NT) S.FG[t] = fg_entry(L, S, in, xv, h, L.N - 1, t);
     {
         double* PN = S.Pk + 36 * L.N;
         double* qN = S.qk + 6 * L.N;
-        if (lane < 36) {
-            const int a = lane / 6, b = lane - 6 * a;
-            PN[lane] = (a < 3 && b < 3) ? S.Lall[36 * L.N + LS(a, b)] : 0.0;
-        } else if (lane < 42) {
-            const int a = lane - 36;
-            qN[a] = (a < 3) ? S.lall[8 * L.N + a] : 0.0;
-        }
+        const bool isP = lane < 36, has = lane < 42;
+        const int a = isP ? lane / 6 : lane - 36, b = isP ? lane - 6 * (lane / 6) : 0;
+        const bool live = has && a < 3 && b < 3;        // (the others store zero and read entry 0)
+        FgOps fo = fg_load(L, S, L.N - 1);
+        double tv = *(isP ? S.Lall + 36 * L.N + (live ? LS(a, b) : 0) : S.lall + 8 * L.N + (live ? a : 0));
+        asm volatile("" : "+v"(fo.cs), "+v"(fo.sn), "+v"(fo.u0), "+v"(fo.u1), "+v"(tv));
+        for (int t = lane; t < 48; t += NT) S.FG[t] = fg_select(L, in, fo, h, t);
+        if (has) *(isP ? PN + lane : qN + a) = live ? tv : 0.0;
     }
     RSYNC();
     RPROF(12)
@@ -1240,54 +1249,71 @@ __device__ __forceinline__ int riccati(const Lay& L, const Sh& S, const Inst& in
         //   P~ f = ( M (Ppp f_p + Ppo f_o) ,  Poo f_o + Pop E M (E^-1 f_p - Ppo f_o) )
         // (second block through M' = E M E^-1), i.e. one 3x3 LU per lane and two substitutions instead of the explicit
         // inverse, the 3x6 product M [Ppp Ppo], the symmetrised 6x6 P~ and a 6x6 quadratic form -- same pivots, same inertia test.
+        // The wavefront is alone on its SIMD: nothing covers an LDS round trip but its own other loads.  So every phase
+        // issues its loads unconditionally at its top (indices valid on every lane: a lane without an entry reads some
+        // entry of the same array), keeps them together with ONE empty asm over the whole batch (left alone, the compiler
+        // sinks each load into the divergent branch of its select and waits for them one by one; pinned one by one, each
+        // load gets a full wait of its own), selects in registers and stores through a selected address.
         double E[3], Dv[3], gh[3];
 #pragma unroll
-        for (int j = 0; j < 3; ++j) { Dv[j] = S.Es[L.r_dyn + 3 * k + j]; E[j] = rcp64(Dv[j]); gh[j] = S.gs[L.r_dyn + 3 * k + j]; }
+        for (int j = 0; j < 3; ++j) { Dv[j] = S.Es[L.r_dyn + 3 * k + j]; gh[j] = S.gs[L.r_dyn + 3 * k + j]; }
         if (NT == 64 || lane < 64) {        // (four wavefronts: the serial sweep is the first wavefront's job alone --
             // the others would only repeat it and compete for the LDS)
             const double* Pl = S.Pk + 36 * (k + 1);
             const double* ql = S.qk + 6 * (k + 1);
+            // lanes 0..35: entry (a, b), a >= b, of the SYMMETRIC stage matrix (packed like the stage blocks: lane = LS(a, b));
+            // lanes 36..43: entry a of its gradient, computed by the same expression: with f = (-ghat, 0) as the "column",
+            //   lall + [F G]' (q~ - P~ (ghat, 0)) = lall + [F G]' (P~ f + q~),   q~ = (M q_p, q_o - Pop E M q_p),
+            // i.e. q_p joins the right-hand sides of the two substitutions and q_o the second block -- no separate pass
+            // (lanes 44..63 repeat a gradient entry and store nothing)
+            const bool isg = lane >= 36;
+            const int a = isg ? (lane - 36) & 7 : (lane >= 28) ? 7 : (lane >= 21) ? 6 : (lane >= 15) ? 5 : (lane >= 10) ? 4 : (lane >= 6) ? 3 : (lane >= 3) ? 2 : (lane >= 1) ? 1 : 0;
+            const int b = isg ? 0 : lane - a * (a + 1) / 2;
+            const double gm = isg ? 1.0 : 0.0;
             // P is used in two halves (rows 0-2: LU and the two right-hand sides; rows 3-5: the second block of P~ f), loaded
             // one after the other -- all 36 entries at once were the register peak of the sweep
             double Pa[18], Pb[18];
 #pragma unroll
             for (int i = 0; i < 18; ++i) Pa[i] = Pl[i];
+            double fgb[6], qp[3];
+#pragma unroll
+            for (int c = 0; c < 6; ++c) fgb[c] = S.FG[8 * c + b];
+#pragma unroll
+            for (int i = 0; i < 3; ++i) qp[i] = ql[i];
+            asm volatile("" : "+v"(fgb[0]), "+v"(fgb[1]), "+v"(fgb[2]), "+v"(fgb[3]), "+v"(fgb[4]), "+v"(fgb[5]),
+                              "+v"(gh[0]), "+v"(gh[1]), "+v"(gh[2]), "+v"(qp[0]), "+v"(qp[1]), "+v"(qp[2]));
+#pragma unroll
+            for (int j = 0; j < 3; ++j) E[j] = rcp64(Dv[j]);
             Lu3 lu;
             bad |= lu3_factor(Pa, 6, E, lu);
-            // lanes 0..35: entry (a, b), a >= b, of the SYMMETRIC stage matrix (packed like the stage blocks: lane = LS(a, b));
-            // lanes 36..43: entry a of its gradient, computed by the same expression: with f = (-ghat, 0) as the "column",
-            //   lall + [F G]' (q~ - P~ (ghat, 0)) = lall + [F G]' (P~ f + q~),   q~ = (M q_p, q_o - Pop E M q_p),
-            // i.e. q_p joins the right-hand sides of the two substitutions and q_o the second block -- no separate pass
-            const bool isg = lane >= 36;
-            const int a = isg ? (lane - 36) & 7 : (lane >= 28) ? 7 : (lane >= 21) ? 6 : (lane >= 15) ? 5 : (lane >= 10) ? 4 : (lane >= 6) ? 3 : (lane >= 3) ? 2 : (lane >= 1) ? 1 : 0;
-            const int b = isg ? 0 : lane - a * (a + 1) / 2;
-            const double gm = isg ? 1.0 : 0.0;
             double fb[6];
 #pragma unroll
-            for (int c = 0; c < 6; ++c) {
-                const double fgc = S.FG[8 * c + b];
-                fb[c] = isg ? (c < 3 ? -gh[c] : 0.0) : fgc;
-            }
+            for (int c = 0; c < 6; ++c) fb[c] = isg ? (c < 3 ? -gh[c] : 0.0) : fgb[c];
             double w3[3], t3[3], u3[3], yp[3], s2[3], yo[3];
 #pragma unroll
             for (int i = 0; i < 3; ++i) {
                 w3[i] = dot3(Pa[6 * i + 3], fb[3], Pa[6 * i + 4], fb[4], Pa[6 * i + 5], fb[5]);          // Ppo f_o
-                const double qi = gm * ql[i];
+                const double qi = gm * qp[i];
                 t3[i] = dot3(Pa[6 * i], fb[0], Pa[6 * i + 1], fb[1], Pa[6 * i + 2], fb[2]) + w3[i] + qi;
                 u3[i] = fma(Dv[i], fb[i], -w3[i]) - qi;
             }
             lu3_solve(lu, t3[0], t3[1], t3[2], yp[0], yp[1], yp[2]);
             lu3_solve(lu, u3[0], u3[1], u3[2], s2[0], s2[1], s2[2]);
+            // second batch: rows 3-5 of P, column a of [F G], q_o and the stage block's own entry (selected by address)
 #pragma unroll
             for (int i = 0; i < 18; ++i) Pb[i] = Pl[18 + i];
-            double fa[6];
+            double fa[6], qo[3];
 #pragma unroll
             for (int c = 0; c < 6; ++c) fa[c] = S.FG[8 * c + a];
 #pragma unroll
+            for (int i = 0; i < 3; ++i) qo[i] = ql[3 + i];
+            double v = *(isg ? S.lall + 8 * k + a : S.Lall + 36 * k + lane);
+            asm volatile("" : "+v"(fa[0]), "+v"(fa[1]), "+v"(fa[2]), "+v"(fa[3]), "+v"(fa[4]), "+v"(fa[5]),
+                              "+v"(qo[0]), "+v"(qo[1]), "+v"(qo[2]), "+v"(v));
+#pragma unroll
             for (int i = 0; i < 3; ++i)
                 yo[i] = dot3(Pb[6 * i + 3], fb[3], Pb[6 * i + 4], fb[4], Pb[6 * i + 5], fb[5]) +
-                        dot3(Pb[6 * i], E[0] * s2[0], Pb[6 * i + 1], E[1] * s2[1], Pb[6 * i + 2], E[2] * s2[2]) + gm * ql[3 + i];
-            double v = isg ? S.lall[8 * k + a] : S.Lall[36 * k + lane];
+                        dot3(Pb[6 * i], E[0] * s2[0], Pb[6 * i + 1], E[1] * s2[1], Pb[6 * i + 2], E[2] * s2[2]) + gm * qo[i];
 #pragma unroll
             for (int c = 0; c < 3; ++c) v = fma(fa[3 + c], yo[c], fma(fa[c], yp[c], v));
             if (lane < 36) S.Mall[lane] = v;
@@ -1302,31 +1328,36 @@ __device__ __forceinline__ int riccati(const Lay& L, const Sh& S, const Inst& in
         RSYNC();
         RPROF(13)
         // ---- phase B ----------------------------------------------------------------------------------
+        // One expression serves P_k = Mxx - Mxu Muu^-1 Mxu' (lanes 0..35: entry (a, b)) and q_k (lanes 36..41: entry a,
+        // with the gradient as the "column"): the ADDRESSES of the column's operands are selected, not the values.  Lanes
+        // 42..63 repeat q_k's entry 0 and store nothing.  The operands of the next stage's [F G] join the batch.
+        FgOps fo = fg_load(L, S, k > m ? k - 1 : k);
         if (NT == 64 || lane < 64) {
-        const double m00 = S.Mall[LS(6, 6)], m01 = S.Mall[LS(7, 6)], m11 = S.Mall[LS(7, 7)];
+        const bool isP = lane < 36, has = lane < 42;
+        const int a = isP ? lane / 6 : (has ? lane - 36 : 0), b = isP ? lane - 6 * (lane / 6) : 0;
+        double m00 = S.Mall[LS(6, 6)], m01 = S.Mall[LS(7, 6)], m11 = S.Mall[LS(7, 7)];
+        double xa0 = S.Mall[LS(6, a)], xa1 = S.Mall[LS(7, a)];
+        double y0 = *(isP ? S.Mall + LS(6, b) : S.mall + 6), y1 = *(isP ? S.Mall + LS(7, b) : S.mall + 7);
+        double base = *(isP ? S.Mall + LS(a, b) : S.mall + a);
+        asm volatile("" : "+v"(m00), "+v"(m01), "+v"(m11), "+v"(xa0), "+v"(xa1), "+v"(y0), "+v"(y1), "+v"(base),
+                          "+v"(fo.cs), "+v"(fo.sn), "+v"(fo.u0), "+v"(fo.u1));
         const double d1 = m11 - m01 * m01 * rcp64(m00);
         if (!(m00 > 0.0) || !(d1 > 0.0)) bad = 1;
         const double idet = rcp64(m00 * d1);
         const double i00 = m11 * idet, i01 = -m01 * idet, i11 = m00 * idet;
-        if (lane < 42) {
-            const int a = (lane < 36) ? lane / 6 : lane - 36, b = (lane < 36) ? lane - 6 * (lane / 6) : 0;
-            const double xa0 = S.Mall[LS(6, a)], xa1 = S.Mall[LS(7, a)];
-            if (lane < 36) {            // P_k = Mxx - Mxu Muu^-1 Mxu'
-                const double xb0 = S.Mall[LS(6, b)], xb1 = S.Mall[LS(7, b)];
-                const double kb0 = -(i00 * xb0 + i01 * xb1), kb1 = -(i01 * xb0 + i11 * xb1);
-                S.Pk[36 * k + lane] = S.Mall[LS(a, b)] + xa0 * kb0 + xa1 * kb1;
-                if (a == 0) { S.Kk[12 * k + b] = kb0; S.Kk[12 * k + 6 + b] = kb1; }      // K = -Muu^-1 Mxu'
-            } else {
-                const double k0 = -(i00 * S.mall[6] + i01 * S.mall[7]), k1 = -(i01 * S.mall[6] + i11 * S.mall[7]);
-                S.qk[6 * k + a] = S.mall[a] + xa0 * k0 + xa1 * k1;
-                if (a == 0) { S.kapk[2 * k] = k0; S.kapk[2 * k + 1] = k1; }
-            }
+        const double kb0 = -(i00 * y0 + i01 * y1), kb1 = -(i01 * y0 + i11 * y1);      // K = -Muu^-1 Mxu' (kappa: its gradient)
+        const double r = base + xa0 * kb0 + xa1 * kb1;
+        if (has) *(isP ? S.Pk + 36 * k + lane : S.qk + 6 * k + a) = r;
+        if (has && a == 0) {
+            double* kp = isP ? S.Kk + 12 * k + b : S.kapk + 2 * k;
+            kp[0] = kb0;
+            kp[isP ? 6 : 1] = kb1;
         }
         }
         if (k > m) {                        // phase A of this stage is over: its [F G] can make room for the next one
             // (with two wavefronts the second one writes it: it has no entry of P_k to compute)
             const int t = NT == 128 ? lane - 64 : lane;
-            if (t >= 0 && t < 48) S.FG[t] = fg_entry(L, S, in, xv, h, k - 1, t);
+            if (t >= 0 && t < 48) S.FG[t] = fg_select(L, in, fo, h, t);
         }
         RSYNC();
         RPROF(14)
@@ -1346,20 +1377,30 @@ __device__ __forceinline__ int riccati(const Lay& L, const Sh& S, const Inst& in
     // stage 0: du_{-1} = 0, elastic initial condition, then the time scale
     double E0[3], D0[3], g0[3];
 #pragma unroll
-    for (int j = 0; j < 3; ++j) { D0[j] = S.Es[L.r_init + j]; E0[j] = rcp64(D0[j]); g0[j] = S.gs[L.r_init + j]; }
+    for (int j = 0; j < 3; ++j) { D0[j] = S.Es[L.r_init + j]; E0[j] = 0.0; g0[j] = S.gs[L.r_init + j]; }     // (E0 = 1 / D0: below, behind the batch)
     Lu3 lu0;
     double s1[3] = {0.0, 0.0, 0.0}, X55 = 1.0, qt5 = 0.0;
     if (m == 0) {
     if (NT == 64 || lane < 64) {
-        const double* P0 = S.Pk;
-        const double* q0 = S.qk;
-        bad |= lu3_factor(P0, 6, E0, lu0);
+        double Pp[9], c5[3], qp[3], r5[3], p55 = S.Pk[35], q5 = S.qk[5];
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) Pp[3 * a + c] = S.Pk[6 * a + c];
+            c5[a] = S.Pk[6 * a + 5]; qp[a] = S.qk[a]; r5[a] = S.Pk[30 + a];
+        }
+        asm volatile("" : "+v"(Pp[0]), "+v"(Pp[1]), "+v"(Pp[2]), "+v"(Pp[3]), "+v"(Pp[4]), "+v"(Pp[5]), "+v"(Pp[6]), "+v"(Pp[7]), "+v"(Pp[8]),
+                          "+v"(c5[0]), "+v"(c5[1]), "+v"(c5[2]), "+v"(qp[0]), "+v"(qp[1]), "+v"(qp[2]), "+v"(r5[0]), "+v"(r5[1]), "+v"(r5[2]),
+                          "+v"(p55), "+v"(q5), "+v"(D0[0]), "+v"(D0[1]), "+v"(D0[2]), "+v"(g0[0]), "+v"(g0[1]), "+v"(g0[2]));
+#pragma unroll
+        for (int j = 0; j < 3; ++j) E0[j] = rcp64(D0[j]);
+        bad |= lu3_factor(Pp, 3, E0, lu0);
         // row / column T of P~: M Ppo e_T, and the (T, T) entry; q~_T
         double zq[3];
-        lu3_solve(lu0, P0[5], P0[11], P0[17], s1[0], s1[1], s1[2]);
-        lu3_solve(lu0, q0[0], q0[1], q0[2], zq[0], zq[1], zq[2]);
-        X55 = P0[35] - dot3(P0[30], E0[0] * s1[0], P0[31], E0[1] * s1[1], P0[32], E0[2] * s1[2]);
-        qt5 = q0[5] - dot3(P0[30], E0[0] * zq[0], P0[31], E0[1] * zq[1], P0[32], E0[2] * zq[2]);
+        lu3_solve(lu0, c5[0], c5[1], c5[2], s1[0], s1[1], s1[2]);
+        lu3_solve(lu0, qp[0], qp[1], qp[2], zq[0], zq[1], zq[2]);
+        X55 = p55 - dot3(r5[0], E0[0] * s1[0], r5[1], E0[1] * s1[1], r5[2], E0[2] * s1[2]);
+        qt5 = q5 - dot3(r5[0], E0[0] * zq[0], r5[1], E0[1] * zq[1], r5[2], E0[2] * zq[2]);
         if (L.free_T && !(X55 > 0.0)) bad = 1;
     }
     bad = red_or(bad);
@@ -1433,8 +1474,14 @@ __device__ __forceinline__ int riccati(const Lay& L, const Sh& S, const Inst& in
     if (m == 0) {
     if (L.free_T) dT = -(qt5 - dot3(s1[0], g0[0], s1[1], g0[1], s1[2], g0[2])) / X55;
     {
-        const double* P0 = S.Pk;
-        const double* q0 = S.qk;
+        double P0[18], q0[3];
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            P0[6 * a] = S.Pk[6 * a]; P0[6 * a + 1] = S.Pk[6 * a + 1]; P0[6 * a + 2] = S.Pk[6 * a + 2]; P0[6 * a + 5] = S.Pk[6 * a + 5];
+            q0[a] = S.qk[a];
+        }
+        asm volatile("" : "+v"(P0[0]), "+v"(P0[1]), "+v"(P0[2]), "+v"(P0[5]), "+v"(P0[6]), "+v"(P0[7]), "+v"(P0[8]), "+v"(P0[11]),
+                          "+v"(P0[12]), "+v"(P0[13]), "+v"(P0[14]), "+v"(P0[17]), "+v"(q0[0]), "+v"(q0[1]), "+v"(q0[2]));
         double t[3];
 #pragma unroll
         for (int a = 0; a < 3; ++a) t[a] = -g0[a] - E0[a] * (P0[6 * a + 5] * dT + q0[a]);
@@ -1469,6 +1516,9 @@ __device__ __forceinline__ int riccati(const Lay& L, const Sh& S, const Inst& in
         const double kap0 = S.kapk[2 * k], kap1 = S.kapk[2 * k + 1];
         const double cs = S.ct[k], sn = S.st[k];
         const double uk0 = S.uv[L.uvs * k + L.uvo], uk1 = S.uv[L.uvs * k + L.uvo + 1];
+        // (NOT pinned as a batch, unlike the phases of the backward sweep: 31 wide reads of operands that are the same on
+        // every lane keep the LDS busy for longer than one round trip takes, and the compiler's own order starts the
+        // arithmetic on the first ones meanwhile -- pinned, the headline launch took 8.01 instead of 7.92 ms)
         const double xi[6] = {dp[0], dp[1], dp[2], up[0], up[1], dT};
         double u[2] = {kap0, kap1};
 #pragma unroll
@@ -1511,9 +1561,21 @@ __device__ __forceinline__ int riccati(const Lay& L, const Sh& S, const Inst& in
         const int k = pr / L.nO, i = pr - k * L.nO;
         const int o0 = S.offm[i], m = S.offm[i + 1] - o0;
         const double* Yo = S.Y + (size_t)pr * (MW * 4);
-        const double* d = S.dx + L.ip(k);
+        const double* dk = S.dx + L.ip(k);
+        // the pair's whole block and its pose step first, as one batch (two asm statements: 30 operands each at most)
+        static_assert(MW == 10, "the batch below lists the 40 entries of a local block");
+        double Yv[4 * MW], d[3] = {dk[0], dk[1], dk[2]};
+#pragma unroll
+        for (int a = 0; a < 4 * MW; ++a) Yv[a] = Yo[a];
+        asm volatile("" : "+v"(Yv[0]), "+v"(Yv[1]), "+v"(Yv[2]), "+v"(Yv[3]), "+v"(Yv[4]), "+v"(Yv[5]), "+v"(Yv[6]), "+v"(Yv[7]),
+                          "+v"(Yv[8]), "+v"(Yv[9]), "+v"(Yv[10]), "+v"(Yv[11]), "+v"(Yv[12]), "+v"(Yv[13]), "+v"(Yv[14]), "+v"(Yv[15]),
+                          "+v"(Yv[16]), "+v"(Yv[17]), "+v"(Yv[18]), "+v"(Yv[19]), "+v"(d[0]), "+v"(d[1]), "+v"(d[2]));
+        asm volatile("" : "+v"(Yv[20]), "+v"(Yv[21]), "+v"(Yv[22]), "+v"(Yv[23]), "+v"(Yv[24]), "+v"(Yv[25]), "+v"(Yv[26]), "+v"(Yv[27]),
+                          "+v"(Yv[28]), "+v"(Yv[29]), "+v"(Yv[30]), "+v"(Yv[31]), "+v"(Yv[32]), "+v"(Yv[33]), "+v"(Yv[34]), "+v"(Yv[35]),
+                          "+v"(Yv[36]), "+v"(Yv[37]), "+v"(Yv[38]), "+v"(Yv[39]));
+#pragma unroll
         for (int a = 0; a < MW; ++a) {
-            const double v = Yo[4 * a + 3] - (Yo[4 * a] * d[0] + Yo[4 * a + 1] * d[1] + Yo[4 * a + 2] * d[2]);
+            const double v = Yv[4 * a + 3] - (Yv[4 * a] * d[0] + Yv[4 * a + 1] * d[1] + Yv[4 * a + 2] * d[2]);
             if (a < OBCA_MAX_EDGES) { if (a < m) S.dx[L.il(k) + o0 + a] = v; }
             else if (a < NW) S.dx[L.imu(k) + 4 * i + (a - OBCA_MAX_EDGES)] = v;
             else S.dnu[2 * pr + (a - NW)] = v;
