@@ -671,8 +671,95 @@ int obca_grid_pool(const uint8_t* grid /* [B,rows,cols] */, int32_t B, int32_t r
                    double* pool_A /* [B,K,4,2] */, double* pool_b /* [B,K,4] */, int32_t* rect /* [B,K,4] or NULL */,
                    int32_t* count /* [B] */, int32_t* ok /* [B] */, int32_t device, void* hip_stream);
 
+/* ------------------------------------------------------------------------------------------------------
+ * Closed loop over scene pools (obca_mpc 0.16), on the device: the harness between two solves of a receding-horizon loop
+ * whose world is a pool (obca_scene_select's: K <= 64 obstacles of E rows, optionally translating).  One step of the loop is
+ * three calls on one stream: obca_scene_select (the pool as it is now, the window and pose below, variant_out as its variant),
+ * obca_solve_batch (its rows), then this call with solved = 1.  It has no handle: the state is the caller's buffers, named by
+ * one descriptor.  csrc/obca_poolloop_core.h holds the serial definition the kernel reproduces word for word.
+ *
+ * solved = 1, for every rollout with flags[b] == OBCA_RUN (the others keep every word of state and history), kb = k[b]:
+ *   record    status_hist[b,kb] = status[b], iters_hist[b,kb] = iters[b], sel_hist[b,kb,:] = sel[b,:]
+ *   read      p1 = xopt[b,:,1], u = uopt[b,:,0], ts = ts_opt[b].  A status outside {0, 1}, a word of p1, u or ts that is not
+ *             finite, or ts <= 0: flags[b] = OBCA_DONE_FAILED and nothing else is written (the failed step counts in no
+ *             other history: obca_rollouts_step's rule)
+ *   measure   (n_sub > 0) c = the smallest signed distance between the car and ANY of the K obstacles over the applied
+ *             interval: obca_scene_select's samples (n_sub + 1 per interval, pose and rows interpolated) of the two-knot plan
+ *             [x0[b], p1] with Ts = ts, an obstacle with a velocity moving from its rows now to its rows ts later.  c NaN:
+ *             OBCA_DONE_FAILED, nothing else written; otherwise clear_hist[b,kb] = c
+ *   move      (pool_v given) pool_b[b,i,r] += ts * (A[r,0] v_x + A[r,1] v_y), the words of obca_scene_select's stage 1: the
+ *             pool accumulates the applied step lengths, it is not b0 + t_total (a . v)
+ *   advance   x0 = p1, u0 = u, x_closed[b,kb+1] = p1, u_closed[b,kb] = u, T_closed[b,kb] = ts, k[b] = kb + 1
+ *   flag      n_sub > 0 and c < clearance: OBCA_DONE_COLLISION (the colliding step stays in the history, as with
+ *             obca_rollouts_set_collision_stop); else kb + 1 == max_steps: OBCA_DONE_CAP; else the car within
+ *             sqrt(goal_tol2) of goal[b] (!(dx dx + dy dy >= goal_tol2), obca_rollouts_step's test with its 0.1):
+ *             OBCA_DONE_GOAL
+ * solved = 0 starts every rollout; the caller has put the start poses into x0 and the pools' rows into pool_b: k = 0, u0 = 0,
+ *   x_closed[b,0] = x0[b] and NaN beyond, u_closed, T_closed, status_hist, iters_hist 0, clear_hist +inf, sel_hist -1;
+ *   flags[b] = OBCA_DONE_FAILED for a pose that is not finite or a path_len[b] outside 1 .. path_max, else OBCA_DONE_GOAL
+ *   for a start at the goal, else OBCA_RUN.  The solve's pointers are not read and may be NULL.
+ * Then, always: for a rollout that is OBCA_RUN variant_out[b] = variant and xref_out[b] = the N + 1 path points from the one
+ *   nearest to the car on (the first strict minimum of the squared distance below 1e5 over path[b,:,0 .. path_len[b]-1],
+ *   point 0 when there is none; the last point repeated beyond the route's end: obca_rollouts_step's window); for every other
+ *   rollout variant_out[b] = 0 and every column of xref_out[b] is x0[b] (0 for a word that is not finite), so that the masked
+ *   launches downstream read numbers.  Nothing written is NaN except the fill of x_closed.
+ * B >= 1, 1 <= K <= 64, 1 <= E <= OBCA_MAX_EDGES, 1 <= N <= 127, path_max >= 1, 1 <= max_steps <= 1024, solved 0 or 1,
+ * variant 4, 6 or 8, 0 <= n_sub <= 256, 0 <= n_sel <= OBCA_MAX_OBST (n_sel >= 1 needs sel and sel_hist), clearance and ego
+ * finite (to measure without stopping pass a clearance no distance reaches, e.g. -1e300), goal_tol2 > 0 and finite,
+ * struct_size == sizeof(obca_pool_loop), device >= 0; every pointer not marked "or NULL" not NULL, the solve's only with
+ * solved = 1.  State the caller broke forms no address outside its buffers: a RUN rollout whose k[b] is outside
+ * 0 .. max_steps-1 ends OBCA_DONE_FAILED with nothing else written, and a path_len[b] outside 1 .. path_max is clamped to
+ * that range where the window reads the path (a start makes such a rollout OBCA_DONE_FAILED).  Words: the window search and
+ * the goal test round every product and sum on their own; the clearance is obca_scene_select's arithmetic as the library
+ * builds it (contracted products, the device's sin / cos), so clear_hist equals obca_scene_select's min_clear on the same
+ * device word for word and a host evaluation only where the arithmetic is exact.  Every argument is checked before the first HIP call; a refused call (OBCA_E_INVAL) has no side effect.
+ * Asynchronous on hip_stream. */
+typedef struct obca_pool_loop {
+    uint32_t struct_size;              /* sizeof(obca_pool_loop): set by obca_pool_loop_init() */
+    uint32_t reserved_;
+    int32_t B, K, E, N, n_sel, path_max, max_steps, variant, n_sub;
+    int32_t reserved2_;
+    double clearance, goal_tol2;       /* obca_pool_loop_init: -1e300 (never stops) and 0.1 */
+    double ego[4];                     /* obca_pool_loop_init: 1.7, 0.75, 1.7, 0.75 (obca_params.ego's default) */
+    /* read-only */
+    const double* pool_A;              /* [B,K,E,2] */
+    const double* pool_v;              /* [B,K,2] or NULL */
+    const double* goal;                /* [B,2] */
+    const double* path;                /* [B,3,path_max] */
+    const int32_t* path_len;           /* [B] */
+    /* the solve (solved = 1) */
+    const int32_t* status;             /* [B] */
+    const int32_t* iters;              /* [B] */
+    const double* ts_opt;              /* [B] */
+    const double* xopt;                /* [B,3,N+1] */
+    const double* uopt;                /* [B,2,N] */
+    const int32_t* sel;                /* [B,n_sel], or NULL with n_sel = 0 */
+    /* state, in and out */
+    double* x0;                        /* [B,3] */
+    double* u0;                        /* [B,2] */
+    double* pool_b;                    /* [B,K,E] */
+    int32_t* k;                        /* [B] */
+    int32_t* flags;                    /* [B] */
+    /* history, S = max_steps */
+    double* x_closed;                  /* [B,S+1,3] */
+    double* u_closed;                  /* [B,S,2] */
+    double* T_closed;                  /* [B,S] */
+    int32_t* status_hist;              /* [B,S] */
+    int32_t* iters_hist;               /* [B,S] */
+    double* clear_hist;                /* [B,S] */
+    int32_t* sel_hist;                 /* [B,S,n_sel], or NULL with n_sel = 0 */
+    /* outputs: the next solve's window and variant */
+    double* xref_out;                  /* [B,3,N+1] */
+    int32_t* variant_out;              /* [B] */
+} obca_pool_loop;
+
+/* zero-fills *d and sets struct_size, clearance, goal_tol2 and ego: the one way to start filling an obca_pool_loop */
+void obca_pool_loop_init(obca_pool_loop* d);
+int obca_pool_loop_advance(const obca_pool_loop* d, int32_t solved, int32_t device, void* hip_stream);
+
 const char* obca_strerror(int code);
-/* "obca_mpc 0.15 (gfx950)": 0.15 = occupancy grids to scene pools (obca_grid_pool);
+/* "obca_mpc 0.16 (gfx950)": 0.16 = closed loop over scene pools (obca_pool_loop_advance);
+ * 0.15 = occupancy grids to scene pools (obca_grid_pool);
  * 0.14 = scene pools (obca_scene_select);
  * 0.13 = route-seeded open-loop planning (obca_grid_dilate_batch, obca_route_resample);
  * 0.12 = the refinement step of the two-stage open-loop planner (obca_plan_refine);

@@ -52,6 +52,23 @@ class ObcaRolloutDims(ctypes.Structure):
                 ("max_steps", ctypes.c_int32), ("device", ctypes.c_int32), ("N_fix", ctypes.c_int32)]
 
 
+class ObcaPoolLoop(ctypes.Structure):
+    """obca_pool_loop (include/obca_mpc.h), the descriptor of obca_pool_loop_advance.  A new instance is what
+    obca_pool_loop_init leaves: all zero, struct_size set, clearance -1e300 (never stops), goal_tol2 0.1, the default ego."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("reserved_", ctypes.c_uint32)] + \
+               [(n, ctypes.c_int32) for n in ("B", "K", "E", "N", "n_sel", "path_max", "max_steps", "variant", "n_sub", "reserved2_")] + \
+               [("clearance", ctypes.c_double), ("goal_tol2", ctypes.c_double), ("ego", ctypes.c_double * 4)] + \
+               [(n, ctypes.c_void_p) for n in ("pool_A", "pool_v", "goal", "path", "path_len", "status", "iters", "ts_opt", "xopt", "uopt",
+                                               "sel", "x0", "u0", "pool_b", "k", "flags", "x_closed", "u_closed", "T_closed",
+                                               "status_hist", "iters_hist", "clear_hist", "sel_hist", "xref_out", "variant_out")]
+
+    def __init__(self, *a, **kw):
+        super().__init__(*a, **kw)
+        self.struct_size = ctypes.sizeof(ObcaPoolLoop)
+        self.clearance, self.goal_tol2 = -1e300, 0.1
+        self.ego = (ctypes.c_double * 4)(1.7, 0.75, 1.7, 0.75)
+
+
 EXPORTS = ("obca_create", "obca_destroy", "obca_solve_batch", "obca_lds_bytes", "obca_strerror", "obca_version", "obca_params_init",
            "obca_set_profile_buffer", "obca_set_mode", "obca_set_two_sided_sweep", "obca_rollouts_create", "obca_rollouts_destroy", "obca_rollouts_debug_stats", "obca_rollouts_debug_harness",
            "obca_rollouts_reset", "obca_rollouts_step", "obca_rollouts_read", "obca_rollouts_run",
@@ -59,7 +76,7 @@ EXPORTS = ("obca_create", "obca_destroy", "obca_solve_batch", "obca_lds_bytes", 
            "obca_rollouts_set_warm_start", "obca_dual_size", "obca_set_certificate_buffers", "obca_rasterise_batch",
            "obca_plan_clearance", "obca_plan_sweep", "obca_plan_tighten", "obca_rollouts_audit", "obca_rollouts_set_collision_stop", "obca_rollouts_set_exact_sensing",
            "obca_rollouts_read_clearance", "obca_rollouts_set_swept_rows", "obca_moving_rows_batch", "obca_plan_refine",
-           "obca_grid_dilate_batch", "obca_route_resample", "obca_scene_select", "obca_grid_pool")
+           "obca_grid_dilate_batch", "obca_route_resample", "obca_scene_select", "obca_grid_pool", "obca_pool_loop_init", "obca_pool_loop_advance")
 
 OBCA_MAX_DYN = 4
 RUN, DONE_GOAL, DONE_CAP, DONE_FAILED, DONE_COLLISION = 0, 1, 2, 3, 4
@@ -196,6 +213,10 @@ def load():
     lib.obca_scene_select.restype = ctypes.c_int
     lib.obca_grid_pool.argtypes = [vp] + [ctypes.c_int32] * 4 + [ctypes.c_double] * 3 + [vp, vp, i32p, i32p, i32p, ctypes.c_int32, vp]
     lib.obca_grid_pool.restype = ctypes.c_int
+    lib.obca_pool_loop_init.argtypes = [ctypes.POINTER(ObcaPoolLoop)]
+    lib.obca_pool_loop_init.restype = None
+    lib.obca_pool_loop_advance.argtypes = [ctypes.POINTER(ObcaPoolLoop), ctypes.c_int32, ctypes.c_int32, vp]
+    lib.obca_pool_loop_advance.restype = ctypes.c_int
     lib.obca_lds_bytes.argtypes = [ctypes.POINTER(ObcaDims)]
     lib.obca_lds_bytes.restype = ctypes.c_int64
     lib.obca_strerror.argtypes = [ctypes.c_int]

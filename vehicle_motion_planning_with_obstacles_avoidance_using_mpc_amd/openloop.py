@@ -92,13 +92,11 @@ def route_reference(path, path_len, N, start=None, goal=None, device=None):
     return xref, ok
 
 
-def route_references(grids, start_cells, goal_cells, N, start=None, goal=None, dilation=0, path_max=None, device=None):
-    """Map -> dilated map -> route -> reference for B worlds on the current stream, no host round trip: grids [B,rows,cols]
-    (non-zero = occupied), start_cells / goal_cells [B,2] as (row, col) -- ``planner.plan_batch``'s arguments --, start /
-    goal [B,3] the poses ``route_reference`` pins.  With dilation > 0 the search runs on ``planner.dilate_batch``'s grid AND on
-    the plain one; an instance takes the dilated route where that search found one (path_len >= 2) and the plain route
-    otherwise, chosen by ``torch.where`` on the device.  Returns (xref [B,3,N+1], ok [B] int32, source [B] int32): 2 = the
-    dilated route, 1 = the plain route, 0 = neither (``route_reference``'s fill)."""
+def route_search(grids, start_cells, goal_cells, dilation=0, path_max=None, device=None):
+    """The search of ``route_references`` alone: the route on ``planner.dilate_batch``'s grid where that search found one
+    (path_len >= 2), the route on the plain grid otherwise, chosen by ``torch.where`` on the device.  Returns device tensors
+    (path [B,3,path_max], path_len [B] int32 -- ``planner.plan_batch``'s, negative codes included -- and src [B] int32: 2 = the
+    dilated search's answer, 1 = the plain one's)."""
     import torch
     from .planner import dilate_batch, plan_batch
     if not isinstance(grids, torch.Tensor):                  # one upload for both searches
@@ -112,6 +110,18 @@ def route_references(grids, start_cells, goal_cells, N, start=None, goal=None, d
         use_d = plen_d >= 2
         path, plen = torch.where(use_d[:, None, None], path_d, path), torch.where(use_d, plen_d, plen)
         src = torch.where(use_d, 2, 1).to(torch.int32)
+    return path, plen, src
+
+
+def route_references(grids, start_cells, goal_cells, N, start=None, goal=None, dilation=0, path_max=None, device=None):
+    """Map -> dilated map -> route -> reference for B worlds on the current stream, no host round trip: grids [B,rows,cols]
+    (non-zero = occupied), start_cells / goal_cells [B,2] as (row, col) -- ``planner.plan_batch``'s arguments --, start /
+    goal [B,3] the poses ``route_reference`` pins.  With dilation > 0 the search runs on ``planner.dilate_batch``'s grid AND on
+    the plain one; an instance takes the dilated route where that search found one (path_len >= 2) and the plain route
+    otherwise, chosen by ``torch.where`` on the device (``route_search``).  Returns (xref [B,3,N+1], ok [B] int32, source [B]
+    int32): 2 = the dilated route, 1 = the plain route, 0 = neither (``route_reference``'s fill)."""
+    import torch
+    path, plen, src = route_search(grids, start_cells, goal_cells, dilation=dilation, path_max=path_max, device=device)
     xref, ok = route_reference(path, plen, N, start, goal, device=device)
     return xref, ok, torch.where(ok == 1, src, 0).to(torch.int32)
 

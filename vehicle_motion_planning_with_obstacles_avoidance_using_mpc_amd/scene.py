@@ -12,6 +12,14 @@ being called with other rows.
 every occupancy grid of a batch with disjoint axis-parallel rectangles, one pool obstacle each.  ``solve_maps`` composes it
 with ``openloop.route_references`` and ``solve_scene``: B maps and B start/goal pairs in, B plans out, each measured against
 its whole map.
+
+``PoolLoop`` is the receding-horizon version: B rollouts, each in a world that is a pool (static, or translating at constant
+velocities), driven by select -> solve -> obca_pool_loop_advance per step.  The advance call (arithmetic and serial definition
+in csrc/obca_poolloop_core.h) records the step, measures the applied interval against the WHOLE pool, moves the pool by the
+applied step length, advances the state, sets the flags and writes the next reference window from the route.  ``drive_maps``
+composes ``grid_pool``, ``openloop.route_search`` and ``PoolLoop``: B maps and B start/goal pairs in, B driven trajectories
+out.  Not here: the reference's 4 -> 6 -> 8 dispatch, its lidar gate and its fixed-time reference preparation
+(``rollouts.DeviceRollouts`` has those, for at most 8 static obstacles).
 """
 import ctypes
 
@@ -252,3 +260,179 @@ def solve_maps(solver, grids, start_cells, goal_cells, start, goal, Ts, K, pad=N
                                rounds=rounds, n_sub=n_sub, target=target, ego=ego)
     info.update(pool=pool, xref=xref, pool_ok=pool["ok"], source=source)
     return result, info
+
+
+NEVER_STOP = -1e300          # obca_pool_loop.clearance must be finite: below every distance a double can hold
+
+
+class PoolLoop:
+    """B closed-loop rollouts over scene pools on one GPU, the counterpart of ``rollouts.DeviceRollouts`` for worlds of up to 64
+    obstacles: ``reset()`` starts them, ``step()`` enqueues one receding-horizon step of every running rollout, ``run()`` all of
+    them, ``read()`` returns state and history.  Everything runs on the current stream without host synchronisation.
+
+    pool_A [B,K,E,2], pool_b [B,K,E] (the pool at the start; the loop moves its own copy), pool_v [B,K,2] or None; start [B,3],
+    goal [B,2] (or [B,3] poses); path [B,3,path_max] and path_len [B] the routes to follow (``planner.plan_batch``'s outputs; a
+    path_len outside 1 .. path_max starts the rollout FAILED); ``solver`` a ``BatchSolver`` with m == [E] * n_sel.
+    variant: 4 (free time; default without pool_v) or 8 (fixed time; default with pool_v); 6 is refused, there is no terminal
+    set here.  Ts [B] or a float is constant over the rollout: for variant 4 the reference's base step (the applied duration
+    is the solve's ts_opt), for 8 the step itself -- choose it to fit the route's spacing.
+    One step: ``select`` (n_sub = select_n_sub) of the pool as it is now around the window and the pose, the solve
+    (rounds = 0: ``solver.solve`` on the selected rows; rounds >= 1: ``solve_scene``, whose held plan is applied), then
+    obca_pool_loop_advance: the applied interval is measured against the whole pool at n_sub + 1 samples (n_sub = 0: not
+    measured) and a rollout whose interval comes closer than ``clearance`` ends with flag "collision" (clearance=None:
+    measured, never stopped -- the C call wants a finite threshold and gets -1e300).  A rollout whose pool or poses ``select``
+    cannot use is masked and ends FAILED with status -5."""
+
+    def __init__(self, solver, pool_A, pool_b, start, goal, path, path_len, Ts, pool_v=None, variant=None, params=None,
+                 max_steps=30, rounds=0, select_n_sub=1, n_sub=8, clearance=None, goal_tol2=0.1, ego=DEFAULT_EGO):
+        import torch
+        if not torch.cuda.is_available():
+            raise RuntimeError("scene.PoolLoop needs a ROCm GPU; there is no CPU fallback on the product path")
+        self.torch, self.lib, self.solver = torch, _lib.load(), solver
+        dev = self.device = solver.device
+        f64 = lambda a: torch.as_tensor(a, dtype=torch.float64, device=dev).contiguous()
+        self.pool_A, self.pool_b0 = f64(pool_A), f64(pool_b)
+        if self.pool_A.dim() != 4 or self.pool_b0.dim() != 3 or tuple(self.pool_A.shape) != tuple(self.pool_b0.shape) + (2,):
+            raise ValueError("expected pool_A [B,K,E,2], pool_b [B,K,E]")
+        B, K, E = (int(v) for v in self.pool_b0.shape)
+        self.B, self.K, self.E, self.N, self.n_sel = B, K, E, solver.N, len(solver.m)
+        if solver.m != [E] * self.n_sel or self.n_sel > K or self.n_sel < 1:
+            raise ValueError("solver.m = %s does not fit a pool of %d obstacles of %d rows: expected [%d] * n_sel, n_sel <= %d" %
+                             (solver.m, K, E, E, K))
+        self.pool_v = None if pool_v is None else solver._dev(pool_v, (B, K, 2))
+        self.variant = int((4 if pool_v is None else 8) if variant is None else variant)
+        if self.variant not in (4, 8):
+            raise ValueError("variant %d: the closed loop over pools runs obca_mpc4 (4) or obca_mpc8 (8); there is no terminal set "
+                             "for 6" % self.variant)
+        self.start = solver._dev(start, (B, 3))
+        goal = f64(goal)
+        if goal.dim() != 2 or goal.shape[0] != B or goal.shape[1] not in (2, 3):
+            raise ValueError("expected goal [B,2] or [B,3], got %s" % (tuple(goal.shape),))
+        self.goal = goal[:, :2].contiguous()
+        self.path = f64(path)
+        if self.path.dim() != 3 or self.path.shape[0] != B or self.path.shape[1] != 3 or self.path.shape[2] < 1:
+            raise ValueError("expected path [B,3,path_max], got %s" % (tuple(self.path.shape),))
+        self.path_len = solver._dev(path_len, (B,), torch.int32)
+        Ts = torch.as_tensor(Ts, dtype=torch.float64, device=dev)
+        self.Ts = solver._dev(Ts.expand(B) if Ts.dim() == 0 else Ts, (B,))
+        self.params = params or SolverParams()
+        self._cparams = self.params.to_c() if isinstance(self.params, SolverParams) else self.params
+        self.max_steps, self.rounds, self.select_n_sub, self.n_sub = int(max_steps), int(rounds), int(select_n_sub), int(n_sub)
+        self.clearance = NEVER_STOP if clearance is None else float(clearance)
+        self.goal_tol2, self.ego = float(goal_tol2), tuple(float(v) for v in ego)
+        S, N, n_sel = self.max_steps, self.N, self.n_sel
+        f = lambda *shape: torch.zeros(*shape, dtype=torch.float64, device=dev)
+        i = lambda *shape: torch.zeros(*shape, dtype=torch.int32, device=dev)
+        self.x0, self.u0, self.pool_b, self.k, self.flags = f(B, 3), f(B, 2), f(B, K, E), i(B), i(B)
+        self.hist = {"x_closed": f(B, S + 1, 3), "u_closed": f(B, S, 2), "T_closed": f(B, S), "status": i(B, S), "iters": i(B, S),
+                     "clear": f(B, S), "sel": i(B, S, n_sel)}
+        self.xref, self.variant_out = f(B, 3, N + 1), i(B)
+        self.term = f(B, 3)
+        self._held = None                                    # the solve's outputs, allocated by the first solve
+        self._last = (None, None)                            # (result, selection) of the last step
+        d = self._desc = _lib.ObcaPoolLoop()
+        d.B, d.K, d.E, d.N, d.n_sel, d.path_max, d.max_steps = B, K, E, N, n_sel, int(self.path.shape[2]), S
+        d.variant, d.n_sub, d.clearance, d.goal_tol2 = self.variant, self.n_sub, self.clearance, self.goal_tol2
+        d.ego = (ctypes.c_double * 4)(*self.ego)
+        a = lambda t: None if t is None else t.data_ptr()
+        for name, t in (("pool_A", self.pool_A), ("pool_v", self.pool_v), ("goal", self.goal), ("path", self.path),
+                        ("path_len", self.path_len), ("x0", self.x0), ("u0", self.u0), ("pool_b", self.pool_b), ("k", self.k),
+                        ("flags", self.flags), ("x_closed", self.hist["x_closed"]), ("u_closed", self.hist["u_closed"]),
+                        ("T_closed", self.hist["T_closed"]), ("status_hist", self.hist["status"]), ("iters_hist", self.hist["iters"]),
+                        ("clear_hist", self.hist["clear"]), ("sel_hist", self.hist["sel"]), ("xref_out", self.xref),
+                        ("variant_out", self.variant_out)):
+            setattr(d, name, a(t))
+        self.steps_enqueued = 0
+        self.reset()
+
+    def _tensors(self):
+        own = [self.pool_A, self.pool_b0, self.pool_v, self.start, self.goal, self.path, self.path_len, self.Ts, self.x0, self.u0,
+               self.pool_b, self.k, self.flags, self.xref, self.variant_out, self.term] + list(self.hist.values())
+        r, sel = self._last                                  # the last solve's outputs: the descriptor still points at them
+        if r is not None:
+            own += [r.xopt, r.uopt, r.ts_opt, r.status, r.iters, r.info, sel]
+        return [t for t in own if t is not None]
+
+    def _on_stream(self):
+        """the launches are asynchronous: every tensor they touch is recorded on the stream they run on (see ``select``)"""
+        s = self.torch.cuda.current_stream(self.device)
+        for t in self._tensors():
+            t.record_stream(s)
+
+    def _advance(self, solved):
+        _lib.check(self.lib.obca_pool_loop_advance(ctypes.byref(self._desc), int(solved), _lib.device_index(self.device),
+                                                   _lib.stream_ptr(self.device)))
+
+    def reset(self):
+        self._on_stream()
+        self.x0.copy_(self.start)
+        self.pool_b.copy_(self.pool_b0)
+        self._advance(0)
+        self.steps_enqueued = 0
+
+    def _step(self):
+        torch, solver, d = self.torch, self.solver, self._desc
+        if self.rounds == 0:
+            s = select(self.pool_A, self.pool_b, self.xref, self.n_sel, pool_v=self.pool_v, Ts=self.Ts, x0=self.x0,
+                       variant=self.variant_out, n_sub=self.select_n_sub, ego=self.ego, device=self.device)
+            var = torch.where(s["ok"] != 0, self.variant_out, 0).to(torch.int32)
+            self._held = solver.solve(var, self.x0, self.u0, self.xref, s["A"], s["b"], self.Ts, self.term, self._cparams,
+                                      out=self._held)
+            r, sel = self._held, s["sel"]
+        else:
+            r, info = solve_scene(solver, self.variant_out, self.x0, self.u0, self.xref, self.pool_A, self.pool_b, self.Ts,
+                                  pool_v=self.pool_v, term=self.term, params=self._cparams, rounds=self.rounds,
+                                  n_sub=max(self.n_sub, 1), ego=self.ego)
+            sel = info["sel"]
+        self._last = (r, sel)                                # alive until the next step replaces them
+        for name, t in (("status", r.status), ("iters", r.iters), ("ts_opt", r.ts_opt), ("xopt", r.xopt), ("uopt", r.uopt),
+                        ("sel", sel)):
+            setattr(d, name, t.data_ptr())
+        self._advance(1)
+        self.steps_enqueued += 1
+
+    def step(self):
+        self._on_stream()
+        self._step()
+
+    def run(self, n_steps=None):
+        self._on_stream()
+        for _ in range(self.max_steps if n_steps is None else int(n_steps)):
+            self._step()
+        return self
+
+    def read(self):
+        """copies, as device tensors on the current stream: x_closed [B,S+1,3] (NaN beyond the driven knots), u_closed [B,S,2],
+        T_closed [B,S], status / iters [B,S], clear [B,S] (+inf where no interval was measured), sel [B,S,n_sel] (-1 where no
+        step was solved), steps [B], flags [B], pool_b [B,K,E] (the pool now), x0 [B,3], min_clear [B] (the smallest measured
+        interval)"""
+        out = {k: v.clone() for k, v in self.hist.items()}
+        out.update(steps=self.k.clone(), flags=self.flags.clone(), pool_b=self.pool_b.clone(), x0=self.x0.clone(),
+                   min_clear=self.hist["clear"].min(dim=1).values)
+        return out
+
+
+def drive_maps(solver, grids, start_cells, goal_cells, start, goal, Ts, K, pad=None, far=100.0, dilation=1, path_max=None, **loop):
+    """B occupancy grids and B start/goal pairs -> B driven trajectories, each measured against its whole map, on the current
+    stream without host synchronisation: ``grid_pool(grids, K, pad=pad, far=far)`` gives the pools,
+    ``openloop.route_search(grids, start_cells, goal_cells, dilation=dilation)`` the routes (the dilated map's where it has
+    one, else the plain map's), ``PoolLoop(solver, pool_A, pool_b, start, goal, path, path_len, Ts, **loop).run()`` drives
+    them.  Arguments as ``solve_maps``; ``loop`` are ``PoolLoop``'s keyword arguments.  Resolution 1 only.
+
+    An instance whose pool is incomplete (grid_pool's ok == 0) or that has no route (path_len < 1) is masked on the device --
+    its path_len becomes 0, so it starts FAILED and is never solved -- and reported, never raised on.  Returns (loop, info):
+    the ``PoolLoop`` after its run (``loop.read()`` gives the histories) and a dict of device tensors: pool (grid_pool's dict),
+    path, path_len (as driven: 0 where masked), pool_ok [B] and source [B] (2 = the dilated route, 1 = the plain route,
+    0 = none)."""
+    import torch
+    from .openloop import route_search
+    dev = solver.device
+    if not isinstance(grids, torch.Tensor):                  # one upload for the cover and both searches
+        import numpy as np
+        grids = torch.as_tensor(np.ascontiguousarray(grids), device=dev)
+    pool = grid_pool(grids, K, resolution=1.0, pad=pad, far=far, device=dev)
+    path, plen, src = route_search(grids, start_cells, goal_cells, dilation=dilation, path_max=path_max, device=dev)
+    source = torch.where(plen >= 1, src, 0).to(torch.int32)
+    plen = torch.where((pool["ok"] != 0) & (source != 0), plen, 0).to(torch.int32)
+    lp = PoolLoop(solver, pool["pool_A"], pool["pool_b"], start, goal, path, plen, Ts, **loop).run()
+    return lp, {"pool": pool, "path": path, "path_len": plen, "pool_ok": pool["ok"], "source": source}
