@@ -51,7 +51,10 @@ typedef struct obca_params {
                                           obca_params_init() (or by hand after zero-initialising).  Anything else -- a caller built
                                           against another layout, a struct that was never initialised -- is answered with
                                           OBCA_E_INVAL instead of being read field by field as something it is not          */
-    uint32_t reserved_;                /* 0                                                        */
+    uint32_t time_bound;               /* [OBCA_TIME_BOUND_REFERENCE] one of the OBCA_TIME_BOUND_* constants below: how variant 4
+                                          bounds its time scale (the word that was `reserved_`, documented as 0, until obca_mpc 0.16:
+                                          size and every offset are unchanged, and the zeroed struct of an older caller means the
+                                          reference's bound); anything else: OBCA_E_INVAL             */
     obca_weights free_time;            /* used by variant 4 (closed_loop.py:77-81)                */
     obca_weights fixed_time;           /* used by variants 6 and 8 (closed_loop.py:94-98)         */
     double xL[2], xU[2];               /* position box (theta is unbounded, obca.py:916)          */
@@ -140,6 +143,24 @@ enum {
     OBCA_START_ZEROS_FIRST = 2,        /* zeros -> window -> x0: the reference's literal start first (the default of
                                           obca_mpc 0.1)                                            */
     OBCA_START_X0_FIRST = 3            /* x0 -> window -> zeros for every variant (the default of obca_mpc 0.2 / 0.3; obca_mpc4's until 0.4) */
+};
+
+/* obca_params.time_bound: the upper bound Tmax of obca_mpc4's time scale T (the step length is T * Ts; OBCA_T_MIN <= T <= Tmax),
+   Tmax = dis / (N * uU[0] * Ts) + 1 with `dis` the distance the window asks the car to cover.  Only variant 4 reads it: the
+   fixed-time variants have no time scale. */
+enum {
+    OBCA_TIME_BOUND_REFERENCE = 0,     /* the reference's: dis = (xref_N.x - x0.x) + (xref_N.y - x0.y), a SIGNED sum (src/obca.py;
+                                          SURVEY.md quirk q3).  A window that runs towards smaller x or smaller y gets a bound
+                                          below what the car needs -- below 1, even below OBCA_T_MIN -- and the problem is
+                                          infeasible by construction.  The default: every output word is the one obca_mpc 0.16
+                                          returned. */
+    OBCA_TIME_BOUND_PATH = 1           /* dis = sum_{k=1..N} (|px_k - px_{k-1}| + |py_k - py_{k-1}|), p_0 = x0[:2], p_k = xref[:2,k]:
+                                          the L1 arc length of the window, summed in the order k = 1 .. N from 0.0, each term
+                                          (|dx| + |dy|) formed first.  The arc length and not the distance of the end points: a
+                                          window round a box turns back, and the end points understate the route.  L1 and not
+                                          Euclidean: it is the reference's own formula read without a direction -- the same word
+                                          wherever the window is monotone in x and in y and the sums are exact, never below the
+                                          reference's value up to rounding, and Tmax never below 1. */
 };
 
 
@@ -758,7 +779,8 @@ void obca_pool_loop_init(obca_pool_loop* d);
 int obca_pool_loop_advance(const obca_pool_loop* d, int32_t solved, int32_t device, void* hip_stream);
 
 const char* obca_strerror(int code);
-/* "obca_mpc 0.16 (gfx950)": 0.16 = closed loop over scene pools (obca_pool_loop_advance);
+/* "obca_mpc 0.17 (gfx950)": 0.17 = opt-in path time bound of obca_mpc4 (obca_params.time_bound, OBCA_TIME_BOUND_PATH);
+ * 0.16 = closed loop over scene pools (obca_pool_loop_advance);
  * 0.15 = occupancy grids to scene pools (obca_grid_pool);
  * 0.14 = scene pools (obca_scene_select);
  * 0.13 = route-seeded open-loop planning (obca_grid_dilate_batch, obca_route_resample);

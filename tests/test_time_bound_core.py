@@ -1,0 +1,384 @@
+"""CPU tier of ``obca_params.time_bound`` (include/obca_mpc.h: OBCA_TIME_BOUND_*): ``obca_time_bound`` (csrc/obca_device.h)
+against a numpy restatement word for word, and the host core (csrc/obca_lpi_core.h through tests/native/time_bound_host.cpp)
+in both modes -- mode 0 against the exerciser that has no mode (``native_build.lpi_solve``), mode 1 against the dense numpy
+oracle with ``p.Tmax`` overwritten by the restatement, on windows that run towards smaller y, on a window whose answer sits on
+the bound, and as the solver of the host pool loop of tests/test_gpu_pool_loop.py.  The worlds and helpers of this module are
+the ones tests/test_gpu_time_bound.py runs on the device."""
+import ctypes
+import functools
+import math
+import os
+
+import numpy as np
+import pytest
+
+from oracle import c_oracle, ipm_dense
+from oracle.obca_nlp import Problem
+from tests import native_build
+from tests import test_pool_loop_core as core
+from tests import test_scene_core as scene_core
+from vehicle_motion_planning_with_obstacles_avoidance_using_mpc_amd import scenarios as sc
+
+REFERENCE, PATH = 0, 1
+N, TS, UU0 = 5, 0.1, 0.6
+TOL_POSE, TOL_TS = 1e-5, 1e-6       # tests/test_lpi_core_cpu.py: host core against a dense solver whose iterates differ by roundoff
+TOL_MIRROR = 1e-9                   # tests/test_lpi_core_cpu.py: TOL_SAME_PATH -- a problem and its reflection are the same problem but for
+                                    # the rounding of 10 - y (1.8e-15): the same iterates, the bound of two such runs
+TOL_ON_BOUND = 1e-9                 # |ts_opt - Tmax Ts| of an answer held on the bound (the dense oracle: 2e-11)
+E_INVAL = -22
+SRC = os.path.join(native_build.HERE, "native", "time_bound_host.cpp")
+DEPS = [SRC, os.path.join(native_build.CSRC, "obca_lpi_core.h"), os.path.join(native_build.CSRC, "obca_device.h"),
+        os.path.join(native_build.ROOT, "include", "obca_mpc.h")]
+DESCENDING_SEEDS = [2, 6, 8, 9]     # loop_world(seed, 0) whose first window runs towards smaller y
+LEFT_OUT_SEEDS = [2, 6, 8, 9, 11, 12, 13, 14]     # tests/test_gpu_pool_loop.py: the seeds POOL_SEEDS leaves out
+
+
+@functools.lru_cache(maxsize=None)
+def load_host():
+    lib = native_build.build_shim("time_bound_host", [SRC], DEPS, openmp=True)
+    lib.time_bound_host_tmax.restype = ctypes.c_double
+    lib.time_bound_host_tmax.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_double]
+    lib.time_bound_host_resolve.restype = ctypes.c_int
+    lib.time_bound_host_resolve.argtypes = [ctypes.c_uint]
+    lib.time_bound_host_solve_batch.restype = ctypes.c_int
+    return lib
+
+
+@pytest.fixture(scope="module")
+def host():
+    return load_host()
+
+
+# ------------------------------------------------------------------------------------------------ the rule, in numpy
+def np_tmax(mode, x0, xref, uU0=UU0, Ts=TS):
+    """include/obca_mpc.h: OBCA_TIME_BOUND_* in Python floats (IEEE doubles, every operation rounded on its own)"""
+    n = xref.shape[1] - 1
+    if mode == REFERENCE:
+        dis = (float(xref[0, n]) - float(x0[0])) + (float(xref[1, n]) - float(x0[1]))
+    else:
+        dis, px, py = 0.0, float(x0[0]), float(x0[1])
+        for k in range(1, n + 1):
+            qx, qy = float(xref[0, k]), float(xref[1, k])
+            dis = dis + (abs(qx - px) + abs(qy - py))
+            px, py = qx, qy
+    return dis / (n * uU0 * Ts) + 1.0
+
+
+def host_tmax(mode, x0, xref, uU0=UU0, Ts=TS):
+    x0, xref = np.ascontiguousarray(x0, float), np.ascontiguousarray(xref, float)
+    return load_host().time_bound_host_tmax(mode, xref.shape[1] - 1, x0.ctypes.data, xref.ctypes.data, xref.shape[1], uU0, Ts)
+
+
+def host_solve(time_bound, n, m, x0, u0, xref, A, b, Ts=TS, variant=4, params=None, rc=0, out=None):
+    """the host core with ``time_bound`` resolved as the library resolves it; arrays as in include/obca_mpc.h"""
+    lib = load_host()
+    x0 = np.ascontiguousarray(x0, float)
+    B, M = x0.shape[0], int(sum(m))
+    var = np.ascontiguousarray(np.broadcast_to(np.asarray(variant, np.int32), (B,)))
+    term = np.zeros((B, 3))
+    params = params or c_oracle.default_params()
+    out = out or dict(xopt=np.zeros((B, 3, n + 1)), uopt=np.zeros((B, 2, n)), ts_opt=np.zeros(B), status=np.zeros(B, np.int32),
+                      iters=np.zeros(B, np.int32), info=np.zeros((B, 4)))
+    arrs = [x0, np.ascontiguousarray(u0, float), np.ascontiguousarray(xref, float).reshape(B, 3, n + 1),
+            np.ascontiguousarray(np.broadcast_to(np.asarray(A, float), (B, n + 1, M, 2))),
+            np.ascontiguousarray(np.broadcast_to(np.asarray(b, float), (B, n + 1, M))),
+            np.ascontiguousarray(np.broadcast_to(np.asarray(Ts, float), (B,)))]
+    p = native_build._ptr
+    got = lib.time_bound_host_solve_batch(n, len(m), (ctypes.c_int * len(m))(*[int(v) for v in m]), p(var), B, *[p(a) for a in arrs], p(term),
+                                          ctypes.byref(params), ctypes.c_uint(time_bound), *[p(out[k]) for k in ("xopt", "uopt", "ts_opt", "status", "iters", "info")])
+    assert got == rc, got
+    return out
+
+
+def dense_solve(mode, q):
+    """the dense numpy oracle on instance ``q`` (a dict as ``instances`` returns, one instance), its Tmax overwritten by the rule"""
+    e3, e2 = np.eye(3), np.eye(2)
+    n = q["xref"].shape[1] - 1
+    M = len(q["b"])
+    p = Problem(4, n, q["m"], q["x0"], q["u0"], q["xref"], np.broadcast_to(q["A"], (n + 1, M, 2)), np.broadcast_to(q["b"], (n + 1, M)), TS,
+                0.1 * e3, 0.01 * e2, 0.1 * e2, 0.1 * e3, sc.XL, sc.XU, [-0.6, -math.pi / 6], [0.6, math.pi / 6], sc.EGO, sc.DMIN)
+    p.Tmax = np_tmax(mode, q["x0"], q["xref"])
+    return ipm_dense.solve(p)
+
+
+# ------------------------------------------------------------------------------------------------ worlds
+def reflect(q):
+    """``q`` mirrored in the corridor's axis y = 5: y -> 10 - y, theta -> -theta, the steering input's sign, the rows' y column"""
+    r = dict(q)
+    r["x0"] = np.array([q["x0"][0], 10.0 - q["x0"][1], -q["x0"][2]])
+    r["u0"] = np.array([q["u0"][0], -q["u0"][1]])
+    r["xref"] = np.stack([q["xref"][0], 10.0 - q["xref"][1], -q["xref"][2]])
+    r["A"] = q["A"] * np.array([1.0, -1.0])
+    r["b"] = q["b"] - 10.0 * q["A"][:, 1]
+    return r
+
+
+def reflect_plan(o):
+    """what the reflection makes of a solve's outputs (xopt [...,3,N+1], uopt [...,2,N])"""
+    x, u = o["xopt"].copy(), o["uopt"].copy()
+    x[..., 1, :] = 10.0 - x[..., 1, :]
+    x[..., 2, :] = -x[..., 2, :]
+    u[..., 1, :] = -u[..., 1, :]
+    return x, u
+
+
+@functools.lru_cache(maxsize=None)
+def corridor_instances():
+    """``scenarios.make_instance(0..5)`` (m = [1, 4, 1]), then their six reflections"""
+    qs = [sc.make_instance(i, N) for i in range(6)]
+    return qs + [reflect(q) for q in qs]
+
+
+def loop_world(seed, n_distract=0):
+    from tests import test_gpu_pool_loop as pl          # (the worlds only: nothing of that module touches a device on import)
+    return pl.loop_world(seed, n_distract)
+
+
+@functools.lru_cache(maxsize=None)
+def descending_instances():
+    """the first window of ``loop_world(seed, 0)``, seeds DESCENDING_SEEDS: the car on the route's first point, u0 = 0, m = [4, 4, 4]"""
+    out = []
+    for s in DESCENDING_SEEDS:
+        w = loop_world(s)
+        out.append(dict(x0=w["start"].copy(), u0=np.zeros(2), xref=sc.window(w["path"], w["start"], N), A=w["pool_A"].reshape(12, 2),
+                        b=w["pool_b"].reshape(12), m=[4, 4, 4]))
+    return out
+
+
+def batch(qs):
+    n = qs[0]["xref"].shape[1] - 1
+    return dict(m=qs[0]["m"], x0=np.stack([q["x0"] for q in qs]), u0=np.stack([q["u0"] for q in qs]), xref=np.stack([q["xref"] for q in qs]),
+                A=np.stack([np.broadcast_to(q["A"], (n + 1,) + q["A"].shape) for q in qs]).copy(),
+                b=np.stack([np.broadcast_to(q["b"], (n + 1,) + q["b"].shape) for q in qs]).copy())
+
+
+def solve_batch_host(mode, bt):
+    return host_solve(mode, bt["xref"].shape[2] - 1, bt["m"], bt["x0"], bt["u0"], bt["xref"], bt["A"], bt["b"])
+
+
+def zigzag(n=N, theta_N=math.pi / 2):
+    """a window that goes to and fro between x = 10 and 10.125 and between y = 5 and 4.875 (dyadic: every sum below is exact) and asks
+    for a quarter turn at its end: the signed sum and the end points see 0.125 m, the arc length 0.125 + 0.25 (n - 1) m.  The
+    quarter turn cannot be made in the time either bound allows, so the held answer (status 2) sits on the bound.  Rows:
+    ``make_instance(0)``'s"""
+    q = sc.make_instance(0, N)
+    k = np.arange(n + 1)
+    xref = np.stack([10.0 + 0.125 * (k % 2), 5.0 - 0.125 * ((k >= 2) & (k % 2 == 0)), np.zeros(n + 1)])
+    xref[2, n] = theta_N
+    return dict(x0=np.array([10.0, 5.0, 0.0]), u0=np.zeros(2), xref=xref, A=q["A"], b=q["b"], m=q["m"])
+
+
+# ------------------------------------------------------------------------------------------------ 1. the function
+def windows(n, rng):
+    """name -> (x0 [3], xref [3, n+1]) with steps that are no dyadic numbers"""
+    step = rng.uniform(0.05, 1.0, (2, n + 1))
+    x0 = rng.uniform(3.0, 8.0, 3)
+    mono = x0[:2, None] + np.cumsum(step, axis=1)
+    zig = x0[:2, None] + step * np.where(np.arange(n + 1) % 2 == 0, 1.0, -1.0)
+    desc = x0[:2, None] - np.cumsum(step, axis=1)
+    mixed = np.stack([mono[0], desc[1]])
+    th = rng.uniform(-1.0, 1.0, (1, n + 1))
+    return {name: (x0, np.concatenate([xy, th])) for name, xy in (("monotone", mono), ("zigzag", zig), ("descending", desc), ("mixed", mixed))}
+
+
+@pytest.mark.parametrize("n", (1, 5, 20, 127))
+def test_obca_time_bound_is_the_numpy_rule_word_for_word(host, n):
+    rng = np.random.default_rng(170 + n)
+    for name, (x0, xref) in windows(n, rng).items():
+        for mode in (REFERENCE, PATH):
+            for uU0, Ts in ((UU0, TS), (0.37, 0.013)):
+                got, ref = host_tmax(mode, x0, xref, uU0, Ts), np_tmax(mode, x0, xref, uU0, Ts)
+                assert core.same_words(np.float64(got), np.float64(ref)), (name, mode, got, ref)
+        ref0, ref1 = np_tmax(REFERENCE, x0, xref), np_tmax(PATH, x0, xref)
+        assert ref1 >= 1.0 and ref1 >= ref0 - 1e-12 * abs(ref0), name            # never below 1, never below the reference's
+        if name == "descending":
+            assert ref0 < 1.0
+    # the reference's formula by hand, and a stride that is not n + 1
+    x0, xref = windows(n, rng)["mixed"]
+    assert host_tmax(REFERENCE, x0, xref) == ((xref[0, n] - x0[0]) + (xref[1, n] - x0[1])) / (n * UU0 * TS) + 1.0
+    wide = np.full((3, n + 9), np.nan)
+    wide[:, :n + 1] = xref
+    for mode in (REFERENCE, PATH):
+        assert load_host().time_bound_host_tmax(mode, n, x0.ctypes.data, wide.ctypes.data, n + 9, UU0, TS) == np_tmax(mode, x0, xref)
+
+
+@pytest.mark.parametrize("n", (1, 5, 20, 127))
+def test_both_bounds_are_one_word_on_a_monotone_window_with_exact_sums(host, n):
+    k = np.arange(n + 1)
+    x0 = np.array([3.25, 2.5, 0.0])
+    xref = np.stack([3.5 + 0.25 * k, 2.5 + 0.125 * (k // 2), np.zeros(n + 1)])
+    a, b = host_tmax(REFERENCE, x0, xref), host_tmax(PATH, x0, xref)
+    assert a == b and a == np_tmax(REFERENCE, x0, xref) and a > 1.0
+
+
+def test_resolution_and_refusals(host):
+    assert host.time_bound_host_resolve(0) == 0 and host.time_bound_host_resolve(1) == 0
+    for bad in (2, 3, 0x7fffffff, 0x80000000, 0xffffffff):
+        assert host.time_bound_host_resolve(bad) == E_INVAL
+    bt = batch(corridor_instances()[:2])
+    out = dict(xopt=np.full((2, 3, N + 1), 7.5), uopt=np.full((2, 2, N), 7.5), ts_opt=np.full(2, 7.5), status=np.full(2, 77, np.int32),
+               iters=np.full(2, 77, np.int32), info=np.full((2, 4), 7.5))
+    for bad in (2, 0xffffffff):
+        host_solve(bad, N, bt["m"], bt["x0"], bt["u0"], bt["xref"], bt["A"], bt["b"], rc=E_INVAL, out=out)
+    assert all(np.all(v == (77 if v.dtype == np.int32 else 7.5)) for v in out.values())
+
+
+# ------------------------------------------------------------------------------------------------ 2. the host core
+def test_mode_0_is_the_host_core_as_it_was():
+    bt = batch(corridor_instances()[:6])
+    got = solve_batch_host(REFERENCE, bt)
+    ref = native_build.lpi_solve(4, N, bt["m"], bt["x0"], bt["u0"], bt["xref"], bt["A"], bt["b"], TS)
+    for k in ref:
+        assert core.same_words(got[k], ref[k]), k
+    assert np.all(np.isin(got["status"], (0, 1)))
+
+
+def the_ten():
+    return descending_instances() + corridor_instances()[6:]
+
+
+@functools.lru_cache(maxsize=None)
+def host_answers(mode):
+    """the host core on the four descending first windows, the six reflected instances and the six originals, in that order"""
+    return [solve_batch_host(mode, batch(descending_instances())), solve_batch_host(mode, batch(corridor_instances()[6:])),
+            solve_batch_host(mode, batch(corridor_instances()[:6]))]
+
+
+def test_windows_towards_smaller_y_are_infeasible_under_the_reference_bound():
+    desc, refl, _ = host_answers(REFERENCE)
+    assert desc["status"].tolist() == [2] * 4 and refl["status"].tolist() == [2] * 6
+    for q in the_ten():
+        assert np_tmax(REFERENCE, q["x0"], q["xref"]) < np_tmax(PATH, q["x0"], q["xref"])
+
+
+def test_windows_towards_smaller_y_are_solved_under_the_path_bound_as_the_dense_oracle_solves_them():
+    desc, refl, _ = host_answers(PATH)
+    worst = [0.0, 0.0]
+    for got, qs in ((desc, descending_instances()), (refl, corridor_instances()[6:])):
+        assert np.all(np.isin(got["status"], (0, 1))), got["status"]
+        for i, q in enumerate(qs):
+            r = dense_solve(PATH, q)
+            assert r.status in (0, 1)
+            dx, dt = float(np.max(np.abs(got["xopt"][i] - r.xopt))), abs(float(got["ts_opt"][i]) - r.Ts_opt)
+            print("instance %d: iterations %d (dense %d), |x - dense| %.2e, |ts - dense| %.2e" % (i, got["iters"][i], r.iters, dx, dt))
+            worst = [max(worst[0], dx), max(worst[1], dt)]
+            assert dx < TOL_POSE and dt < TOL_TS, (i, dx, dt)
+            assert got["ts_opt"][i] <= np_tmax(PATH, q["x0"], q["xref"]) * TS * (1 + 1e-12)
+    print("largest |host - dense|: poses %.2e, ts_opt %.2e" % tuple(worst))
+
+
+def test_mirror_relation_under_the_path_bound():
+    _, refl, orig = host_answers(PATH)
+    assert np.array_equal(refl["status"], orig["status"]) and np.all(np.isin(orig["status"], (0, 1)))
+    x, u = reflect_plan(refl)
+    d = max(float(np.max(np.abs(x - orig["xopt"]))), float(np.max(np.abs(u - orig["uopt"]))), float(np.max(np.abs(refl["ts_opt"] - orig["ts_opt"]))))
+    print("iterations %s / mirrored %s, largest difference %.2e" % (orig["iters"].tolist(), refl["iters"].tolist(), d))
+    assert d < TOL_MIRROR
+    # and on a monotone window the path bound is the reference's: the originals are solved under either
+    ref0 = host_answers(REFERENCE)[2]
+    assert np.array_equal(ref0["status"], orig["status"])
+
+
+def test_the_bound_is_visible_where_the_answer_sits_on_it():
+    q = zigzag()
+    assert abs(np_tmax(REFERENCE, q["x0"], q["xref"]) - (0.125 / 0.3 + 1.0)) < 1e-12 and abs(np_tmax(PATH, q["x0"], q["xref"]) - 4.75) < 1e-12
+    for mode, ts in ((REFERENCE, 0.425 / 3.0), (PATH, 0.475)):
+        got = solve_batch_host(mode, batch([q]))
+        print("mode %d: status %d, ts_opt %.12f" % (mode, got["status"][0], got["ts_opt"][0]))
+        assert got["status"][0] == 2 and abs(got["ts_opt"][0] - ts) < TOL_ON_BOUND
+    # without the quarter turn the window is feasible, with one optimum under either bound
+    flat = [solve_batch_host(mode, batch([zigzag(theta_N=0.0)])) for mode in (REFERENCE, PATH)]
+    assert flat[0]["status"][0] in (0, 1) and flat[1]["status"][0] in (0, 1)
+    assert abs(flat[0]["ts_opt"][0] - flat[1]["ts_opt"][0]) < TOL_TS and np.max(np.abs(flat[0]["xopt"] - flat[1]["xopt"])) < TOL_POSE
+
+
+# N -> (under the reference's bound, under the path bound): is the answer to zigzag(N) held on the bound -- status 2, ts_opt = Tmax Ts?
+# At N = 20 under the path bound (Tmax Ts = 0.50625) twenty steps are time enough for the quarter turn and the solve ends feasible
+# (ts_opt = 0.170820393895, 27 iterations).  tests/test_gpu_time_bound.py reads this table.
+ZIGZAG_ON_BOUND = {1: (True, True), 5: (True, True), 20: (True, False)}
+
+
+@pytest.mark.parametrize("n", (1, 5, 20))
+def test_zigzag_table_is_what_the_dense_oracle_says(n):
+    """the dense numpy oracle, with ``p.Tmax`` from the rule, on every entry but one: N = 20 under the reference's bound takes it 369
+    iterations of a 1114-row dense factorisation (a minute; measured once: status 2, ts_opt 0.089583333316 = Tmax Ts to 2e-11), so
+    that entry is held by the host core here"""
+    q = zigzag(n)
+    for mode in (REFERENCE, PATH):
+        bound = np_tmax(mode, q["x0"], q["xref"]) * TS
+        if (n, mode) == (20, REFERENCE):
+            h = solve_batch_host(mode, batch([q]))
+            status, ts = int(h["status"][0]), float(h["ts_opt"][0])
+        else:
+            r = dense_solve(mode, q)
+            status, ts = int(r.status), float(r.Ts_opt)
+        print("N %d mode %d: status %d ts_opt %.12f, Tmax Ts %.12f" % (n, mode, status, ts, bound))
+        if ZIGZAG_ON_BOUND[n][mode]:
+            assert status == 2 and abs(ts - bound) < TOL_ON_BOUND
+        else:
+            assert status == 0 and ts < bound - 0.1
+    assert np_tmax(REFERENCE, zigzag(1)["x0"], zigzag(1)["xref"]) == np_tmax(PATH, zigzag(1)["x0"], zigzag(1)["xref"])     # a one-term sum
+
+
+# ------------------------------------------------------------------------------------------------ 3. the host pool loop
+def host_step(scene_host, w, x0, u0, xref, variant, pool_b, mode, n_sel=3):
+    """tests/test_gpu_pool_loop.py: host_step with the host core in ``mode``"""
+    B = len(x0)
+    s = scene_core.host_select(scene_host, w["pool_A"], pool_b, xref, n_sel, x0=x0, variant=variant, n_sub=1)
+    o = dict(xopt=np.zeros((B, 3, N + 1)), uopt=np.zeros((B, 2, N)), ts_opt=np.zeros(B), status=np.full(B, -5, np.int32),
+             iters=np.zeros(B, np.int32))
+    on = (variant != 0) & (s["ok"] == 1)
+    if on.any():
+        r = host_solve(mode, N, [4] * n_sel, x0[on], u0[on], xref[on], s["A"][on], s["b"][on])
+        for k in o:
+            o[k][on] = r[k]
+    return s, o, on
+
+
+def host_loop(loop_host, scene_host, w, mode, K, n_sel=3, steps=12, route_points=12, goal_tol2=1.0):
+    """tests/test_gpu_pool_loop.py: host_loop with the host core in ``mode``; returns (case, feasible_everywhere [B], solves, iterations)"""
+    B = len(w["start"])
+    c = core.Case(B, K, 4, N, n_sel, route_points, steps, n_sub=8, goal_tol2=goal_tol2)
+    for k in ("pool_A", "pool_b", "goal", "path", "path_len"):
+        c[k][...] = w[k]
+    c["x0"][...] = w["start"]
+    core.advance(loop_host, c, 0)
+    ok, iters = np.ones(B, bool), []
+    for _ in range(steps):
+        s, o, on = host_step(scene_host, w, c["x0"].copy(), c["u0"].copy(), c["xref_out"].copy(), c["variant_out"].copy(), c["pool_b"].copy(), mode, n_sel)
+        ok &= ~on | np.isin(o["status"], (0, 1))
+        iters += o["iters"][on].tolist()
+        for k in ("xopt", "uopt", "ts_opt", "status", "iters"):
+            c[k][...] = o[k]
+        c["sel"][...] = s["sel"]
+        core.advance(loop_host, c, 1)
+    return c, ok, iters
+
+
+def test_host_pool_loop_reaches_every_goal_under_the_path_bound():
+    """the host loop of tests/test_gpu_pool_loop.py (K = 16, n_sel = 3, 12 steps, ``loop_world(seed, 13)``, seeds 0 .. 15): under the
+    reference's bound the eight POOL_SEEDS are feasible; under the path bound every solve of all sixteen is, and every rollout
+    ends at its goal (as with the dense oracle as the solver: 112 solves, all GOAL at step 7)"""
+    from tests import test_gpu_pool_loop as pl
+    w = pl.loop_worlds(list(range(16)), pl.K_POOL - 3)
+    c, ok, iters = host_loop(core.load_host(), scene_core.load_host(), w, PATH, pl.K_POOL)
+    print("solves %d, iterations mean %.1f max %d, steps %s flags %s" % (len(iters), np.mean(iters), max(iters), c["k"].tolist(), c["flags"].tolist()))
+    assert ok.all(), np.flatnonzero(~ok).tolist()
+    assert np.all(c["flags"] == core.GOAL), c["flags"].tolist()
+    c0, ok0, _ = host_loop(core.load_host(), scene_core.load_host(), w, REFERENCE, pl.K_POOL)
+    assert [s for s in range(16) if ok0[s]] == pl.POOL_SEEDS and np.all(c0["flags"][LEFT_OUT_SEEDS] == core.FAILED) and np.all(c0["k"][LEFT_OUT_SEEDS] == 0)
+
+
+# ------------------------------------------------------------------------------------------------ 4. Python
+def test_solver_params_carry_the_bound():
+    from vehicle_motion_planning_with_obstacles_avoidance_using_mpc_amd import _lib
+    from vehicle_motion_planning_with_obstacles_avoidance_using_mpc_amd.solver import SolverParams
+    assert _lib.TIME_BOUNDS == {"reference": 0, "path": 1}
+    assert SolverParams().to_c().time_bound == 0 and SolverParams(time_bound="reference").to_c().time_bound == 0
+    assert SolverParams(time_bound="path").to_c().time_bound == 1 and SolverParams(time_bound=1).time_bound == 1
+    for bad in ("arc", "Path", 2, -1, None):
+        with pytest.raises(ValueError):
+            SolverParams(time_bound=bad)
+    p = SolverParams(time_bound="path").to_c()
+    assert _lib.ObcaParams.time_bound.offset == 4 and _lib.ObcaParams.time_bound.size == 4
+    assert bytes(p)[4:8] == (1).to_bytes(4, "little")

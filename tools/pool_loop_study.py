@@ -1,11 +1,12 @@
 """The closed loop over scene pools (scene.PoolLoop, scene.drive_maps) measured: where a step's time goes, closed-loop steps
 per second from maps, and the same rollouts through the closed loop that existed (rollouts.DeviceRollouts).
 
-    python tools/pool_loop_study.py [--worlds 4096] [--small 64] [--steps 40] [--out profiles/FILE.json]
+    python tools/pool_loop_study.py [--worlds 4096] [--small 64] [--steps 40] [--time-bound reference|path] [--out profiles/FILE.json]
 
 Worlds: tools/grid_pool_study.py's -- 11 x 40 maps, rows 0 and 10 occupied, two boxes; start cell (5, 3), goal cell (5, 38),
 start pose (3, 5, 0), goal (38, 5).  N = 5, obca_mpc4, Ts = 0.1, K = 16, n_sel = 4, dilation 1, measured intervals at
-n_sub = 8, never stopped, max_steps = --steps.  Per batch size (--worlds, and --small to see the launch-bound end):
+n_sub = 8, never stopped, max_steps = --steps, the free-time problem's time bound --time-bound (include/obca_mpc.h:
+time_bound; "reference" is the signed sum under which a route that descends is infeasible).  Per batch size (--worlds, and --small to see the launch-bound end):
   step_ms           one step split into select / solve / advance by HIP events on the stream (the three public calls of
                     PoolLoop's step, issued by this tool between events): median over the steps after one untimed step,
                     and the share of rollouts still running at the median step
@@ -91,7 +92,7 @@ def study(B, a):
     from vehicle_motion_planning_with_obstacles_avoidance_using_mpc_amd.rollouts import DeviceRollouts, PackedWorlds
     from vehicle_motion_planning_with_obstacles_avoidance_using_mpc_amd.solver import BatchSolver, SolverParams
     g, sc, gc, start, goal = inputs(B, a.seed)
-    params = SolverParams(xL=(0.0, 0.0), xU=(39.0, 10.0))
+    params = SolverParams(xL=(0.0, 0.0), xU=(39.0, 10.0), time_bound=a.time_bound)
     kw = dict(variant=4, params=params, max_steps=a.steps, n_sub=N_SUB)
     solver = BatchSolver(N, [4] * N_SEL, B)
     out = {"B": B}
@@ -154,12 +155,13 @@ def main():
     ap.add_argument("--small", type=int, default=64)
     ap.add_argument("--steps", type=int, default=40)
     ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--time-bound", choices=("reference", "path"), default="reference")
     ap.add_argument("--seed", type=int, default=17)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     import torch
     doc = {"how": "see the tool's docstring; ms: HIP events", "device": torch.cuda.get_device_name(0), "N": N, "K": K, "n_sel": N_SEL,
-           "n_sub": N_SUB, "steps": a.steps, "repeats": a.repeats, "seed": a.seed, "batches": []}
+           "n_sub": N_SUB, "steps": a.steps, "time_bound": a.time_bound, "repeats": a.repeats, "seed": a.seed, "batches": []}
     for B in (a.worlds, a.small):
         if B > 0:
             doc["batches"].append(study(B, a))

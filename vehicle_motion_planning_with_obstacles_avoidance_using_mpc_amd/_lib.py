@@ -26,7 +26,7 @@ class ObcaWeights(ctypes.Structure):
 class ObcaParams(ctypes.Structure):
     """obca_params (include/obca_mpc.h).  A new instance is what obca_params_init leaves: all zero (= every default),
     struct_size set."""
-    _fields_ = [("struct_size", ctypes.c_uint32), ("reserved_", ctypes.c_uint32),
+    _fields_ = [("struct_size", ctypes.c_uint32), ("time_bound", ctypes.c_uint32),
                 ("free_time", ObcaWeights), ("fixed_time", ObcaWeights),
                 ("xL", ctypes.c_double * 2), ("xU", ctypes.c_double * 2),
                 ("uL", ctypes.c_double * 2), ("uU", ctypes.c_double * 2),
@@ -44,6 +44,9 @@ class ObcaParams(ctypes.Structure):
 # obca_params.start_order (include/obca_mpc.h)
 START_DEFAULT, START_WINDOW_FIRST, START_ZEROS_FIRST, START_X0_FIRST = 0, 1, 2, 3
 START_ORDERS = {"default": START_DEFAULT, "x0": START_X0_FIRST, "window": START_WINDOW_FIRST, "zeros": START_ZEROS_FIRST}
+# obca_params.time_bound (include/obca_mpc.h): obca_mpc4's bound on its time scale -- the reference's signed sum, or the window's L1 arc length
+TIME_BOUND_REFERENCE, TIME_BOUND_PATH = 0, 1
+TIME_BOUNDS = {"reference": TIME_BOUND_REFERENCE, "path": TIME_BOUND_PATH}
 
 
 class ObcaRolloutDims(ctypes.Structure):

@@ -287,6 +287,7 @@ class BatchClosedLoop:
         self._BatchSolver, self._SolverParams = BatchSolver, SolverParams
         self.rollouts = list(rollouts)
         self.start_order = (params_kw or {}).get("start_order", 0)           # include/obca_mpc.h: start_order
+        self.time_bound = (params_kw or {}).get("time_bound", "reference")  # include/obca_mpc.h: time_bound
         self.solvers = {}
         self.steps_solved = 0
         self.steps_converged = 0
@@ -308,6 +309,7 @@ class BatchClosedLoop:
         free = calls[0][1] == 4
         kw = dict(xL=a0[6], xU=a0[7], uL=a0[8], uU=a0[9], ego=a0[16], dmin=a0[15])
         kw["start_order"] = self.start_order
+        kw["time_bound"] = self.time_bound
         kw["single_start"] = calls[0][1] == 6   # obca_mpc8 follows a failed obca_mpc6 (step()): the first start only
         prm = self._SolverParams(Q_free=a0[2], R_free=a0[3], P_free=a0[1], **kw) if free else \
             self._SolverParams(Q_fix=a0[2], R_fix=a0[3], P_fix=a0[1], **kw)

@@ -244,6 +244,7 @@ int obca_internal_fill_launch(obca_handle* h, const int32_t* variant, int32_t B,
     L.prm.opt.max_iter_fixed = p->max_iter_fixed > 0 ? p->max_iter_fixed : 1000;
     L.prm.opt.max_soc = p->max_soc == 0 ? OBCA_MAX_SOC : (p->max_soc < 0 ? 0 : p->max_soc);
     if (!obca_resolve_starts(&L.prm.opt, p->start_order, p->single_start, p->patience, p->retry_iter, h->dims.N, p->dodge, p->terminal_screen)) return OBCA_E_INVAL;
+    if (!obca_resolve_time_bound(&L.prm.opt, p->time_bound)) return OBCA_E_INVAL;
     if (lds_bytes) *lds_bytes = h->cap.lds_bytes;
     if (wave_ok) *wave_ok = sel::wave_offered(h->cap, h->refused) ? 1 : 0;
     return OBCA_OK;
@@ -311,7 +312,7 @@ extern "C" const char* obca_strerror(int code) {
     }
 }
 
-extern "C" const char* obca_version(void) { return "obca_mpc 0.16 (gfx950)"; }
+extern "C" const char* obca_version(void) { return "obca_mpc 0.17 (gfx950)"; }
 extern "C" void obca_params_init(obca_params* p) {
     if (!p) return;
     memset(p, 0, sizeof(*p));

@@ -221,8 +221,9 @@ constexpr int obca_soc_lds_mw(int N, int nO, int M) {            /* four-wavefro
 #define OBCA_MW_SHAPES(X) X(20, 3, 6) X(20, 5, 14)
 
 struct ObcaWeightsDev { double Q[9], P[9], R1[4], R2[4]; };
-/* order: obca_params.start_order (validated); nstarts: 1 (single_start) or 3; patience / retry_iter: resolved (> 0) */
-struct ObcaOptsDev { double tol, rho, feas_tol; int32_t max_iter_free, max_iter_fixed, max_soc, order, nstarts, patience, retry_iter, dodge, screen, pad_; };
+/* order: obca_params.start_order (validated); nstarts: 1 (single_start) or 3; patience / retry_iter: resolved (> 0);
+   time_bound: obca_params.time_bound (validated: obca_resolve_time_bound), in the word that was padding */
+struct ObcaOptsDev { double tol, rho, feas_tol; int32_t max_iter_free, max_iter_fixed, max_soc, order, nstarts, patience, retry_iter, dodge, screen, time_bound; };
 /* the start fields of obca_params -> their resolved form; false: start_order / single_start outside its range.  dodge /
    terminal_screen follow the zero-initialisation rule of obca_params: 0 = the default (on), negative = off */
 static inline bool obca_resolve_starts(ObcaOptsDev* o, int start_order, int single_start, int patience, int retry_iter, int N, int dodge = 0, int terminal_screen = 0) {
@@ -233,8 +234,37 @@ static inline bool obca_resolve_starts(ObcaOptsDev* o, int start_order, int sing
     o->retry_iter = retry_iter > 0 ? retry_iter : OBCA_RETRY_ITER(N);
     o->dodge = dodge >= 0 ? 1 : 0;
     o->screen = terminal_screen >= 0 ? 1 : 0;
-    o->pad_ = 0;
+    o->time_bound = OBCA_TIME_BOUND_REFERENCE;
     return true;
+}
+/* obca_params.time_bound -> its resolved form, after obca_resolve_starts (which leaves the reference's bound); false: outside
+   its range */
+static inline bool obca_resolve_time_bound(ObcaOptsDev* o, uint32_t time_bound) {
+    if (time_bound != OBCA_TIME_BOUND_REFERENCE && time_bound != OBCA_TIME_BOUND_PATH) return false;
+    o->time_bound = (int32_t)time_bound;
+    return true;
+}
+/* Upper bound Tmax of obca_mpc4's time scale (include/obca_mpc.h: OBCA_TIME_BOUND_*) from the pose x0 and the window xref
+   (x at xref[k], y at xref[stride + k], k = 0 .. N): the one definition behind every kernel and the host core.  No product
+   feeds a sum here, so the words do not depend on contraction. */
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+static inline double obca_time_bound(int mode, int N, const double* x0, const double* xref, int stride, double uU0, double Ts) {
+    double dis;
+    if (mode == OBCA_TIME_BOUND_PATH) {
+        double px = x0[0], py = x0[1];
+        dis = 0.0;
+#pragma unroll 1
+        for (int k = 1; k <= N; ++k) {
+            const double qx = xref[k], qy = xref[stride + k];
+            dis += fabs(qx - px) + fabs(qy - py);
+            px = qx; py = qy;
+        }
+    } else {
+        dis = (xref[N] - x0[0]) + (xref[stride + N] - x0[1]);       // signed sum (q3)
+    }
+    return dis / (N * uU0 * Ts) + 1.0;
 }
 /* Closed-form screen of obca_mpc6 (rule and derivation: oracle/ipm_dense.py:terminal_set_shortfall): by how much no trajectory
    the rows allow can reach the terminal set's x_N >= termx -- the heading of the first step is x0's, the speeds are bounded by

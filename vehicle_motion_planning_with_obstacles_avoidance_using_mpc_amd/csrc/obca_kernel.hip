@@ -1590,6 +1590,11 @@ __device__ __forceinline__ int riccati(const Lay& L, const Sh& S, const Inst& in
 // by differences clipped to their box, free-time problem (iT >= 0): the time scale at which the window is driven at
 // OBCA_WINDOW_SPEED_FRAC of the speed bound; lambda = mu = 0 (x is zero on entry).  Rare, one lane, out of line with scalar
 // arguments only: inlined into the body it cost the four-wavefront kernels 400 B of scratch.
+// obca_time_bound (csrc/obca_device.h) for a bound other than the reference's, out of line like the start points below: the
+// body gains a test and a call, not the loop
+__device__ __noinline__ void other_time_bound(Inst* inp, const double* xref, int mode, int N) {
+    inp->Tmax = obca_time_bound(mode, N, inp->x0, xref, N + 1, inp->uU[0], inp->Ts);
+}
 __device__ __noinline__ void window_start_point(double* x, const double* xref, const Inst* inp, int N, int NS, int iT) {
     const Inst& in = *inp;
     const int N1 = N + 1;
@@ -1924,9 +1929,9 @@ __device__ __forceinline__ void obca_ipm_body(DESC& Ain, const int inst, const b
             S.bobs[t] = bg[(size_t)(L.variant == 4 ? 0 : k) * L.M + q];
         }
         SYNC();
-        const double dis = (S.xref[0 * N1 + L.N] - in.x0[0]) + (S.xref[1 * N1 + L.N] - in.x0[1]);   // signed sum (q3)
+        // (in.Tmax, obca_mpc4's bound on its time scale, is NOT formed here: the pass drivers write it once per instance, before the
+        // first pass -- terminal_screen_dev's tmax, below -- and nothing else writes that word, so it holds for every pass of the ladder)
         if (lane == 0) {
-            in.Tmax = dis / (L.N * in.uU[0] * in.Ts) + 1.0;
             // (every thread read the ladder's state before the barriers above)
             ladder_state[0] = escalated | held_bits; ladder_state[3] = start_s;
             if (first) { ladder_state[1] = 0; ladder_state[2] = 0; }
@@ -2607,7 +2612,12 @@ __device__ __forceinline__ void obca_ipm_body(DESC& Ain, const int inst, const b
 // entered.  Out of line and outside the body on purpose: inside the body's prologue the same forty lines cost the headline kernel
 // 85 more scratch loads (the allocator's choices for the whole solve changed).  // Returns 1: screened out; 2: not screened, but with less than OBCA_DODGE_MIN_SPARE of reach beyond the terminal set -- the ladder's
 // dodge rung is not tried (the drivers stop after the order's starts); 0: nothing to say.
-__device__ __noinline__ int terminal_screen_dev(const ObcaLaunch* a, int inst, int lane, int nt) {
+// tmax: obca_mpc4's bound on its time scale (csrc/obca_device.h: obca_time_bound, whichever obca_params.time_bound asks for) goes to
+// *tmax -- the Tmax word of the instance data in LDS -- once per instance, from the caller's arrays: the body reads it in every pass
+// of the ladder and carries neither the sum nor the test of the mode.  NULL: not wanted (the closed loop's fixed-time groups).
+__device__ __noinline__ int terminal_screen_dev(const ObcaLaunch* a, int inst, int lane, int nt, double* tmax) {
+    if (tmax != nullptr && lane == 0 && inst < a->B && a->variant[inst] == 4)
+        *tmax = obca_time_bound(a->prm.opt.time_bound, a->N, a->x0 + (size_t)inst * 3, a->xref + (size_t)inst * 3 * (a->N + 1), a->N + 1, a->prm.uU[0], a->Ts[inst]);
     if (inst >= a->B || a->term == nullptr || a->variant[inst] != 6) return 0;
     const double* x0s = a->x0 + (size_t)inst * 3;
     const double ts = a->Ts[inst];
@@ -2655,7 +2665,9 @@ __device__ __forceinline__ void solve_passes(DESC& A, DESC& A2, DESC& A3) {
     // (every kernel's first argument is the launch descriptor: its address is the kernarg segment's)
     __shared__ int drv_scr;           // what the screen said (kept in LDS: nothing of it may occupy a register during the solves)
     {
-        const int scr = terminal_screen_dev((const ObcaLaunch*)__builtin_amdgcn_kernarg_segment_ptr(), inst, threadIdx.x, blockDim.x);
+        extern __shared__ __attribute__((aligned(16))) double smem[];
+        const int scr = terminal_screen_dev((const ObcaLaunch*)__builtin_amdgcn_kernarg_segment_ptr(), inst, threadIdx.x, blockDim.x,
+                                            &reinterpret_cast<Inst*>(smem + A.inst_off)->Tmax);
         if (scr == 1) return;
         if (threadIdx.x == 0) drv_scr = scr;
     }
@@ -2759,7 +2771,7 @@ __device__ __noinline__ void ro_finish(const rollout::Dev* D, int b) { rollout::
 // (C5 with the stop off: 2.6 x the HBM writes, +2 % time); out of line it costs only its own frame (callee-saved
 // registers), which is touched only when the stop is on.
 __device__ __noinline__ void ro_stop(const rollout::Dev* D, int b) { rollout::stop_check_wave(*D, b); }
-__device__ __noinline__ int ro_screen(const ObcaLaunch* L, int b) { return terminal_screen_dev(L, b, 0, 1); }
+__device__ __noinline__ int ro_screen(const ObcaLaunch* L, int b, double* tmax) { return terminal_screen_dev(L, b, 0, 1, tmax); }
 __device__ __noinline__ int ro_retry(const rollout::Dev* D, int g, int b) { rollout::make_retry(*D, g, b); return D->var8[g][b]; }
 // (flag in the low half, group in the high half: an out-parameter would be a stack slot, i.e. scratch)
 __device__ __noinline__ long long ro_flag_sel(const rollout::Dev* D, int b) { return ((long long)D->sel[b] << 32) | (unsigned)D->flags[b]; }
@@ -2807,8 +2819,13 @@ __device__ __forceinline__ void ro_solve_step(const rollout::Dev& D, const ObcaL
             }
             Lp = launches + g + rollout::MAX_GROUPS;
         }
+        if (attempt == 0 && g == 0) {     // obca_mpc4: its time bound, once per step (terminal_screen_dev; the barrier orders it before the body's reads)
+            extern __shared__ __attribute__((aligned(16))) double smem[];
+            if (lane == 0) (void)ro_screen(Lp, b, &reinterpret_cast<Inst*>(smem + Lp->inst_off)->Tmax);
+            __syncthreads();
+        }
         if (attempt == 0 && g > 0) {      // obca_mpc6 that cannot reach its terminal set: answered by lane 0, on to obca_mpc8's turn
-            if (lane == 0) ro_msg[0] = ro_screen(Lp, b);
+            if (lane == 0) ro_msg[0] = ro_screen(Lp, b, nullptr);
             __syncthreads();
             const int scr = ro_msg[0];
             __syncthreads();

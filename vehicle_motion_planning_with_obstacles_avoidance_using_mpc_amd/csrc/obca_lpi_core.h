@@ -1521,8 +1521,7 @@ LPI_FN void run_instance(const ObcaLaunch& A, double* ws, size_t stride, size_t 
         for (int q = 0; q < 2 * L.M; ++q) S.Aobs[k * 2 * L.M + q] = Ag[(size_t)ks * L.M * 2 + q];
         for (int q = 0; q < L.M; ++q) S.bobs[k * L.M + q] = bg[(size_t)ks * L.M + q];
     }
-    const double dis = (S.xref[0 * N1 + L.N] - in.x0[0]) + (S.xref[1 * N1 + L.N] - in.x0[1]);
-    in.Tmax = dis / (L.N * in.uU[0] * in.Ts) + 1.0;
+    in.Tmax = obca_time_bound(A.prm.opt.time_bound, L.N, in.x0, xr, N1, in.uU[0], in.Ts);
     const bool warm = A.warm_z != nullptr && (A.warm_use == nullptr || A.warm_use[inst] != 0);
     // obca_mpc6 whose terminal set no trajectory can reach (csrc/obca_device.h: obca_terminal_shortfall) is not run
     double shortfall = -INFINITY;

@@ -198,7 +198,8 @@ extern "C" int obca_rollouts_reset(obca_rollouts* r, const double* start, const 
     {
         ObcaOptsDev probe;
         if (params->struct_size != (uint32_t)sizeof(obca_params) ||
-            !obca_resolve_starts(&probe, params->start_order, params->single_start, params->patience, params->retry_iter, r->dims.N, params->dodge, params->terminal_screen))
+            !obca_resolve_starts(&probe, params->start_order, params->single_start, params->patience, params->retry_iter, r->dims.N, params->dodge, params->terminal_screen) ||
+            !obca_resolve_time_bound(&probe, params->time_bound))
             return OBCA_E_INVAL;
     }
     // swept rows are built from the sensed box's own rectangle and velocity together: only exact sensing pairs the two

@@ -28,6 +28,9 @@ class obca:
         # the closed-form terminal-set screen of obca_mpc6 (a call that cannot succeed is answered feas=False without a solve)
         self.dodge = True
         self.terminal_screen = True
+        # obca_mpc4's bound on its time scale (include/obca_mpc.h: time_bound): "reference" -- the reference's signed sum -- or
+        # "path", the window's L1 arc length, with which a window may run in any direction
+        self.time_bound = "reference"
 
     def _solver(self, N, m):
         key = (int(N), tuple(m))
@@ -48,7 +51,7 @@ class obca:
                                                                 terminal_set)
         kw = dict(xL=xL, xU=xU, uL=uL, uU=uU, ego=ego, dmin=dmin)
         kw.update(start_order=self.start_order if start_order is None else start_order, single_start=bool(single_start or self.single_start),
-                  dodge=self.dodge, terminal_screen=self.terminal_screen)
+                  dodge=self.dodge, terminal_screen=self.terminal_screen, time_bound=self.time_bound)
         if variant == 4:
             prm = SolverParams(Q_free=Q, R_free=R, P_free=P, **kw)
         else:

@@ -4,7 +4,7 @@ corridor with one random box, A*-like lattice reference, N+1-point window, obca_
 World: corridor ``xL=[0,0]``, ``xU=[39,10]`` with walls y >= 9 and y <= 1 (one half-space each, exactly the
 rows the reference derives for demo1: src/demo_setting.py:93-95 -> src/model_obstacle.py:37-102) and one
 axis-aligned box.  Instance ``i`` uses ``numpy.random.default_rng(seed0 + i)``; windows whose start or terminal
-pose is in collision, or whose time-scale bound ``max_Topt`` (signed sum, src/obca.py:961-962) cannot cover
+pose is in collision, or whose time-scale bound ``max_Topt`` (signed sum, src/obca.py:961-962: the default ``time_bound``) cannot cover
 the window length, are redrawn from the same generator, so the batch is reproducible from ``seed0`` alone.
 """
 import math
@@ -345,7 +345,9 @@ def make_batch_c3(B, N=20, first=0, gated=True, procs=1):
 def _one_way_path(y0, box):
     """lattice_path that detours upwards only and stays on the detour row: the reference's time-scale bound is a
     SIGNED sum of the window's x and y extents (src/obca.py:961-962, quirk q3), so its free-time problem is
-    infeasible on windows that run towards smaller y -- the reference's own demos only ever climb."""
+    infeasible on windows that run towards smaller y -- the reference's own demos only ever climb.  (That is the default bound,
+    which these worlds keep; ``SolverParams(time_bound="path")`` bounds the time scale by the window's arc length instead and
+    solves such windows: include/obca_mpc.h, OBCA_TIME_BOUND_PATH.)"""
     path = lattice_path(y0, box)
     if path is None:
         return None

@@ -35,7 +35,7 @@ class SolverParams:
                  ego=DEFAULT_EGO, dmin=0.05,
                  Q_free=None, R_free=None, P_free=None, Q_fix=None, R_fix=None, P_fix=None,
                  tol=0.0, rho=0.0, feas_tol=0.0, max_iter_free=0, max_iter_fixed=0, max_soc=0,
-                 start_order=0, single_start=False, patience=0, retry_iter=0, dodge=True, terminal_screen=True):
+                 start_order=0, single_start=False, patience=0, retry_iter=0, dodge=True, terminal_screen=True, time_bound="reference"):
         self.xL, self.xU, self.uL, self.uU = [tuple(float(v) for v in a[:2]) for a in (xL, xU, uL, uU)]
         self.ego = tuple(float(v) for v in ego)
         self.dmin = float(dmin)
@@ -58,6 +58,11 @@ class SolverParams:
         self.single_start = bool(single_start)
         self.patience, self.retry_iter = int(patience), int(retry_iter)
         self.dodge, self.terminal_screen = bool(dodge), bool(terminal_screen)
+        # obca_mpc4's bound on its time scale (include/obca_mpc.h: OBCA_TIME_BOUND_*): "reference" -- the reference's signed sum,
+        # infeasible by construction where the window runs towards smaller x or y -- or "path", the window's L1 arc length
+        if time_bound not in _lib.TIME_BOUNDS and time_bound not in _lib.TIME_BOUNDS.values():
+            raise ValueError("time_bound must be one of %s, got %r" % (sorted(_lib.TIME_BOUNDS), time_bound))
+        self.time_bound = int(_lib.TIME_BOUNDS.get(time_bound, time_bound))
 
     def to_c(self):
         p = _lib.ObcaParams()
@@ -76,6 +81,7 @@ class SolverParams:
         p.start_order, p.single_start = self.start_order, int(self.single_start)
         p.patience, p.retry_iter = self.patience, self.retry_iter
         p.dodge, p.terminal_screen = (0 if self.dodge else -1), (0 if self.terminal_screen else -1)
+        p.time_bound = self.time_bound
         return p
 
 
