@@ -778,8 +778,76 @@ typedef struct obca_pool_loop {
 void obca_pool_loop_init(obca_pool_loop* d);
 int obca_pool_loop_advance(const obca_pool_loop* d, int32_t solved, int32_t device, void* hip_stream);
 
+/* ------------------------------------------------------------------------------------------------------
+ * Fleet closed loop (obca_mpc 0.18), on the device: V cars that share one world avoid each other.  A fleet is G worlds of V
+ * cars; rollout b = g V + a of a closed loop over scene pools (above) is car a of world g, B = G V.  Every rollout's pool has
+ * K = Ks + V slots of E = 4 rows: slots 0 .. Ks-1 are the caller's obstacles and are never touched here, slot Ks + j is "car j
+ * of my world".  The fleet's time is synchronous: the loop runs obca_mpc8 with one Ts per world.  One step of the loop is the
+ * three calls of obca_pool_loop_advance's recipe (after a copy of x0 to x_prev) and then this call with measure = 1 and
+ * step = the loop step just applied; a start is obca_pool_loop_advance(solved = 0), then this call with measure = 0.  It has
+ * no handle; csrc/obca_fleet_core.h holds the serial definition the kernel reproduces.
+ *
+ * measure = 1 and n_sub > 0, for every car that applied a step in this loop step (k[b] == step + 1):
+ *   measure   c = the smallest signed distance to every OTHER car of its world over the interval, at n_sub + 1 samples with
+ *             both poses interpolated linearly (obca_plan_sweep's samples): obca_plan_clearance's distance between the
+ *             footprint of the car of lower index and the rows of the car of higher index (no margin), so that both cars of
+ *             a pair read one word; folded in ascending index of the other car.  A car that stepped moves from x_prev[b] to
+ *             x0[b]; one that did not stands at x0[b].  A pair with a pose word that is not finite is not measured (+inf).
+ *             `see` does not enter: a car is hit by whoever is there.
+ *   record    agent_clear_hist[b,step] = c (not written when c is NaN: a distance that overflowed)
+ *   flag      c NaN: OBCA_DONE_FAILED; c < clearance and flags[b] == OBCA_RUN: OBCA_DONE_COLLISION (a car that has just reached
+ *             its goal keeps OBCA_DONE_GOAL; its distance is recorded all the same).  A car flagged here gets variant_out[b] = 0
+ *             and every column of xref_out[b] = x0[b] (0 for a word that is not finite): obca_pool_loop_advance's rule for
+ *             masked launches.  A car that did not step gets no history word and keeps its flag.
+ * Then, always, from the flags as they are now, for every rollout (g, a) and every j < V:
+ *   spare     j == a, or see == OBCA_FLEET_SEE_LOWER and j > a (prioritised planning: a car yields only to lower indices), or a
+ *             word of car j's pose that is not finite: the rows of the unit square [-far-1, -far]^2 (obca_grid_pool's spare,
+ *             for its reason) and v = 0
+ *   car j     otherwise pool_A / pool_b[b,Ks+j] = the rectangle of car j at x0[g V + j] (obca_plan_clearance's footprint:
+ *             L = ego0 + ego2, W = ego1 + ego3, centre off = L/2 - ego2 ahead of the pose point) grown by margin, as four
+ *             unit rows in obca_grid_pool's order: (-sin, cos | n.c + W/2 + margin), (cos, sin | n.c + L/2 + margin) and the
+ *             two negated normals; every product and sum rounded on its own (no FMA), no -0.0 in A, so that heading 0 gives
+ *             the words of the axis-parallel box.  pool_v[b,Ks+j] = s (cos, sin) with s = u0[g V + j, 0] if
+ *             predict == OBCA_FLEET_PREDICT_VELOCITY and flags[g V + j] == OBCA_RUN, else 0: a car that has ended is parked
+ *             where it stands and stays an obstacle.
+ * Nothing written is ever NaN.
+ * G >= 1, 1 <= V <= 16, Ks >= 0, Ks + V <= 64, 1 <= N <= 127, 0 <= step < max_steps <= 1024, 0 <= n_sub <= 256 (0: not
+ * measured), measure 0 or 1, see and predict each one of their two values, clearance finite (-1e300: measured, never stopped),
+ * margin >= 0, far > 0 and ego finite, struct_size == sizeof(obca_fleet), device >= 0, no pointer NULL.  Every argument is
+ * checked before the first HIP call; a refused call (OBCA_E_INVAL) has no side effect.  Asynchronous on hip_stream. */
+#define OBCA_FLEET_SEE_ALL 0           /* every other car of the world is an obstacle */
+#define OBCA_FLEET_SEE_LOWER 1         /* only the cars of lower index are */
+#define OBCA_FLEET_PREDICT_VELOCITY 0  /* a running car translates with its last applied speed along its heading */
+#define OBCA_FLEET_PREDICT_STATIC 1    /* every car stands where it is */
+typedef struct obca_fleet {
+    uint32_t struct_size;              /* sizeof(obca_fleet): set by obca_fleet_init() */
+    uint32_t reserved_;
+    int32_t G, V, Ks, N, max_steps, step, n_sub, see, predict;
+    int32_t reserved2_;
+    double clearance, margin, far;     /* obca_fleet_init: -1e300 (never stops), 0 and 100 */
+    double ego[4];                     /* obca_fleet_init: 1.7, 0.75, 1.7, 0.75 (obca_params.ego's default) */
+    /* read-only, B = G V */
+    const double* x_prev;              /* [B,3] the poses before the step */
+    const double* x0;                  /* [B,3] the poses now */
+    const double* u0;                  /* [B,2] the last applied inputs */
+    const int32_t* k;                  /* [B] */
+    /* in and out */
+    int32_t* flags;                    /* [B] */
+    double* pool_A;                    /* [B,K,4,2], K = Ks + V: slots Ks .. K-1 written */
+    double* pool_b;                    /* [B,K,4] */
+    double* pool_v;                    /* [B,K,2] */
+    double* agent_clear_hist;          /* [B,max_steps] */
+    double* xref_out;                  /* [B,3,N+1] */
+    int32_t* variant_out;              /* [B] */
+} obca_fleet;
+
+/* zero-fills *d and sets struct_size, clearance, far and ego: the one way to start filling an obca_fleet */
+void obca_fleet_init(obca_fleet* d);
+int obca_fleet_step(const obca_fleet* d, int32_t measure, int32_t device, void* hip_stream);
+
 const char* obca_strerror(int code);
-/* "obca_mpc 0.17 (gfx950)": 0.17 = opt-in path time bound of obca_mpc4 (obca_params.time_bound, OBCA_TIME_BOUND_PATH);
+/* "obca_mpc 0.18 (gfx950)": 0.18 = fleet closed loop (obca_fleet_step);
+ * 0.17 = opt-in path time bound of obca_mpc4 (obca_params.time_bound, OBCA_TIME_BOUND_PATH);
  * 0.16 = closed loop over scene pools (obca_pool_loop_advance);
  * 0.15 = occupancy grids to scene pools (obca_grid_pool);
  * 0.14 = scene pools (obca_scene_select);

@@ -72,6 +72,29 @@ class ObcaPoolLoop(ctypes.Structure):
         self.ego = (ctypes.c_double * 4)(1.7, 0.75, 1.7, 0.75)
 
 
+# obca_fleet.see / obca_fleet.predict (include/obca_mpc.h)
+FLEET_SEE_ALL, FLEET_SEE_LOWER = 0, 1
+FLEET_SEE = {"all": FLEET_SEE_ALL, "lower": FLEET_SEE_LOWER}
+FLEET_PREDICT_VELOCITY, FLEET_PREDICT_STATIC = 0, 1
+FLEET_PREDICT = {"velocity": FLEET_PREDICT_VELOCITY, "static": FLEET_PREDICT_STATIC}
+
+
+class ObcaFleet(ctypes.Structure):
+    """obca_fleet (include/obca_mpc.h), the descriptor of obca_fleet_step.  A new instance is what obca_fleet_init leaves: all
+    zero (see ALL, predict VELOCITY, margin 0), struct_size set, clearance -1e300 (never stops), far 100, the default ego."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("reserved_", ctypes.c_uint32)] + \
+               [(n, ctypes.c_int32) for n in ("G", "V", "Ks", "N", "max_steps", "step", "n_sub", "see", "predict", "reserved2_")] + \
+               [("clearance", ctypes.c_double), ("margin", ctypes.c_double), ("far", ctypes.c_double), ("ego", ctypes.c_double * 4)] + \
+               [(n, ctypes.c_void_p) for n in ("x_prev", "x0", "u0", "k", "flags", "pool_A", "pool_b", "pool_v", "agent_clear_hist",
+                                               "xref_out", "variant_out")]
+
+    def __init__(self, *a, **kw):
+        super().__init__(*a, **kw)
+        self.struct_size = ctypes.sizeof(ObcaFleet)
+        self.clearance, self.far = -1e300, 100.0
+        self.ego = (ctypes.c_double * 4)(1.7, 0.75, 1.7, 0.75)
+
+
 EXPORTS = ("obca_create", "obca_destroy", "obca_solve_batch", "obca_lds_bytes", "obca_strerror", "obca_version", "obca_params_init",
            "obca_set_profile_buffer", "obca_set_mode", "obca_set_two_sided_sweep", "obca_rollouts_create", "obca_rollouts_destroy", "obca_rollouts_debug_stats", "obca_rollouts_debug_harness",
            "obca_rollouts_reset", "obca_rollouts_step", "obca_rollouts_read", "obca_rollouts_run",
@@ -79,7 +102,8 @@ EXPORTS = ("obca_create", "obca_destroy", "obca_solve_batch", "obca_lds_bytes", 
            "obca_rollouts_set_warm_start", "obca_dual_size", "obca_set_certificate_buffers", "obca_rasterise_batch",
            "obca_plan_clearance", "obca_plan_sweep", "obca_plan_tighten", "obca_rollouts_audit", "obca_rollouts_set_collision_stop", "obca_rollouts_set_exact_sensing",
            "obca_rollouts_read_clearance", "obca_rollouts_set_swept_rows", "obca_moving_rows_batch", "obca_plan_refine",
-           "obca_grid_dilate_batch", "obca_route_resample", "obca_scene_select", "obca_grid_pool", "obca_pool_loop_init", "obca_pool_loop_advance")
+           "obca_grid_dilate_batch", "obca_route_resample", "obca_scene_select", "obca_grid_pool", "obca_pool_loop_init", "obca_pool_loop_advance",
+           "obca_fleet_init", "obca_fleet_step")
 
 OBCA_MAX_DYN = 4
 RUN, DONE_GOAL, DONE_CAP, DONE_FAILED, DONE_COLLISION = 0, 1, 2, 3, 4
@@ -220,6 +244,10 @@ def load():
     lib.obca_pool_loop_init.restype = None
     lib.obca_pool_loop_advance.argtypes = [ctypes.POINTER(ObcaPoolLoop), ctypes.c_int32, ctypes.c_int32, vp]
     lib.obca_pool_loop_advance.restype = ctypes.c_int
+    lib.obca_fleet_init.argtypes = [ctypes.POINTER(ObcaFleet)]
+    lib.obca_fleet_init.restype = None
+    lib.obca_fleet_step.argtypes = [ctypes.POINTER(ObcaFleet), ctypes.c_int32, ctypes.c_int32, vp]
+    lib.obca_fleet_step.restype = ctypes.c_int
     lib.obca_lds_bytes.argtypes = [ctypes.POINTER(ObcaDims)]
     lib.obca_lds_bytes.restype = ctypes.c_int64
     lib.obca_strerror.argtypes = [ctypes.c_int]

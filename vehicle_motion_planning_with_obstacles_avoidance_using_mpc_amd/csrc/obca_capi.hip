@@ -312,7 +312,7 @@ extern "C" const char* obca_strerror(int code) {
     }
 }
 
-extern "C" const char* obca_version(void) { return "obca_mpc 0.17 (gfx950)"; }
+extern "C" const char* obca_version(void) { return "obca_mpc 0.18 (gfx950)"; }
 extern "C" void obca_params_init(obca_params* p) {
     if (!p) return;
     memset(p, 0, sizeof(*p));

@@ -18,7 +18,8 @@ velocities), driven by select -> solve -> obca_pool_loop_advance per step.  The 
 in csrc/obca_poolloop_core.h) records the step, measures the applied interval against the WHOLE pool, moves the pool by the
 applied step length, advances the state, sets the flags and writes the next reference window from the route.  ``drive_maps``
 composes ``grid_pool``, ``openloop.route_search`` and ``PoolLoop``: B maps and B start/goal pairs in, B driven trajectories
-out.  Not here: the reference's 4 -> 6 -> 8 dispatch, its lidar gate and its fixed-time reference preparation
+out.  ``FleetLoop`` puts V of those rollouts into one world: after every step obca_fleet_step (csrc/obca_fleet_core.h) writes
+the other cars of the world into the last V pool slots of each car and measures what the cars did to each other.  Not here: the reference's 4 -> 6 -> 8 dispatch, its lidar gate and its fixed-time reference preparation
 (``rollouts.DeviceRollouts`` has those, for at most 8 static obstacles).
 """
 import ctypes
@@ -409,6 +410,128 @@ class PoolLoop:
         out = {k: v.clone() for k, v in self.hist.items()}
         out.update(steps=self.k.clone(), flags=self.flags.clone(), pool_b=self.pool_b.clone(), x0=self.x0.clone(),
                    min_clear=self.hist["clear"].min(dim=1).values)
+        return out
+
+
+class FleetLoop(PoolLoop):
+    """G worlds of V cars each: ``PoolLoop`` whose rollouts share worlds.  Rollout b = g V + a is car a of world g (B = G V, a
+    multiple of V); the caller gives the static part of every pool -- pool_A [B,Ks,4,2], pool_b [B,Ks,4] and optionally pool_v
+    [B,Ks,2], or None for Ks = 0 -- and the loop appends V agent slots, slot Ks + j being "car j of my world": the rectangle of
+    that car where it stands (grown by ``margin``), translating with its last applied speed along its heading
+    (predict="velocity") or standing (predict="static"); a car that has ended is parked where it stands and stays an obstacle.
+    see="all": every other car is an obstacle; see="lower": only the cars of lower index are (prioritised planning: car 0
+    yields to nobody).  A spare slot (the car itself, a car not seen, a car without a pose) is ``grid_pool``'s spare at ``far``.
+
+    The fleet's time is synchronous: variant 8 only, and Ts must be one value per world -- checked here when Ts is a float or a
+    host array; a device tensor is taken at its word (checking it would cost a host synchronisation).
+    One step: x_prev = x0, ``PoolLoop``'s step unchanged (select, solve, obca_pool_loop_advance: its ``clear`` measures a car
+    against the PREDICTION of the others), then obca_fleet_step (arithmetic and serial definition in csrc/obca_fleet_core.h):
+    the smallest distance of every car that stepped to every other car of its world over the interval both actually drove
+    (agent_n_sub + 1 samples; 0: not measured), a car closer than ``agent_clearance`` ends with flag "collision"
+    (None: measured, never stopped), and the agent slots are rewritten from the poses, inputs and flags as they are now.
+    ``read()`` adds agent_clear [B,S] (+inf where nothing was measured) and agent_min_clear [B].
+
+        solver = BatchSolver(5, [4] * 3, B)                       # two corridor walls and the nearest other car
+        loop = FleetLoop(solver, 2, walls_A, walls_b, start, goal, path, path_len, Ts=1.5, see="lower").run()
+        out = loop.read()                                         # out["flags"], out["agent_min_clear"], out["x_closed"], ...
+    """
+
+    def __init__(self, solver, V, pool_A, pool_b, start, goal, path, path_len, Ts, pool_v=None, see="all", predict="velocity",
+                 margin=0.0, far=100.0, agent_clearance=None, agent_n_sub=8, **kw):
+        import numpy as np
+        import torch
+        if not torch.cuda.is_available():
+            raise RuntimeError("scene.FleetLoop needs a ROCm GPU; there is no CPU fallback on the product path")
+        dev = solver.device
+        V = self.V = int(V)
+        if see not in _lib.FLEET_SEE or predict not in _lib.FLEET_PREDICT:
+            raise ValueError("see is one of %s and predict one of %s" % (sorted(_lib.FLEET_SEE), sorted(_lib.FLEET_PREDICT)))
+        if kw.get("variant") not in (None, 8):
+            raise ValueError("variant %r: a fleet's time is synchronous, the loop runs obca_mpc8 (8) only" % (kw["variant"],))
+        kw["variant"] = 8
+        start = torch.as_tensor(start, dtype=torch.float64, device=dev)
+        B = int(start.shape[0])
+        if V < 1 or V > 16 or B % V != 0:
+            raise ValueError("B = %d rollouts are no whole number of worlds of V = %d cars (1 <= V <= 16)" % (B, V))
+        self.G = B // V
+        f64 = lambda a: torch.as_tensor(a, dtype=torch.float64, device=dev)
+        if pool_A is None or pool_b is None:
+            if pool_A is not None or pool_b is not None or pool_v is not None:
+                raise ValueError("pool_A and pool_b are given together; without them there is no pool_v")
+            sA, sb = torch.zeros(B, 0, 4, 2, dtype=torch.float64, device=dev), torch.zeros(B, 0, 4, dtype=torch.float64, device=dev)
+        else:
+            sA, sb = f64(pool_A), f64(pool_b)
+        if sA.dim() != 4 or sb.dim() != 3 or tuple(sA.shape) != tuple(sb.shape) + (2,) or sb.shape[0] != B or sb.shape[2] != 4:
+            raise ValueError("expected pool_A [B,Ks,4,2], pool_b [B,Ks,4] with B = %d" % B)
+        Ks = self.Ks = int(sb.shape[1])
+        if Ks + V > 64:
+            raise ValueError("Ks + V = %d slots: a pool holds 64 at the most" % (Ks + V))
+        sv = torch.zeros(B, Ks, 2, dtype=torch.float64, device=dev) if pool_v is None else solver._dev(pool_v, (B, Ks, 2))
+        if not isinstance(Ts, torch.Tensor) or not Ts.is_cuda:
+            t = np.asarray(Ts.cpu() if isinstance(Ts, torch.Tensor) else Ts, dtype=float)
+            if t.ndim != 0 and (t.shape != (B,) or not np.all(t.reshape(self.G, V) == t.reshape(self.G, V)[:, :1])):
+                raise ValueError("Ts must be one value per world: [B] with the same word for the V cars of a world, or a float")
+        # the agent slots start as spares; obca_fleet_step writes them at every reset and after every step
+        far = float(far)
+        spare_A = torch.tensor([[0.0, 1.0], [1.0, 0.0], [0.0, -1.0], [-1.0, 0.0]], dtype=torch.float64, device=dev)
+        spare_b = torch.tensor([-far, -far, far + 1.0, far + 1.0], dtype=torch.float64, device=dev)
+        full_A = torch.cat([sA, spare_A.expand(B, V, 4, 2)], dim=1).contiguous()
+        full_b = torch.cat([sb, spare_b.expand(B, V, 4)], dim=1).contiguous()
+        full_v = torch.cat([sv, torch.zeros(B, V, 2, dtype=torch.float64, device=dev)], dim=1).contiguous()
+        self.see, self.predict, self.margin, self.far = see, predict, float(margin), far
+        self.agent_clearance = NEVER_STOP if agent_clearance is None else float(agent_clearance)
+        self.agent_n_sub = int(agent_n_sub)
+        self._fdesc = None                                   # made by the first reset, which PoolLoop's constructor ends with
+        super().__init__(solver, full_A, full_b, start, goal, path, path_len, Ts, pool_v=full_v, **kw)
+
+    def _make_fleet(self):
+        torch = self.torch
+        self.x_prev = torch.zeros(self.B, 3, dtype=torch.float64, device=self.device)
+        self.agent_clear = torch.zeros(self.B, self.max_steps, dtype=torch.float64, device=self.device)
+        d = self._fdesc = _lib.ObcaFleet()
+        d.G, d.V, d.Ks, d.N, d.max_steps, d.n_sub = self.G, self.V, self.Ks, self.N, self.max_steps, self.agent_n_sub
+        d.see, d.predict = _lib.FLEET_SEE[self.see], _lib.FLEET_PREDICT[self.predict]
+        d.clearance, d.margin, d.far = self.agent_clearance, self.margin, self.far
+        d.ego = (ctypes.c_double * 4)(*self.ego)
+        for name, t in (("x_prev", self.x_prev), ("x0", self.x0), ("u0", self.u0), ("k", self.k), ("flags", self.flags),
+                        ("pool_A", self.pool_A), ("pool_b", self.pool_b), ("pool_v", self.pool_v),
+                        ("agent_clear_hist", self.agent_clear), ("xref_out", self.xref), ("variant_out", self.variant_out)):
+            setattr(d, name, t.data_ptr())
+
+    def _tensors(self):
+        own = super()._tensors()
+        if self._fdesc is not None:
+            own += [self.x_prev, self.agent_clear]
+        return own
+
+    def _fleet_step(self, measure, step):
+        self._fdesc.step = int(step)
+        _lib.check(self.lib.obca_fleet_step(ctypes.byref(self._fdesc), int(measure), _lib.device_index(self.device),
+                                            _lib.stream_ptr(self.device)))
+
+    def reset(self):
+        super().reset()
+        if self._fdesc is None:
+            self._make_fleet()
+            self._on_stream()
+        self.x_prev.copy_(self.x0)
+        self.agent_clear.fill_(float("inf"))
+        self._fleet_step(0, 0)
+
+    def _step(self):
+        self.x_prev.copy_(self.x0)
+        super()._step()
+        idx = self.steps_enqueued - 1
+        if idx < self.max_steps:
+            self._fleet_step(1, idx)
+        else:                                                # beyond the cap nobody steps: the slots alone
+            self._fleet_step(0, 0)
+
+    def read(self):
+        """``PoolLoop.read()``'s dict and agent_clear [B,S] (the smallest distance to another car of the world over every
+        interval the car drove, +inf where nothing was measured), agent_min_clear [B]"""
+        out = super().read()
+        out.update(agent_clear=self.agent_clear.clone(), agent_min_clear=self.agent_clear.min(dim=1).values)
         return out
 
 
