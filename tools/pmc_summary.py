@@ -65,7 +65,10 @@ for tgt, shape in SHAPES.items():
             if "obca" not in k:
                 continue
             e = per.setdefault(k, {})
-            e.setdefault(r["Counter_Name"], []).append(float(r["Counter_Value"]))
+            cname = r["Counter_Name"]
+            if "SQ_WAIT_INST_LDS" in os.path.basename(d) and cname in ("SQ_WAVE_CYCLES", "SQ_WAIT_INST_ANY"):
+                cname += "@lds"               # the attribution pass's own copies: its shares come from ONE pass
+            e.setdefault(cname, []).append(float(r["Counter_Value"]))
             e["_dur"] = e.get("_dur", []) + [(int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e6]
             e["_meta"] = {x: r.get(x) for x in ("Grid_Size", "Workgroup_Size", "LDS_Block_Size", "Scratch_Size", "VGPR_Count", "Accum_VGPR_Count", "SGPR_Count")}
         shutil.copy(cc, os.path.join(dst, "%s_pmc_%s_%s.csv" % (tag, tgt, os.path.basename(d).split("_", 2)[2][:24])))
@@ -87,6 +90,18 @@ for tgt, shape in SHAPES.items():
             rec.update(sq_wave_cycles=wc, valu_busy_frac=g("SQ_ACTIVE_INST_VALU") / wc, wave_wait_frac=g("SQ_WAIT_ANY") / wc,
                        inst_any_frac=g("SQ_ACTIVE_INST_ANY") / wc, issue_stall_frac=(g("SQ_WAIT_INST_ANY") or 0) / wc,
                        valu_insts_per_wave=g("SQ_INSTS_VALU") / max(g("SQ_WAVES") or 1, 1), valu_insts=g("SQ_INSTS_VALU"))
+        # attribution passes of tools/profile.sh (headline kernel): instruction cache, and the LDS share of the issue waits
+        gm = lambda n: max(e[n]) if n in e else None
+        if gm("SQC_ICACHE_REQ"):
+            rec.update(icache_req=gm("SQC_ICACHE_REQ"), icache_hits=gm("SQC_ICACHE_HITS"), icache_misses=gm("SQC_ICACHE_MISSES"),
+                       ifetch=gm("SQ_IFETCH"), icache_miss_rate=(gm("SQC_ICACHE_MISSES") or 0) / gm("SQC_ICACHE_REQ"))
+        if gm("SQ_WAIT_INST_LDS") is not None:
+            rec.update(wait_inst_lds=gm("SQ_WAIT_INST_LDS"), insts_lds=gm("SQ_INSTS_LDS"), active_inst_lds=gm("SQ_ACTIVE_INST_LDS"),
+                       lds_bank_conflict=gm("SQ_LDS_BANK_CONFLICT"))
+            if gm("SQ_WAIT_INST_ANY@lds"):
+                rec.update(lds_share_of_wait_inst_any=gm("SQ_WAIT_INST_LDS") / gm("SQ_WAIT_INST_ANY@lds"),
+                           wait_inst_lds_frac=gm("SQ_WAIT_INST_LDS") / gm("SQ_WAVE_CYCLES@lds") if gm("SQ_WAVE_CYCLES@lds") else None,
+                           wait_inst_any_frac_same_pass=gm("SQ_WAIT_INST_ANY@lds") / gm("SQ_WAVE_CYCLES@lds") if gm("SQ_WAVE_CYCLES@lds") else None)
         out["kernels"].append(rec)
 with open(os.path.join(dst, tag + "_pmc_summary.json"), "w") as f:
     json.dump(out, f, indent=1)

@@ -336,75 +336,82 @@ __device__ __forceinline__ double eval_objective(const Lay& L, const Sh& S, cons
 
 // out = gf + J^T ymul (+ rotation rows with nu): gradient of the Lagrangian w.r.t. x.
 // One target entry per lane (gather form, deterministic).
-// HAT: multipliers yhat = y + ghat / E of the condensed rows (the soft rows keep y) evaluated on the fly -- storing
-// them cost one more row array in LDS
+// HAT: multipliers yhat = y + ghat / E of the condensed rows (the soft rows keep y), staged in S.tmp by the rows' owner lanes
+// right before the call (S.tmp is free from the accepted trial's row values to the row steps: it shares Y's storage, which the
+// local blocks write after this gather's closing barrier).
+// Loads as in riccati(): every loop issues what its lanes may need unconditionally, with indices valid on every lane, as one
+// batch under one empty asm; the lane-dependent cases only select among registers.
 template <bool HAT>
 __device__ __forceinline__ void gather_grad(const Lay& L, const Sh& S, const Inst& in, double* out, int lane) {
-    auto YM = [&](int r) -> double { return HAT ? S.y[r] + S.gh[r] * S.Einv[r] : S.y[r]; };     // condensed rows
-    auto YS = [&](int r) -> double { return S.y[r]; };                                             // init, dyn (soft)
+    const double* ym = HAT ? S.tmp : S.y;
     const double* xv = S.x;
     const double T = L.free_T ? xv[L.iT()] : 1.0;
     const double h = T * in.Ts, ih = rcp64(h), iTh = ih * rcp64(T);
     // poses and inputs
     for (int t = lane; t < (L.N + 1) * 5; t += NT) {
         const int k = t / 5, j = t - 5 * k;
-        if (j >= 3 && k == L.N) continue;
-        const double cs = S.ct[k], sn = S.st[k];
-        double v;
-        if (j < 3) {
-            v = S.gf[L.ig(k) + j];
-            if (k == 0) v += YS(L.r_init + j);
-            if (k >= 1) v += YS(L.r_dyn + 3 * (k - 1) + j);
+        const bool pose = j < 3;
+        const int kc = k < L.N ? k : L.N - 1, kn = k + 1 < L.N ? k + 1 : kc;     // stages of the dynamics / input rows read
+        const int c = pose ? 0 : j - 3, jx = j < 2 ? j : 1;
+        double cs = S.ct[k], sn = S.st[k], v = S.gf[L.ig(k) + j];
+        double yd0 = ym[L.r_dyn + 3 * kc], yd1 = ym[L.r_dyn + 3 * kc + 1], yd2 = ym[L.r_dyn + 3 * kc + 2];
+        double vel = xv[L.iu(kc)];
+        // pose entry: row of the stage before (initial condition at stage 0), its box row, terminal row; input entry: its box row,
+        // the acceleration rows of this stage and of the next
+        double ya = ym[pose ? (k == 0 ? L.r_init + j : L.r_dyn + 3 * (k - 1) + j) : L.r_ub + 2 * kc + c];
+        double yb = ym[pose ? L.r_xb + 2 * k + jx : L.r_acc + 2 * kc + c];
+        double yc = ym[pose ? (L.variant == 4 ? L.r_term + j : L.variant == 6 ? L.r_tx + jx : 0) : L.r_acc + 2 * kn + c];
+        asm volatile("" : "+v"(cs), "+v"(sn), "+v"(v), "+v"(yd0), "+v"(yd1), "+v"(yd2), "+v"(vel), "+v"(ya), "+v"(yb), "+v"(yc));
+        if (pose) {
+            v += ya;
             if (k < L.N) {
-                const double* yd = S.y + L.r_dyn + 3 * k;
-                v -= yd[j];
-                if (j == 2) {
-                    const double vel = xv[L.iu(k)];
-                    v -= h * vel * (-sn * yd[0] + cs * yd[1]);
-                }
+                v -= (j == 0) ? yd0 : (j == 1) ? yd1 : yd2;
+                if (j == 2) v -= h * vel * (-sn * yd0 + cs * yd1);
             }
-            if (k == L.N && L.variant == 4) v += YM(L.r_term + j);
+            if (k == L.N && L.variant == 4) v += yc;
             if (j < 2) {
-                v += YM(L.r_xb + 2 * k + j);
-                if (k == L.N && L.variant == 6) v += YM(L.r_tx + j);
+                v += yb;
+                if (k == L.N && L.variant == 6) v += yc;
             }
-            for (int i = 0; i < L.nO; ++i) {
-                const int pr = k * L.nO + i;
-                const double c0 = S.cc[2 * pr], c1 = S.cc[2 * pr + 1];
-                const double yd = YM(L.r_dist + pr);
-                if (j == 0) v += yd * c0;
-                else if (j == 1) v += yd * c1;
-                else {
-                    const double dth = -sn * c0 + cs * c1;
-                    v += yd * in.off * dth + S.nu[2 * pr] * dth + S.nu[2 * pr + 1] * (-cs * c0 - sn * c1);
-                }
-            }
-            out[L.ip(k) + j] = v;
-        } else {
-            const int c = j - 3;
-            v = S.gf[L.ig(k) + 3 + c];
-            const double* yd = S.y + L.r_dyn + 3 * k;
-            v -= (c == 0) ? h * (cs * yd[0] + sn * yd[1]) : h * yd[2];
-            v += YM(L.r_ub + 2 * k + c);
-            v -= YM(L.r_acc + 2 * k + c) * ih;
-            if (k + 1 < L.N) v += YM(L.r_acc + 2 * (k + 1) + c) * ih;
-            out[L.iu(k) + c] = v;
         }
+        for (int i = 0; i < L.nO; ++i) {
+            const int pr = k * L.nO + i;
+            double c0 = S.cc[2 * pr], c1 = S.cc[2 * pr + 1], yd = ym[L.r_dist + pr], nu0 = S.nu[2 * pr], nu1 = S.nu[2 * pr + 1];
+            asm volatile("" : "+v"(c0), "+v"(c1), "+v"(yd), "+v"(nu0), "+v"(nu1));
+            if (j == 0) v += yd * c0;
+            else if (j == 1) v += yd * c1;
+            else if (j == 2) {
+                const double dth = -sn * c0 + cs * c1;
+                v += yd * in.off * dth + nu0 * dth + nu1 * (-cs * c0 - sn * c1);
+            }
+        }
+        if (!pose) {
+            v -= (c == 0) ? h * (cs * yd0 + sn * yd1) : h * yd2;
+            v += ya;
+            v -= yb * ih;
+            if (k + 1 < L.N) v += yc * ih;
+        }
+        if (pose || k < L.N) out[pose ? L.ip(k) + j : L.iu(kc) + c] = v;
     }
     // lambda
     for (int t = lane; t < (L.N + 1) * L.M; t += NT) {
         const int k = t / L.M, j = t - k * L.M;
-        int i = 0;
-        while (j >= S.offm[i + 1]) ++i;
+        int i = 0;                   // the obstacle of edge j: how many of the later obstacles' first edges lie at or before it
+#pragma unroll
+        for (int q = 1; q < OBCA_MAX_OBST; ++q) { const int o = S.offm[q]; i += (q < L.nO && j >= o) ? 1 : 0; }
         const int pr = k * L.nO + i;
-        const double a0 = S.Aobs[((size_t)k * L.M + j) * 2], a1 = S.Aobs[((size_t)k * L.M + j) * 2 + 1];
-        const double cs = S.ct[k], sn = S.st[k], c0 = S.cc[2 * pr], c1 = S.cc[2 * pr + 1];
+        double a0 = S.Aobs[((size_t)k * L.M + j) * 2], a1 = S.Aobs[((size_t)k * L.M + j) * 2 + 1];
+        double cs = S.ct[k], sn = S.st[k], c0 = S.cc[2 * pr], c1 = S.cc[2 * pr + 1];
         const double* pk = xv + L.ip(k);
-        const double tx = pk[0] + cs * in.off, ty = pk[1] + sn * in.off;
-        double v = S.nu[2 * pr] * (cs * a0 + sn * a1) + S.nu[2 * pr + 1] * (-sn * a0 + cs * a1);
-        v += YM(L.r_norm + pr) * 2.0 * (a0 * c0 + a1 * c1);
-        v += YM(L.r_dist + pr) * (tx * a0 + ty * a1 - S.bobs[(size_t)k * L.M + j]);
-        v += YM(L.r_lam + t);
+        double p0 = pk[0], p1 = pk[1], nu0 = S.nu[2 * pr], nu1 = S.nu[2 * pr + 1];
+        double yn = ym[L.r_norm + pr], yd = ym[L.r_dist + pr], yl = ym[L.r_lam + t], bj = S.bobs[(size_t)k * L.M + j];
+        asm volatile("" : "+v"(a0), "+v"(a1), "+v"(cs), "+v"(sn), "+v"(c0), "+v"(c1), "+v"(p0), "+v"(p1), "+v"(nu0), "+v"(nu1),
+                          "+v"(yn), "+v"(yd), "+v"(yl), "+v"(bj));
+        const double tx = p0 + cs * in.off, ty = p1 + sn * in.off;
+        double v = nu0 * (cs * a0 + sn * a1) + nu1 * (-sn * a0 + cs * a1);
+        v += yn * 2.0 * (a0 * c0 + a1 * c1);
+        v += yd * (tx * a0 + ty * a1 - bj);
+        v += yl;
         out[L.il(k) + j] = v;
     }
     // mu
@@ -412,25 +419,31 @@ __device__ __forceinline__ void gather_grad(const Lay& L, const Sh& S, const Ins
         const int w4 = 4 * L.nO, k = t / w4, q = t - k * w4, i = q >> 2, j = q & 3;
         const int pr = k * L.nO + i;
         const double sgn = (j < 2) ? 1.0 : -1.0;
-        double v = sgn * S.nu[2 * pr + (j & 1)];
-        v -= in.gego[j] * YM(L.r_dist + pr);
-        v += YM(L.r_mu + t);
+        double nuj = S.nu[2 * pr + (j & 1)], gj = in.gego[j], yd = ym[L.r_dist + pr], ymu = ym[L.r_mu + t];
+        asm volatile("" : "+v"(nuj), "+v"(gj), "+v"(yd), "+v"(ymu));
+        double v = sgn * nuj;
+        v -= gj * yd;
+        v += ymu;
         out[L.imu(k) + q] = v;
     }
     // time scale
     if (L.free_T) {
+        double gT = S.gf[L.igT()], yT0 = ym[L.r_T], yT1 = ym[L.r_T + 1];
         double part = 0.0;
         for (int k = lane; k < L.N; k += NT) {
+            const int km = k > 0 ? k - 1 : 0;
             const double* u = xv + L.iu(k);
-            const double* yd = S.y + L.r_dyn + 3 * k;
-            part -= in.Ts * (u[0] * S.ct[k] * yd[0] + u[0] * S.st[k] * yd[1] + u[1] * yd[2]);
-            for (int c = 0; c < 2; ++c) {
-                const double prev = (k == 0) ? in.u0[c] : xv[L.iu(k - 1) + c];
-                part -= YM(L.r_acc + 2 * k + c) * (prev - u[c]) * iTh;
-            }
+            const double* yd = ym + L.r_dyn + 3 * k;
+            double u0 = u[0], u1 = u[1], cs = S.ct[k], sn = S.st[k], yd0 = yd[0], yd1 = yd[1], yd2 = yd[2];
+            double um0 = xv[L.iu(km)], um1 = xv[L.iu(km) + 1], ya0 = ym[L.r_acc + 2 * k], ya1 = ym[L.r_acc + 2 * k + 1];
+            asm volatile("" : "+v"(u0), "+v"(u1), "+v"(cs), "+v"(sn), "+v"(yd0), "+v"(yd1), "+v"(yd2), "+v"(um0), "+v"(um1),
+                              "+v"(ya0), "+v"(ya1), "+v"(gT), "+v"(yT0), "+v"(yT1));
+            part -= in.Ts * (u0 * cs * yd0 + u0 * sn * yd1 + u1 * yd2);
+            part -= ya0 * ((k == 0 ? in.u0[0] : um0) - u0) * iTh;
+            part -= ya1 * ((k == 0 ? in.u0[1] : um1) - u1) * iTh;
         }
         part = red_sum(part);
-        if (lane == 0) out[L.iT()] = S.gf[L.igT()] + part + (L.N + 1) * (YM(L.r_T) + YM(L.r_T + 1));
+        if (lane == 0) out[L.iT()] = gT + part + (L.N + 1) * (yT0 + yT1);
     }
     SYNC();
 }
@@ -677,7 +690,28 @@ __device__ __forceinline__ void assemble_stages(const Lay& L, const Sh& S, const
         // the stage block is accumulated in registers (read-modify-write through LDS serialised ~100 round trips)
         double Hpp[3][3], Huu[2][2] = {{0.0, 0.0}, {0.0, 0.0}}, Cpu[2][2] = {{0.0, 0.0}, {0.0, 0.0}};
         double hpu = 0.0, hpT = 0.0, huT[2] = {0.0, 0.0};
-        const double cs = S.ct[k], sn = S.st[k];
+        // Loads as in riccati(): the stage's own operands as one batch under one empty asm, from indices valid at every stage
+        // (the last stage reads the input and acceleration rows of the one before, stage 0 its own inputs as the previous
+        // ones, a variant without terminal rows the first rows), then one batch per obstacle.
+        const int kc = k < L.N ? k : L.N - 1, kn = k + 1 < L.N ? k + 1 : kc, km = k >= 1 ? k - 1 : 0;
+        const int rt = L.variant == 4 ? L.r_term : L.variant == 6 ? L.r_tx : 0;
+        double cs = S.ct[k], sn = S.st[k];
+        double Exb0 = S.Einv[L.r_xb + 2 * k], Exb1 = S.Einv[L.r_xb + 2 * k + 1];
+        double Et0 = S.Einv[rt], Et1 = S.Einv[rt + 1], Et2 = S.Einv[rt + 2];
+        double u0 = xv[L.iu(kc)], u1 = xv[L.iu(kc) + 1];
+        double y0 = S.y[L.r_dyn + 3 * kc], y1 = S.y[L.r_dyn + 3 * kc + 1], y2 = S.y[L.r_dyn + 3 * kc + 2];
+        double Eub[2] = {S.Einv[L.r_ub + 2 * kc], S.Einv[L.r_ub + 2 * kc + 1]};
+        double Eac[2] = {S.Einv[L.r_acc + 2 * kc], S.Einv[L.r_acc + 2 * kc + 1]};
+        double Ean[2] = {S.Einv[L.r_acc + 2 * kn], S.Einv[L.r_acc + 2 * kn + 1]};
+        double yac[2] = {S.y[L.r_acc + 2 * kc], S.y[L.r_acc + 2 * kc + 1]};
+        double yan[2] = {S.y[L.r_acc + 2 * kn], S.y[L.r_acc + 2 * kn + 1]};
+        double un[2] = {xv[L.iu(kn)], xv[L.iu(kn) + 1]}, um[2] = {xv[L.iu(km)], xv[L.iu(km) + 1]};
+        double bu0 = S.bx[L.iu(kc)], bu1 = S.bx[L.iu(kc) + 1];
+        double bp0 = S.bx[L.ip(k)], bp1 = S.bx[L.ip(k) + 1], bp2 = S.bx[L.ip(k) + 2];
+        asm volatile("" : "+v"(cs), "+v"(sn), "+v"(Exb0), "+v"(Exb1), "+v"(Et0), "+v"(Et1), "+v"(Et2), "+v"(u0), "+v"(u1), "+v"(y0),
+                          "+v"(y1), "+v"(y2), "+v"(Eub[0]), "+v"(Eub[1]), "+v"(Eac[0]), "+v"(Eac[1]), "+v"(Ean[0]), "+v"(Ean[1]),
+                          "+v"(yac[0]), "+v"(yac[1]), "+v"(yan[0]), "+v"(yan[1]), "+v"(un[0]), "+v"(un[1]), "+v"(um[0]), "+v"(um[1]),
+                          "+v"(bu0), "+v"(bu1), "+v"(bp0), "+v"(bp1), "+v"(bp2));
         const double* W = (k < L.N) ? in.Q : in.P;
 #pragma unroll
         for (int a = 0; a < 3; ++a) {
@@ -685,28 +719,27 @@ __device__ __forceinline__ void assemble_stages(const Lay& L, const Sh& S, const
             for (int b = 0; b < 3; ++b) Hpp[a][b] = sf * 2.0 * W[3 * a + b];
             Hpp[a][a] += dw;
         }
-        Hpp[0][0] += S.Einv[L.r_xb + 2 * k];
-        Hpp[1][1] += S.Einv[L.r_xb + 2 * k + 1];
-        if (k == L.N && L.variant == 4) { Hpp[0][0] += S.Einv[L.r_term]; Hpp[1][1] += S.Einv[L.r_term + 1]; Hpp[2][2] += S.Einv[L.r_term + 2]; }
-        if (k == L.N && L.variant == 6) { Hpp[0][0] += S.Einv[L.r_tx]; Hpp[1][1] += S.Einv[L.r_tx + 1]; }
+        Hpp[0][0] += Exb0;
+        Hpp[1][1] += Exb1;
+        if (k == L.N && L.variant == 4) { Hpp[0][0] += Et0; Hpp[1][1] += Et1; Hpp[2][2] += Et2; }
+        if (k == L.N && L.variant == 6) { Hpp[0][0] += Et0; Hpp[1][1] += Et1; }
         double hth = 0.0;                                           // theta-theta Lagrangian curvature
         for (int i = 0; i < L.nO; ++i) {
             const int pr = k * L.nO + i;
-            const double c0 = S.cc[2 * pr], c1 = S.cc[2 * pr + 1];
-            const double yd = S.y[L.r_dist + pr], Ei = S.Einv[L.r_dist + pr];
+            double c0 = S.cc[2 * pr], c1 = S.cc[2 * pr + 1];
+            double yd = S.y[L.r_dist + pr], Ei = S.Einv[L.r_dist + pr];
+            double nu0 = S.nu[2 * pr], nu1 = S.nu[2 * pr + 1];
+            asm volatile("" : "+v"(c0), "+v"(c1), "+v"(yd), "+v"(Ei), "+v"(nu0), "+v"(nu1));
             const double gp[3] = {c0, c1, in.off * (-sn * c0 + cs * c1)};
 #pragma unroll
             for (int a = 0; a < 3; ++a)
 #pragma unroll
                 for (int b = 0; b < 3; ++b) Hpp[a][b] += Ei * gp[a] * gp[b];
             hth += yd * in.off * (-cs * c0 - sn * c1);
-            hth += S.nu[2 * pr] * (-cs * c0 - sn * c1) + S.nu[2 * pr + 1] * (sn * c0 - cs * c1);
+            hth += nu0 * (-cs * c0 - sn * c1) + nu1 * (sn * c0 - cs * c1);
         }
         double lu0 = 0.0, lu1 = 0.0;
         if (k < L.N) {
-            const double* u = xv + L.iu(k);
-            const double* yd = S.y + L.r_dyn + 3 * k;
-            const double u0 = u[0], u1 = u[1], y0 = yd[0], y1 = yd[1], y2 = yd[2];
             hth += h * u0 * (y0 * cs + y1 * sn);
             hpu = h * (y0 * sn - y1 * cs);                            // theta - v
             const int ncost = (k + 1 < L.N ? 1 : 0) + (k >= 1 ? 1 : 0);  // acceleration cost pairs touching u_k
@@ -717,16 +750,16 @@ __device__ __forceinline__ void assemble_stages(const Lay& L, const Sh& S, const
                     Huu[a][b] = sf * 2.0 * in.R1[2 * a + b] + sf * 2.0 * in.R2[2 * a + b] * ih2 * ncost;
                     if (k >= 1) Cpu[a][b] = -sf * 2.0 * in.R2[2 * a + b] * ih2;
                 }
-                Huu[a][a] += dw + S.Einv[L.r_ub + 2 * k + a];
+                Huu[a][a] += dw + Eub[a];
             }
-            lu0 = S.bx[L.iu(k)]; lu1 = S.bx[L.iu(k) + 1];
+            lu0 = bu0; lu1 = bu1;
             // acceleration rows k (u_{k-1}, u_k) and k+1 (u_k, u_{k+1})
 #pragma unroll
             for (int c = 0; c < 2; ++c) {
-                const double Ek = S.Einv[L.r_acc + 2 * k + c];
+                const double Ek = Eac[c];
                 Huu[c][c] += Ek * ih2;
                 if (k >= 1) Cpu[c][c] -= Ek * ih2;
-                if (k + 1 < L.N) Huu[c][c] += S.Einv[L.r_acc + 2 * (k + 1) + c] * ih2;
+                if (k + 1 < L.N) Huu[c][c] += Ean[c] * ih2;
             }
             if (L.free_T) {
                 // (theta,T), (u,T) and (T,T) entries
@@ -735,17 +768,17 @@ __device__ __forceinline__ void assemble_stages(const Lay& L, const Sh& S, const
                 huT[1] = -in.Ts * y2;
                 const double uc[2] = {u0, u1};
                 double qa[2] = {0, 0}, qb[2] = {0, 0};
-                if (k + 1 < L.N) { qa[0] = xv[L.iu(k + 1)] - u0; qa[1] = xv[L.iu(k + 1) + 1] - u1; }
-                if (k >= 1) { qb[0] = u0 - xv[L.iu(k - 1)]; qb[1] = u1 - xv[L.iu(k - 1) + 1]; }
+                if (k + 1 < L.N) { qa[0] = un[0] - u0; qa[1] = un[1] - u1; }
+                if (k >= 1) { qb[0] = u0 - um[0]; qb[1] = u1 - um[1]; }
 #pragma unroll
                 for (int c = 0; c < 2; ++c) {
                     const double q = (k == 0) ? in.u0[c] - uc[c] : -qb[c];     // u_{k-1} - u_k
-                    const double ya = S.y[L.r_acc + 2 * k + c], Ek = S.Einv[L.r_acc + 2 * k + c];
+                    const double ya = yac[c], Ek = Eac[c];
                     huT[c] += ya * iTh + Ek * q * iThh;
                     HTT += ya * 2.0 * q * (iT * iTh) + Ek * q * q * (iTh * iTh);
                     if (k + 1 < L.N) {
                         const double qn = -qa[c];                              // u_k - u_{k+1}
-                        const double yn = S.y[L.r_acc + 2 * (k + 1) + c], En = S.Einv[L.r_acc + 2 * (k + 1) + c];
+                        const double yn = yan[c], En = Ean[c];
                         huT[c] += -yn * iTh - En * qn * iThh;
                     }
                 }
@@ -784,7 +817,7 @@ __device__ __forceinline__ void assemble_stages(const Lay& L, const Sh& S, const
                 else if (b == 5 && a >= 6) v = huT[a - 6];
                 H[a * (a + 1) / 2 + b] = v;
             }
-        lv[0] = S.bx[L.ip(k)]; lv[1] = S.bx[L.ip(k) + 1]; lv[2] = S.bx[L.ip(k) + 2];
+        lv[0] = bp0; lv[1] = bp1; lv[2] = bp2;
         lv[3] = 0.0; lv[4] = 0.0; lv[5] = 0.0; lv[6] = lu0; lv[7] = lu1;
     }
     if (L.free_T) {
@@ -815,24 +848,50 @@ __device__ __forceinline__ int local_blocks(const Lay& L, const Sh& S, const Ins
         const int pr = w >> 1;
         const bool hi = (w & 1) != 0;
         const int k = pr / L.nO, i = pr - k * L.nO;
-        const int o0 = S.offm[i], m = S.offm[i + 1] - o0;
-        const double cs = S.ct[k], sn = S.st[k];
-        const double c0 = S.cc[2 * pr], c1 = S.cc[2 * pr + 1];
+        // Loads as in riccati(): two batches, each under one empty asm.  First everything the pair's index alone addresses
+        // (with the obstacle's edge range), then the edge operands through that range: slot j of an obstacle with fewer edges
+        // reads the obstacle's last edge and selects its padding value in registers.
+        int o0 = S.offm[i], o1 = S.offm[i + 1];
+        double cs = S.ct[k], sn = S.st[k];
+        double c0 = S.cc[2 * pr], c1 = S.cc[2 * pr + 1];
         const double* pk = S.x + L.ip(k);
-        const double tx = pk[0] + cs * in.off, ty = pk[1] + sn * in.off;
-        const double yn = S.y[L.r_norm + pr], En = S.Einv[L.r_norm + pr];
-        const double yd = S.y[L.r_dist + pr], Ed = S.Einv[L.r_dist + pr];
-        const double nu1 = S.nu[2 * pr], nu2 = S.nu[2 * pr + 1];
+        double p0 = pk[0], p1 = pk[1];
+        double yn = S.y[L.r_norm + pr], En = S.Einv[L.r_norm + pr];
+        double yd = S.y[L.r_dist + pr], Ed = S.Einv[L.r_dist + pr];
+        double nu1 = S.nu[2 * pr], nu2 = S.nu[2 * pr + 1];
+        double cr0 = S.crot[2 * pr], cr1 = S.crot[2 * pr + 1];
+        double Em[4], bm[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { Em[j] = S.Einv[L.r_mu + k * 4 * L.nO + 4 * i + j]; bm[j] = S.bx[L.imu(k) + 4 * i + j]; }
+        asm volatile("" : "+v"(o0), "+v"(o1), "+v"(cs), "+v"(sn), "+v"(c0), "+v"(c1), "+v"(p0), "+v"(p1), "+v"(yn), "+v"(En),
+                          "+v"(yd), "+v"(Ed), "+v"(nu1), "+v"(nu2), "+v"(cr0), "+v"(cr1), "+v"(Em[0]), "+v"(Em[1]), "+v"(Em[2]),
+                          "+v"(Em[3]), "+v"(bm[0]), "+v"(bm[1]), "+v"(bm[2]), "+v"(bm[3]));
+        const int m = o1 - o0;
+        const double tx = p0 + cs * in.off, ty = p1 + sn * in.off;
         double a0[OBCA_MAX_EDGES], a1[OBCA_MAX_EDGES], gn[OBCA_MAX_EDGES], gd[NW];
+        double bl[OBCA_MAX_EDGES], El[OBCA_MAX_EDGES], bxl[OBCA_MAX_EDGES];
+#pragma unroll
+        for (int j = 0; j < OBCA_MAX_EDGES; ++j) {
+            const int e = o0 + (j < m ? j : m - 1);
+            a0[j] = S.Aobs[((size_t)k * L.M + e) * 2];
+            a1[j] = S.Aobs[((size_t)k * L.M + e) * 2 + 1];
+            bl[j] = S.bobs[(size_t)k * L.M + e];
+            El[j] = S.Einv[L.r_lam + k * L.M + e];
+            bxl[j] = S.bx[L.il(k) + e];
+        }
+        static_assert(OBCA_MAX_EDGES == 4, "the batch below names four edge slots");
+        asm volatile("" : "+v"(a0[0]), "+v"(a0[1]), "+v"(a0[2]), "+v"(a0[3]), "+v"(a1[0]), "+v"(a1[1]), "+v"(a1[2]), "+v"(a1[3]),
+                          "+v"(bl[0]), "+v"(bl[1]), "+v"(bl[2]), "+v"(bl[3]), "+v"(El[0]), "+v"(El[1]), "+v"(El[2]), "+v"(El[3]),
+                          "+v"(bxl[0]), "+v"(bxl[1]), "+v"(bxl[2]), "+v"(bxl[3]));
         double K[MW * (MW + 1) / 2], Yv[MW][2], G0[MW], G1[MW], G2[MW];
 #define KP(a, b) K[((a) * ((a) + 1)) / 2 + (b)]
         const double dth = -sn * c0 + cs * c1;          // d(dist)/d(theta) / off  and  d(e1)/d(theta)
 #pragma unroll
         for (int j = 0; j < OBCA_MAX_EDGES; ++j) {
             const bool on = j < m;
-            a0[j] = on ? S.Aobs[((size_t)k * L.M + o0 + j) * 2] : 0.0;
-            a1[j] = on ? S.Aobs[((size_t)k * L.M + o0 + j) * 2 + 1] : 0.0;
-            const double bj = on ? S.bobs[(size_t)k * L.M + o0 + j] : 0.0;
+            a0[j] = on ? a0[j] : 0.0;
+            a1[j] = on ? a1[j] : 0.0;
+            const double bj = on ? bl[j] : 0.0;
             gn[j] = 2.0 * (a0[j] * c0 + a1[j] * c1);
             gd[j] = on ? (tx * a0[j] + ty * a1[j] - bj) : 0.0;
         }
@@ -852,8 +911,8 @@ __device__ __forceinline__ int local_blocks(const Lay& L, const Sh& S, const Ins
 #pragma unroll
         for (int j = 0; j < OBCA_MAX_EDGES; ++j) {
             const bool on = j < m;
-            KP(j, j) += on ? (dw + S.Einv[L.r_lam + k * L.M + o0 + j]) : 1.0;   // padded slots: identity
-            rl[j] = on ? -S.bx[L.il(k) + o0 + j] : 0.0;
+            KP(j, j) += on ? (dw + El[j]) : 1.0;   // padded slots: identity
+            rl[j] = on ? -bxl[j] : 0.0;
             // coupling to the pose: columns (x, y, theta)
             G0[j] = Ed * gd[j] * c0 + yd * a0[j];
             G1[j] = Ed * gd[j] * c1 + yd * a1[j];
@@ -866,8 +925,8 @@ __device__ __forceinline__ int local_blocks(const Lay& L, const Sh& S, const Ins
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int a = OBCA_MAX_EDGES + j;
-            KP(a, a) += dw + S.Einv[L.r_mu + k * 4 * L.nO + 4 * i + j];
-            rl[a] = -S.bx[L.imu(k) + 4 * i + j];
+            KP(a, a) += dw + Em[j];
+            rl[a] = -bm[j];
             G0[a] = Ed * gd[a] * c0;
             G1[a] = Ed * gd[a] * c1;
             G2[a] = Ed * gd[a] * in.off * dth;
@@ -875,8 +934,8 @@ __device__ __forceinline__ int local_blocks(const Lay& L, const Sh& S, const Ins
             KP(NW + 1, a) = (j == 1) ? 1.0 : (j == 3) ? -1.0 : 0.0;
         }
         KP(NW, NW) = 0.0; KP(NW + 1, NW) = 0.0; KP(NW + 1, NW + 1) = 0.0;
-        G0[NW] = 0.0; G1[NW] = 0.0; G2[NW] = dth; rl[NW] = -S.crot[2 * pr];
-        G0[NW + 1] = 0.0; G1[NW + 1] = 0.0; G2[NW + 1] = -cs * c0 - sn * c1; rl[NW + 1] = -S.crot[2 * pr + 1];
+        G0[NW] = 0.0; G1[NW] = 0.0; G2[NW] = dth; rl[NW] = -cr0;
+        G0[NW + 1] = 0.0; G1[NW + 1] = 0.0; G2[NW + 1] = -cs * c0 - sn * c1; rl[NW + 1] = -cr1;
 #pragma unroll
         for (int a = 0; a < MW; ++a) { Yv[a][0] = hi ? G2[a] : G0[a]; Yv[a][1] = hi ? rl[a] : G1[a]; }
         // LDL^T without pivoting (quasi-definite when the primal block is positive definite), forward substitution
@@ -951,13 +1010,28 @@ __device__ __forceinline__ int local_blocks(const Lay& L, const Sh& S, const Ins
     for (int k = lane; k <= L.N; k += NT) {
         double* H = S.Lall + 36 * k;
         double* lv = S.lall + 8 * k;
+        // the pose block and its gradient are accumulated in registers, each obstacle's Schur complement read as one batch
+        double h0 = H[0], h1 = H[1], h2 = H[2], h3 = H[3], h4 = H[4], h5 = H[5], l0 = lv[0], l1 = lv[1], l2 = lv[2];
+        asm volatile("" : "+v"(h0), "+v"(h1), "+v"(h2), "+v"(h3), "+v"(h4), "+v"(h5), "+v"(l0), "+v"(l1), "+v"(l2));
+        double Hr[6] = {h0, h1, h2, h3, h4, h5}, lr[3] = {l0, l1, l2};
         for (int i = 0; i < L.nO; ++i) {
-            const double* So = S.Sloc + (size_t)(k * L.nO + i) * 12;
+            const double* Sp = S.Sloc + (size_t)(k * L.nO + i) * 12;
+            double So[12];
+#pragma unroll
+            for (int e = 0; e < 12; ++e) So[e] = Sp[e];
+            asm volatile("" : "+v"(So[0]), "+v"(So[1]), "+v"(So[2]), "+v"(So[3]), "+v"(So[4]), "+v"(So[5]), "+v"(So[6]), "+v"(So[7]),
+                              "+v"(So[8]), "+v"(So[9]), "+v"(So[10]), "+v"(So[11]));
+#pragma unroll
             for (int a = 0; a < 3; ++a) {
-                for (int b = 0; b <= a; ++b) H[a * (a + 1) / 2 + b] -= 0.5 * (So[4 * a + b] + So[4 * b + a]);
-                lv[a] += So[4 * a + 3];
+#pragma unroll
+                for (int b = 0; b <= a; ++b) Hr[a * (a + 1) / 2 + b] -= 0.5 * (So[4 * a + b] + So[4 * b + a]);
+                lr[a] += So[4 * a + 3];
             }
         }
+#pragma unroll
+        for (int e = 0; e < 6; ++e) H[e] = Hr[e];
+#pragma unroll
+        for (int a = 0; a < 3; ++a) lv[a] = lr[a];
     }
     SYNC();
     return red_or(bad);
@@ -2179,6 +2253,7 @@ __device__ __forceinline__ void obca_ipm_body(DESC& Ain, const int inst, const b
                     const double Ei = rcp64(q.iDs + q.iDp + q.iDn);
                     S.Einv[r] = Ei;
                     S.gh[r] = gh;
+                    S.tmp[r] = row_soft(L, r) ? y : fma(gh, Ei, y);      // yhat, read by gather_grad<true> (soft rows keep y)
                 }
             }
             SYNC();
