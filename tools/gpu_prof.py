@@ -16,15 +16,23 @@ for _ in range(2):
     out=s.solve(b['variant'],b['x0'],b['u0'],b['xref'],b['A'],b['b'],b['Ts'],b['term'],SolverParams())
 torch.cuda.synchronize()
 p=prof.cpu().numpy(); it=out.iters.cpu().numpy(); nf=out.info[:,3].cpu().numpy()
-if p[:,19].max() > 0 and p[:,18].max() <= p[:,19].max():     # four-wavefront kernels: share of the solves whose sweep ran two-sided
+# Slots 18 / 19 mean different things in different builds.  One-wavefront kernels (shapes of at most 384 rows, include/obca_mpc.h): clocks of
+# rowsteps' slot loop and staging loop.  Four-wavefront kernels: counts of two-sided sweeps, or, in a -DOBCA_TWO_SIDED_CHECK build, step
+# differences -- the two branches below, which therefore only apply above 384 rows (as before the clocks existed; a shape above 384 rows that
+# mode "global1" runs on one wavefront is still read their way).  Rows from the handle: the dual vector is the rows plus two per (stage, obstacle).
+rows = int(s.lib.obca_dual_size(ctypes.byref(s._dims))) - 2*(N+1)*len(b['m'])
+onewave = rows <= 384
+if onewave:
+    pass                                                        # clocks: printed with the others below
+elif p[:,19].max() > 0 and p[:,18].max() <= p[:,19].max():     # four-wavefront kernels: share of the solves whose sweep ran two-sided
     print('two-sided sweeps: %.3f of the solves (%.3f more with E^-1 in (1e6, 4e6])' % (p[:,18].sum()/p[:,19].sum(), p[:,10].sum()/p[:,19].sum()))
     p[:,18:] = 0; p[:,10] = 0
 elif p[:,18].max() > 0:     # library built with -DOBCA_TWO_SIDED_CHECK: slots 18 / 19 hold step differences, not clocks
     print('two-sided vs one-sided sweep, same data: max rel. difference of the step %.2e (median of per-instance maxima %.2e), of the elastic multiplier steps %.2e (median %.2e)'
           % (p[:,18].max()/1e18, np.median(p[:,18])/1e18, p[:,19].max()/1e18, np.median(p[:,19])/1e18))
     p[:,18:] = 0
-names=["grad+err","mu","rowE+gatherB","asm_stages","local","riccati","rowsteps","linesearch","accept","reeval","prologue","loop","r:FG+term","r:phaseA","r:phaseB","r:stage0","r:forward","r:recover","-","-"]
-tot=p[:,:12].sum(1)
+names=["grad+err","mu","rowE+gatherB","asm_stages","local","riccati","rowsteps","linesearch","accept","reeval","prologue","loop","r:FG+term","r:phaseA","r:phaseB","r:stage0","r:forward","r:recover","rs:slotloop","rs:staging"]      # one-wavefront kernels: rowsteps' rolled staging loop (row_jdx) and unrolled slot loop; "rowsteps" is the rest of that phase
+tot=p[:,:12].sum(1)+(p[:,18]+p[:,19] if onewave else 0)
 print('mean iters %.1f nfact %.1f total cycles/solve %.3e'%(it.mean(), nf.mean(), tot.mean()))
 for i,n in enumerate(names):
     print('%-14s %6.2f%%  cycles/iter %9.0f'%(n, 100*p[:,i].sum()/tot.sum(), p[:,i].sum()/it.sum()))

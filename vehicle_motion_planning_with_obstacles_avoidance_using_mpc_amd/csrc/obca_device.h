@@ -183,6 +183,27 @@ constexpr ObcaShapeSizes obca_shape_sizes(int N, int nO, int M) {
     t += OBCA_INST_DOUBLES;
     return ObcaShapeSizes{n_max, R_max, inst_off, t};
 }
+/* Row slots that hold nothing but `mu >= 0` rows.  Thread t owns rows t, t + nt, t + 2 nt, ... (slot j = rows nt j .. nt j + nt - 1,
+   csrc/obca_kernel.hip: Rows), and the mu rows are the layout's last block: they begin at r_mu = r_lam + (N + 1) M, which is largest
+   for obca_mpc4 (three terminal rows and two Topt rows against obca_mpc6's two terminal-set rows and obca_mpc8's none).  First slot j
+   with nt j >= r_mu of every variant: every row of that slot and of the ones behind it has lo = 0, up = +inf, weight 1, is neither an
+   equality nor a soft row, its value is one entry of x and its Jacobian row a unit vector -- whatever the variant of the instance.
+   The compile-time-shape kernels (ShapeIs) drop the bound loads and the equality / upper-bound / weight paths there; a value beyond
+   the kernel's slots (or OBCA_NO_MU_SLOT, the generic kernels) changes nothing. */
+#define OBCA_NO_MU_SLOT (1 << 20)
+constexpr int obca_r_mu(int N, int nO, int M, int variant) {
+    return 3 + 3 * N + (variant == 4 ? 3 : 0) + 2 * (N + 1) + 2 * N + 2 * N + (variant == 4 ? 2 : 0) + (variant == 6 ? 2 : 0) +
+           2 * (N + 1) * nO + (N + 1) * M;
+}
+constexpr int obca_mu_slot(int N, int nO, int M, int nt) {
+    int r = obca_r_mu(N, nO, M, 4);
+    if (obca_r_mu(N, nO, M, 6) > r) r = obca_r_mu(N, nO, M, 6);
+    if (obca_r_mu(N, nO, M, 8) > r) r = obca_r_mu(N, nO, M, 8);
+    return (r + nt - 1) / nt;
+}
+static_assert(obca_mu_slot(5, 3, 6, 64) == 2 && obca_mu_slot(6, 3, 6, 64) == 3 && obca_mu_slot(5, 2, 2, 64) == 2 &&
+              obca_mu_slot(5, 5, 14, 64) == 4 && obca_mu_slot(5, 6, 18, 64) == 4, "mu slots of the one-wavefront shapes");
+static_assert(obca_mu_slot(20, 3, 6, 256) == 2 && obca_mu_slot(20, 5, 14, 256) == 3, "mu slots of the four-wavefront shapes");
 /* Scratch of the second-order correction: the original direction (n_max + R_max + 2 npair doubles) and the accumulated residuals of
    the rows (R_max).  Where it costs no occupancy it lives in LDS BEHIND everything else the kernel carves -- the one-wavefront kernels
    keep as many workgroups per CU as without it (at most four: one wavefront per SIMD at 512 registers), the four-wavefront kernels

@@ -555,55 +555,17 @@ struct Rows<-5> {
 
 struct Err { double E, dual, prim, comp; };
 
-template <int RPL>
-__device__ __forceinline__ Err ipm_errors(const Lay& L, const Sh& S, const Rows<RPL>& W, double mu, double rho, double rxmax,
-                          double crotmax, double nusum, int lane) {
-    double dual = 0.0, prim = 0.0, comp = 0.0, ysum = 0.0, zsum = 0.0, nz = 0.0, nrow = 0.0;
-#pragma unroll
-    for (int j = 0; j < W.slots(); ++j) {
-        const int r = lane + NT * j;
-        if (r < L.R) {
-            const double w = row_w(L, r);
-            const bool eq = row_iseq(L, r);
-            const double lo_ = S.Lb[r], up_ = S.Ub[r];
-            const bool hasL = !eq && lo_ > -INFINITY, hasU = !eq && up_ < INFINITY;
-            const double s = W.s(j), y = S.y[r], p = W.p(j), n = W.n(j);
-            const double zL = hasL ? W.zL(j) : 0.0, zU = hasU ? W.zU(j) : 0.0, zp = W.zp(j), zn = W.zn(j);
-            if (!eq) dual = dmaxabs(dual, -y - zL + zU);
-            dual = dmaxabs(dual, rho - y - zp);
-            dual = dmaxabs(dual, rho + y - zn);
-            prim = dmaxabs(prim, W.g(j) - (eq ? 0.0 : s) - p + n);
-            comp = dmaxabs(comp, p * zp - mu);
-            comp = dmaxabs(comp, n * zn - mu);
-            if (hasL) comp = dmaxabs(comp, (s - lo_) * zL - mu);
-            if (hasU) comp = dmaxabs(comp, (up_ - s) * zU - mu);
-            ysum += w * fabs(y);
-            zsum += w * (zL + zU + zp + zn);
-            nz += w * ((hasL ? 1.0 : 0.0) + (hasU ? 1.0 : 0.0) + 2.0);
-            nrow += w;
-        }
-    }
-    dual = fmax(red_max(dual), rxmax);
-    prim = fmax(red_max(prim), crotmax);
-    comp = red_max(comp);
-    ysum = red_sum(ysum) + nusum;
-    zsum = red_sum(zsum);
-    nz = red_sum(nz);
-    nrow = red_sum(nrow) + 2.0 * L.npair;
-    const double sd = fmax(OBCA_S_MAX, (ysum + zsum) / (nrow + nz)) / OBCA_S_MAX;
-    const double sc = fmax(OBCA_S_MAX, zsum / nz) / OBCA_S_MAX;
-    Err e;
-    e.dual = dual; e.prim = prim; e.comp = comp;
-    e.E = fmax(fmax(dual / sd, prim), comp / sc);
-    return e;
-}
+// slot j holds mu rows only (csrc/obca_device.h: obca_mu_slot).  A constant after unrolling; without a trait (generic kernels) false
+// at compile time, also where the number of slots is a run-time value and the loop stays rolled (rows in memory)
+template <int MUS>
+__device__ __forceinline__ constexpr bool mu_only(int j) { return MUS < OBCA_NO_MU_SLOT && j >= MUS; }
 
 // First evaluation of an iteration: the optimality error at mu = 0 (termination tests) and at the current mu (barrier
 // update) differ only in the complementarity term, and the constraint violation theta, the elastic sum and the largest
 // elastic variable read the same registers -- one pass over the rows instead of three.  nz / nrow (numbers of bound
 // multipliers and of rows) never change and are passed in.  th_lane carries the lane's rotation-row part of theta in.
-struct ErrFirst { Err e0, em; double th, pnsum, emax; };
-template <int RPL>
+struct ErrFirst { Err e0, em; double th, pnsum, emax, dsd, sc; };
+template <int RPL, int MUS>
 __device__ __forceinline__ ErrFirst ipm_errors_first(const Lay& L, const Sh& S, const Rows<RPL>& W, double mu, double rho, double rxmax,
                                      double crotmax, double nusum, double th_lane, double nz, double nrow, int lane) {
     double dual = 0.0, prim = 0.0, comp0 = 0.0, compm = 0.0, ysum = 0.0, zsum = 0.0, th = th_lane, pnsum = 0.0, emax = 0.0;
@@ -611,9 +573,10 @@ __device__ __forceinline__ ErrFirst ipm_errors_first(const Lay& L, const Sh& S, 
     for (int j = 0; j < W.slots(); ++j) {
         const int r = lane + NT * j;
         if (r < L.R) {
-            const double w = row_w(L, r);
-            const bool eq = row_iseq(L, r);
-            const double lo_ = S.Lb[r], up_ = S.Ub[r];
+            const bool muk = mu_only<MUS>(j);
+            const double w = muk ? 1.0 : row_w(L, r);
+            const bool eq = muk ? false : row_iseq(L, r);
+            const double lo_ = muk ? 0.0 : S.Lb[r], up_ = muk ? INFINITY : S.Ub[r];
             const bool hasL = !eq && lo_ > -INFINITY, hasU = !eq && up_ < INFINITY;
             const double s = W.s(j), y = S.y[r], p = W.p(j), n = W.n(j);
             const double zL = hasL ? W.zL(j) : 0.0, zU = hasU ? W.zU(j) : 0.0, zp = W.zp(j), zn = W.zn(j);
@@ -643,9 +606,34 @@ __device__ __forceinline__ ErrFirst ipm_errors_first(const Lay& L, const Sh& S, 
     o.th = red_sum(th); o.pnsum = red_sum(pnsum); o.emax = red_max(emax);
     const double sd = fmax(OBCA_S_MAX, (ysum + zsum) / (nrow + nz)) / OBCA_S_MAX;
     const double sc = fmax(OBCA_S_MAX, zsum / nz) / OBCA_S_MAX;
-    o.e0.dual = dual; o.e0.prim = prim; o.e0.comp = comp0; o.e0.E = fmax(fmax(dual / sd, prim), comp0 / sc);
-    o.em.dual = dual; o.em.prim = prim; o.em.comp = compm; o.em.E = fmax(fmax(dual / sd, prim), compm / sc);
+    o.dsd = dual / sd; o.sc = sc;          // (with e0.prim: what a re-check at another mu composes its E from, ipm_comp below)
+    o.e0.dual = dual; o.e0.prim = prim; o.e0.comp = comp0; o.e0.E = fmax(fmax(o.dsd, prim), comp0 / sc);
+    o.em.dual = dual; o.em.prim = prim; o.em.comp = compm; o.em.E = fmax(fmax(o.dsd, prim), compm / sc);
     return o;
+}
+
+// The barrier update's re-check after a decrease.  Of the optimality error only the complementarity term depends on mu: dual,
+// prim and both scalings are those of ipm_errors_first at the same iterate.  One pass over the rows, one reduction; the caller
+// composes E by the same expression, fmax(fmax(dual / sd, prim), comp / sc).
+template <int RPL, int MUS>
+__device__ __forceinline__ double ipm_comp(const Lay& L, const Sh& S, const Rows<RPL>& W, double mu, int lane) {
+    double comp = 0.0;
+#pragma unroll
+    for (int j = 0; j < W.slots(); ++j) {
+        const int r = lane + NT * j;
+        if (r < L.R) {
+            const bool muk = mu_only<MUS>(j);
+            const bool eq = muk ? false : row_iseq(L, r);
+            const double lo_ = muk ? 0.0 : S.Lb[r], up_ = muk ? INFINITY : S.Ub[r];
+            const bool hasL = !eq && lo_ > -INFINITY, hasU = !eq && up_ < INFINITY;
+            const double s = W.s(j);
+            comp = dmaxabs(comp, W.p(j) * W.zp(j) - mu);
+            comp = dmaxabs(comp, W.n(j) * W.zn(j) - mu);
+            if (hasL) comp = dmaxabs(comp, (s - lo_) * W.zL(j) - mu);
+            if (hasU) comp = dmaxabs(comp, (up_ - s) * W.zU(j) - mu);
+        }
+    }
+    return red_max(comp);
 }
 
 // linearisation of one row at the current iterate: inverse D's and residuals (IPOPT's Sigma + delta_w)
@@ -1794,13 +1782,17 @@ typedef const __attribute__((address_space(4))) ObcaLaunch ObcaLaunchConst;   //
 // The problem shape as the body sees it: ShapeAny -- read from the launch descriptor (any shape the kernel's limits allow);
 // ShapeIs<N, nO, M> -- compile-time constants (csrc/obca_device.h: OBCA_SHAPES): same code, same arithmetic, same results,
 // but every LDS offset, loop bound and index division folds.  The host only launches an instantiation for its own shape.
-struct ShapeAny { static constexpr bool fixed = false; static constexpr int N = 0, nO = 0, M = 0, n_max = 0, R_max = 0, inst_off = 0, soc_lds = 0; };
+struct ShapeAny { static constexpr bool fixed = false; static constexpr int N = 0, nO = 0, M = 0, n_max = 0, R_max = 0, inst_off = 0, soc_lds = 0, mu_slot = OBCA_NO_MU_SLOT; };
 // FT: the fixed-time variants only (the closed loop's groups with sensed boxes: their layouts have three rows less than the
 // free-time layout the handle sizes for, csrc/obca_rollout.hip)
 template <int N_, int NO_, int M_, bool FT = false>
 struct ShapeIs {
     static constexpr bool fixed = true;
     static constexpr int N = N_, nO = NO_, M = M_;
+    // first row slot of mu rows only (csrc/obca_device.h).  One-wavefront kernels only: in the four-wavefront kernels the trait
+    // (2 for (20, 3, 6), 3 for (20, 5, 14) at 256 threads) moved the gated half of C3 by less than its launch spread
+    // (profiles/r21_row_kinds_ab.txt), so they keep the generic row loops
+    static constexpr int mu_slot = OBCA_NT == 64 ? obca_mu_slot(N_, NO_, M_, OBCA_NT) : OBCA_NO_MU_SLOT;
     static constexpr int n_max = obca_shape_sizes(N_, NO_, M_).n_max, R_max = obca_shape_sizes(N_, NO_, M_).R_max - (FT ? 3 : 0),
                          inst_off = obca_shape_sizes(N_, NO_, M_).inst_off;
 #if OBCA_NT == 64
@@ -1912,6 +1904,10 @@ __device__ __forceinline__ void obca_ipm_body(DESC& Ain, const int inst, const b
     // the stage-serial sweep touches -- O(N) doubles -- lives in LDS, everything that grows with the number of rows or
     // variables in this instance's slice of the HBM workspace (stays in L2: ~1 MB per instance at N = 74) -----------------
     constexpr bool GM = (RPL == 0);
+    // Slots j >= MUS of the unrolled row loops hold mu rows only (csrc/obca_device.h: obca_mu_slot): lo = 0, up = +inf, weight 1,
+    // no equality.  There the loops name these constants instead of loading the bounds and deriving the flags; j is a constant
+    // after unrolling, so the compiler drops the untaken branches.  The generic kernels have no such slot.
+    constexpr int MUS = SHAPE::mu_slot;
     Sh S;
     Rows<RPL> W;
     {
@@ -2098,8 +2094,9 @@ __device__ __forceinline__ void obca_ipm_body(DESC& Ain, const int inst, const b
             W.zL(j) = 0.0; W.zU(j) = 0.0; W.zp(j) = 1.0; W.zn(j) = 1.0; W.g(j) = 0.0; W.dy(j) = 0.0;
             W.iDs(j) = 0.0; W.iDp(j) = 1.0; W.iDn(j) = 1.0; W.rs(j) = 0.0; W.rp(j) = 0.0; W.rn(j) = 0.0;
             if (r < L.R) {
-                const double lo = S.Lb[r], up = S.Ub[r];
-                const bool eq = row_iseq(L, r);
+                const bool muk = mu_only<MUS>(j);
+                const double lo = muk ? 0.0 : S.Lb[r], up = muk ? INFINITY : S.Ub[r];
+                const bool eq = muk ? false : row_iseq(L, r);
                 const double g = S.tmp[r];
                 double s = g;
                 const bool hasL = lo > -INFINITY, hasU = up < INFINITY;
@@ -2137,6 +2134,7 @@ __device__ __forceinline__ void obca_ipm_body(DESC& Ain, const int inst, const b
     for (int j = 0; j < W.slots(); ++j) {
         const int r = lane + NT * j;
         if (r < L.R) {
+            if (mu_only<MUS>(j)) { cnt_nz += 3.0; cnt_rows += 1.0; continue; }      // a lower bound and the elastic pair, weight 1
             const double w = row_w(L, r);
             const bool eq = row_iseq(L, r);
             cnt_nz += w * (((!eq && S.Lb[r] > -INFINITY) ? 1.0 : 0.0) + ((!eq && S.Ub[r] < INFINITY) ? 1.0 : 0.0) + 2.0);
@@ -2187,7 +2185,7 @@ __device__ __forceinline__ void obca_ipm_body(DESC& Ain, const int inst, const b
         for (int t = lane; t < L.n; t += NT) rxmax = dmaxabs(rxmax, S.bx[t]);
         for (int t = lane; t < 2 * L.npair; t += NT) { crotmax = dmaxabs(crotmax, S.crot[t]); nusum += fabs(S.nu[t]); th += fabs(S.crot[t]); }
         rxmax = red_max(rxmax); crotmax = red_max(crotmax); nusum = red_sum(nusum);
-        const ErrFirst ef = ipm_errors_first<RPL>(L, S, W, mu, rho, rxmax, crotmax, nusum, th, GET(IV_CNTNZ), GET(IV_CNTROWS), lane);
+        const ErrFirst ef = ipm_errors_first<RPL, MUS>(L, S, W, mu, rho, rxmax, crotmax, nusum, th, GET(IV_CNTNZ), GET(IV_CNTROWS), lane);
         th = ef.th; pnsum = ef.pnsum; PUT(IV_EMAX, ef.emax);
         const Err e0 = ef.e0;
         const double E0 = e0.E;
@@ -2209,9 +2207,10 @@ __device__ __forceinline__ void obca_ipm_body(DESC& Ain, const int inst, const b
             const double mu_floor = O.tol / (OBCA_KAPPA_EPS + 1.0);
             bool first_mu = true;
             while (mu > mu_floor) {
-                const Err em = first_mu ? ef.em : ipm_errors<RPL>(L, S, W, mu, rho, rxmax, crotmax, nusum, lane);
+                // (after a decrease only the complementarity term is formed again: nothing else of E depends on mu)
+                const double Em = first_mu ? ef.em.E : fmax(fmax(ef.dsd, ef.e0.prim), ipm_comp<RPL, MUS>(L, S, W, mu, lane) / ef.sc);
                 first_mu = false;
-                if (em.E > OBCA_KAPPA_EPS * mu) break;
+                if (Em > OBCA_KAPPA_EPS * mu) break;
                 mu = fmax(mu_floor, fmin(OBCA_KAPPA_MU * mu, mu * sqrt(mu)));      // mu^theta_mu, theta_mu = 1.5
                 PUT(IV_TAU, fmax(OBCA_TAU_MIN, 1.0 - mu));
                 PUT(IV_PHIK, NAN);                 // the barrier function has changed
@@ -2243,9 +2242,10 @@ __device__ __forceinline__ void obca_ipm_body(DESC& Ain, const int inst, const b
             for (int j = 0; j < W.slots(); ++j) {
                 const int r = lane + NT * j;
                 if (r < L.R) {
-                    const bool eq = row_iseq(L, r);
+                    const bool muk = mu_only<MUS>(j);
+                    const bool eq = muk ? false : row_iseq(L, r);
                     const double y = S.y[r];
-                    const double lo_ = S.Lb[r], up_ = S.Ub[r];
+                    const double lo_ = muk ? 0.0 : S.Lb[r], up_ = muk ? INFINITY : S.Ub[r];
                     const Lin q = row_lin(lo_, up_, eq, W.s(j), W.p(j), W.n(j), y, W.zL(j), W.zU(j), W.zp(j),
                                           W.zn(j), mu, rho, delta_w);
                     const double rg = soc_pass ? ws_gsoc[r] : W.g(j) - (eq ? 0.0 : W.s(j)) - W.p(j) + W.n(j);
@@ -2253,7 +2253,7 @@ __device__ __forceinline__ void obca_ipm_body(DESC& Ain, const int inst, const b
                     const double Ei = rcp64(q.iDs + q.iDp + q.iDn);
                     S.Einv[r] = Ei;
                     S.gh[r] = gh;
-                    S.tmp[r] = row_soft(L, r) ? y : fma(gh, Ei, y);      // yhat, read by gather_grad<true> (soft rows keep y)
+                    S.tmp[r] = (!muk && row_soft(L, r)) ? y : fma(gh, Ei, y);      // yhat, read by gather_grad<true> (soft rows keep y)
                 }
             }
             SYNC();
@@ -2335,13 +2335,17 @@ __device__ __forceinline__ void obca_ipm_body(DESC& Ain, const int inst, const b
         const double tau = GET(IV_TAU);
         for (int r = lane; r < L.R; r += NT)
             S.tmp[r] = row_soft(L, r) ? S.dy[r] : (row_jdx(L, S, in, r) + S.gh[r]) * S.Einv[r];
+#if OBCA_NT == 64
+        PROF(19)         // rowsteps in three parts (one-wavefront kernels, where slots 18 / 19 are free): 19 the rolled staging loop above,
+#endif                   // 18 the unrolled slot loop, 6 the rest (objective part of dphi, reductions, the switching condition's powers)
 #pragma unroll
         for (int j = 0; j < W.slots(); ++j) {
             const int r = lane + NT * j;
             if (r < L.R) {
-                const bool eq = row_iseq(L, r);
-                const double lo_ = S.Lb[r], up_ = S.Ub[r];
-            const bool hasL = !eq && lo_ > -INFINITY, hasU = !eq && up_ < INFINITY;
+                const bool muk = mu_only<MUS>(j);
+                const bool eq = muk ? false : row_iseq(L, r);
+                const double lo_ = muk ? 0.0 : S.Lb[r], up_ = muk ? INFINITY : S.Ub[r];
+                const bool hasL = !eq && lo_ > -INFINITY, hasU = !eq && up_ < INFINITY;
                 const double dy = S.tmp[r];
                 W.dy(j) = dy;
                 {   // cached for the line search and the update (not kept live across the factorisation)
@@ -2349,7 +2353,7 @@ __device__ __forceinline__ void obca_ipm_body(DESC& Ain, const int inst, const b
                                           W.zn(j), mu, rho, delta_w);
                     W.iDs(j) = q.iDs; W.iDp(j) = q.iDp; W.iDn(j) = q.iDn; W.rs(j) = q.rs; W.rp(j) = q.rp; W.rn(j) = q.rn;
                 }
-                const double w = row_w(L, r);
+                const double w = muk ? 1.0 : row_w(L, r);
                 const double ds = (dy - W.rs(j)) * W.iDs(j);
                 const double dp = (dy - W.rp(j)) * W.iDp(j);
                 const double dn = (-dy - W.rn(j)) * W.iDn(j);
@@ -2378,6 +2382,9 @@ __device__ __forceinline__ void obca_ipm_body(DESC& Ain, const int inst, const b
                 dphi += w * (gs * ds + (rho - mu * ip) * dp + (rho - mu * inn) * dn);
             }
         }
+#if OBCA_NT == 64
+        PROF(18)
+#endif
         for (int t = lane; t < L.n; t += NT) {                       // same lane <-> entry assignment as a dense gradient
             const int k = t / L.NS, q = t - k * L.NS;
             if (L.free_T && t == L.iT()) dphi += S.gf[L.igT()] * S.dx[t];
@@ -2389,11 +2396,17 @@ __device__ __forceinline__ void obca_ipm_body(DESC& Ain, const int inst, const b
         double pw_th = 0.0, pw_dphi = 1.0;
         double alpha = a_max, a_try = a_max, th_old = 0.0;
         if (!soc_pass) {
+            // The two powers (161 instructions each) are read under th <= theta_min only -- here and in the line search's switching
+            // condition, which a corrected pass meets with the same th -- so only then are they formed.  They are the same in every
+            // lane: read back from lane 0 they are scalars, and no vector register carries them through the line search.
+            const bool sw = dphi < 0.0 && th <= GET(IV_THMIN);
+            if (sw) {
+                pw_th = lane_read(dpow(th, OBCA_S_THETA), 0);
+                pw_dphi = lane_read(dpow(-dphi, OBCA_S_PHI), 0);
+            }
             if (dphi < 0.0) {
-                pw_th = dpow(th, OBCA_S_THETA);
-                pw_dphi = dpow(-dphi, OBCA_S_PHI);
                 double c = fmin(OBCA_GAMMA_THETA, OBCA_GAMMA_PHI * th / (-dphi));
-                if (th <= GET(IV_THMIN)) c = fmin(c, OBCA_DELTA * pw_th / pw_dphi);
+                if (sw) c = fmin(c, OBCA_DELTA * pw_th / pw_dphi);
                 alpha_min = OBCA_GAMMA_ALPHA * c;
             } else alpha_min = OBCA_GAMMA_ALPHA * OBCA_GAMMA_THETA;
             first_trial = true; use_soc = false; soc_it = 0;
@@ -2418,9 +2431,10 @@ __device__ __forceinline__ void obca_ipm_body(DESC& Ain, const int inst, const b
             for (int j = 0; j < W.slots(); ++j) {
                 const int r = lane + NT * j;
                 if (r < L.R) {
-                    const bool eq = row_iseq(L, r);
-                    const double dy = W.dy(j), w = row_w(L, r);
-                    const double lo_ = S.Lb[r], up_ = S.Ub[r];
+                    const bool muk = mu_only<MUS>(j);
+                    const bool eq = muk ? false : row_iseq(L, r);
+                    const double dy = W.dy(j), w = muk ? 1.0 : row_w(L, r);
+                    const double lo_ = muk ? 0.0 : S.Lb[r], up_ = muk ? INFINITY : S.Ub[r];
                     const double st = eq ? 0.0 : W.s(j) + a_try * (dy - W.rs(j)) * W.iDs(j);
                     const double pt = W.p(j) + a_try * (dy - W.rp(j)) * W.iDp(j);
                     const double nt = W.n(j) + a_try * (-dy - W.rn(j)) * W.iDn(j);
@@ -2446,7 +2460,7 @@ __device__ __forceinline__ void obca_ipm_body(DESC& Ain, const int inst, const b
             const bool blocked = (th_t >= GET(IV_THMAX)) || red_or(f_valid && th_t >= f_th && phi_t >= f_phi);
 #endif
             if (finite && !blocked) {
-                const bool switching = dphi < 0.0 && alpha * pw_dphi > OBCA_DELTA * pw_th;
+                const bool switching = dphi < 0.0 && alpha * pw_dphi > OBCA_DELTA * pw_th;      // (the powers: only valid under th <= theta_min)
                 if (th <= GET(IV_THMIN) && switching) {
                     ok = phi_t <= phi + OBCA_ETA_PHI * alpha * dphi + 10.0 * 2.220446049250313e-16 * fabs(phi);
                 } else {
@@ -2480,7 +2494,7 @@ __device__ __forceinline__ void obca_ipm_body(DESC& Ain, const int inst, const b
                 for (int j = 0; j < W.slots(); ++j) {
                     const int r = lane + NT * j;
                     if (r < L.R) {
-                        const bool eq = row_iseq(L, r);
+                        const bool eq = mu_only<MUS>(j) ? false : row_iseq(L, r);
                         const double dy = W.dy(j);
                         const double st = eq ? 0.0 : W.s(j) + a_try * (dy - W.rs(j)) * W.iDs(j);
                         const double pt = W.p(j) + a_try * (dy - W.rp(j)) * W.iDp(j);
@@ -2539,9 +2553,10 @@ __device__ __forceinline__ void obca_ipm_body(DESC& Ain, const int inst, const b
         for (int j = 0; j < W.slots(); ++j) {
             const int r = lane + NT * j;
             if (r < L.R) {
-                const bool eq = row_iseq(L, r);
-                const double lo_ = S.Lb[r], up_ = S.Ub[r];
-            const bool hasL = !eq && lo_ > -INFINITY, hasU = !eq && up_ < INFINITY;
+                const bool muk = mu_only<MUS>(j);
+                const bool eq = muk ? false : row_iseq(L, r);
+                const double lo_ = muk ? 0.0 : S.Lb[r], up_ = muk ? INFINITY : S.Ub[r];
+                const bool hasL = !eq && lo_ > -INFINITY, hasU = !eq && up_ < INFINITY;
                 const double dy = W.dy(j);
                 const double dyz = use_soc ? ws_dyo[r] : dy;
                 const double ds = (dy - W.rs(j)) * W.iDs(j);
@@ -2821,6 +2836,8 @@ __device__ __forceinline__ void solve_with_escalation(const ObcaLaunch& A, const
     }
 OBCA_TU_SHAPE(OBCA_DEFINE_SHAPE_KERNEL)
 #elif OBCA_NT == 64
+// internal (not part of the C ABI; tests/test_row_kinds.py): the slot trait the compile-time-shape kernels are built with
+extern "C" int obca_internal_mu_slot(int N, int nO, int M, int nt) { return obca_mu_slot(N, nO, M, nt); }
 extern "C" __global__ void __launch_bounds__(64) obca_ipm_kernel_r4(ObcaLaunch A, ObcaLaunch A2, ObcaLaunch A3) { solve_with_escalation<4, OBCA_LOOP_R4>(A, A2, A3); }
 extern "C" __global__ void __launch_bounds__(64) obca_ipm_kernel_r5(ObcaLaunch A, ObcaLaunch A2, ObcaLaunch A3) { solve_with_escalation<5, OBCA_LOOP_R56>(A, A2, A3); }
 extern "C" __global__ void __launch_bounds__(64) obca_ipm_kernel_r6(ObcaLaunch A, ObcaLaunch A2, ObcaLaunch A3) { solve_with_escalation<6, OBCA_LOOP_R56>(A, A2, A3); }
