@@ -845,8 +845,81 @@ typedef struct obca_fleet {
 void obca_fleet_init(obca_fleet* d);
 int obca_fleet_step(const obca_fleet* d, int32_t measure, int32_t device, void* hip_stream);
 
+/* ------------------------------------------------------------------------------------------------------
+ * Fleet closed loop, prediction by plans (obca_mpc 0.19), on the device.  obca_fleet_step predicts another car as a rectangle
+ * that translates at its last speed; the N-stage plan that car has just solved says where it will be, and how it will be
+ * turned, at exactly the stage times of the other cars' next solves.  Two calls: obca_fleet_tracks turns the plans just applied
+ * into rows per stage (a track per car), obca_scene_select_staged is obca_scene_select with such rows for the last Kt slots.
+ * One step of the loop: obca_scene_select_staged (Kt = V, stage_group = V, the tracks and track_ok of the last step),
+ * obca_solve_batch, obca_pool_loop_advance, obca_fleet_step (OBCA_FLEET_PREDICT_VELOCITY: the pool slots stay the velocity
+ * prediction, the fallback for a car without a usable plan and what obca_pool_loop_advance's clearance measures), then
+ * obca_fleet_tracks with the solve just applied.  A start zeroes track_ok.
+ *
+ * obca_fleet_tracks, B = G V, car j of world g is rollout q = g V + j:
+ *   usable plan   flags[q] == OBCA_RUN, k[q] == step + 1 (the car applied this loop step), status[q] 0 or 1, and all
+ *                 3 (N + 1) words of xopt[q] finite
+ *   stage poses   the next solve starts one step later, so its stage kk is knot kk + 1 of this plan: xopt[q,:,kk+1] for
+ *                 kk < N; for kk = N the position x_N + (x_N - x_N-1) (each operation rounded on its own) with the heading of
+ *                 knot N
+ *   track         track_A / track_b[g,j,kk] = the four rows obca_fleet_step writes for a car at that pose (its rectangle
+ *                 grown by margin).  obca_pool_loop_advance copied knot 1 to x0, so stage 0 holds the words of the pool slot.
+ *                 Without a usable plan every stage holds the rows at x0[q], or the spare's where that pose is not finite.
+ *   track_ok      [B,V]: track_ok[g V + a, j] = 1 where the plan of car j is usable and slot Ks + j of car a is no spare
+ *                 (obca_fleet_step's rule: j == a, see == OBCA_FLEET_SEE_LOWER and j > a, a pose word that is not finite)
+ * Nothing written is NaN as long as the rows of the poses are finite (poses below 1e150 m).  G >= 1, 1 <= V <= 16,
+ * 1 <= N <= 127, step >= 0, see one of its two values, margin >= 0, far > 0 and ego finite, struct_size ==
+ * sizeof(struct obca_fleet_tracks), device >= 0, no pointer NULL.  Every argument is checked before the first HIP call; a refused
+ * call (OBCA_E_INVAL) has no side effect.  Asynchronous on hip_stream; csrc/obca_fleet_tracks_core.h is the serial definition. */
+struct obca_fleet_tracks {
+    uint32_t struct_size;              /* sizeof(struct obca_fleet_tracks): set by obca_fleet_tracks_init() */
+    uint32_t reserved_;
+    int32_t G, V, N, step, see;
+    int32_t reserved2_;
+    double margin, far;                /* obca_fleet_tracks_init: 0 and 100 */
+    double ego[4];                     /* obca_fleet_tracks_init: 1.7, 0.75, 1.7, 0.75 */
+    /* read-only, B = G V, as they are after obca_fleet_step */
+    const double* x0;                  /* [B,3] */
+    const int32_t* flags;              /* [B] */
+    const int32_t* k;                  /* [B] */
+    const double* xopt;                /* [B,3,N+1] the solve that was just applied */
+    const int32_t* status;             /* [B] */
+    /* written */
+    double* track_A;                   /* [G,V,N+1,4,2] one track per car per world, shared by its observers */
+    double* track_b;                   /* [G,V,N+1,4] */
+    int32_t* track_ok;                 /* [B,V] what observer b = g V + a may use of car j */
+};   /* no typedef: the call has the descriptor's name, so C and C++ say `struct obca_fleet_tracks` */
+
+/* zero-fills *d and sets struct_size, far and ego: the one way to start filling an obca_fleet_tracks */
+void obca_fleet_tracks_init(struct obca_fleet_tracks* d);
+int obca_fleet_tracks(const struct obca_fleet_tracks* d, int32_t device, void* hip_stream);
+
+/* obca_scene_select with rows per stage for the last Kt pool slots.  The arguments are obca_scene_select's and
+ *   Kt            0 <= Kt <= K
+ *   stage_group   >= 1, B % stage_group == 0: instance b reads block b / stage_group (a fleet passes V)
+ *   stage_A       [B/stage_group, Kt, N+1, E, 2], stage_b [B/stage_group, Kt, N+1, E], stage_ok [B,Kt]; NULL only with Kt = 0
+ * Pool slot K - Kt + t of instance b is staged where stage_ok[b,t] != 0: its rows at stage kk are stage_A / stage_b[b /
+ * stage_group, t, kk] and its pool_v plays no part in them (its pool words are still checked).  Every other slot, and a
+ * staged slot with stage_ok == 0, behaves exactly as in obca_scene_select.  The samples of a staged slot are the same (x0
+ * against stage 0, per interval the n_sub + 1 samples, variant 4: stage 0 at every sample); at sample j of interval s its rows
+ * are A and b interpolated entry by entry between stages s and s + 1 (obca_plan_sweep's rule for rows per stage; the distance
+ * normalises the slightly shorter normals of a rectangle that turns).  Ranking, sel, variant_out and min_clear are unchanged;
+ * a selected staged slot hands its stage rows to A_out / b_out as they are.  Unusable as well: a staged row word that is not
+ * finite, a staged row a = (0, 0) at any stage of a slot with stage_ok != 0.  With Kt = 0 or every stage_ok 0 every output is
+ * obca_scene_select's word for word, and so it is for a track that holds obca_scene_select's own stage rows. */
+int obca_scene_select_staged(const double ego[4], int32_t B, int32_t K, int32_t E, int32_t N, int32_t n_sel, int32_t n_sub,
+                             int32_t accumulate, const double* pool_A, const double* pool_b, const double* pool_v /* or NULL */,
+                             const double* Ts /* [B] */, const double* x, const double* x0 /* [B,3] or NULL */,
+                             const int32_t* variant /* [B] or NULL */, const int32_t* status /* [B] or NULL */, int32_t Kt,
+                             int32_t stage_group, const double* stage_A, const double* stage_b, const int32_t* stage_ok,
+                             double* score /* [B,K] */, int32_t* sel /* [B,n_sel] */, double* A_out, double* b_out,
+                             int32_t* variant_out /* [B] */, int32_t* ok_out /* [B] */, double* min_clear /* [B] or NULL */,
+                             int32_t device, void* hip_stream);
+
 const char* obca_strerror(int code);
-/* "obca_mpc 0.18 (gfx950)": 0.18 = fleet closed loop (obca_fleet_step);
+/* "obca_mpc 0.18 (gfx950)" -- the string still reads 0.18: 0.19 adds calls and changes no existing word, and callers detect
+ * it by the exported symbols obca_fleet_tracks / obca_scene_select_staged.
+ * 0.19 = fleet prediction by plans (obca_fleet_tracks, obca_scene_select_staged);
+ * 0.18 = fleet closed loop (obca_fleet_step);
  * 0.17 = opt-in path time bound of obca_mpc4 (obca_params.time_bound, OBCA_TIME_BOUND_PATH);
  * 0.16 = closed loop over scene pools (obca_pool_loop_advance);
  * 0.15 = occupancy grids to scene pools (obca_grid_pool);

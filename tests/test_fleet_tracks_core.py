@@ -1,0 +1,329 @@
+"""CPU tier of the fleet tracks (csrc/obca_fleet_tracks_core.h: the serial definition of obca_fleet_tracks), built for the host
+from tests/native/fleet_tracks_host.cpp.
+
+Yardstick: ``ref_tracks``, a numpy restatement of the rules -- which plans are usable, knot kk + 1 as stage kk, the
+extrapolated last stage with one rounding per operation, ``test_fleet_core.ref_car_rows`` for the rows, the mask -- compared
+on every written buffer, each of which sits between guard bands.
+
+Words and bounds.  Everything without sin or cos is word for word: the masks, the spares, and the rows of worlds at heading 0
+with dyadic coordinates (``exact``).  At general headings the rows are within tests/test_fleet_core.py's A_TOL / ROW_TOL,
+derived there for coordinates below 100 m; the worlds here stay below 100 m.  The helpers are shared with
+tests/test_gpu_fleet_plan.py."""
+import ctypes
+import os
+
+import numpy as np
+import pytest
+
+from tests import native_build, test_fleet_core as core, test_scene_core as tsc
+from vehicle_motion_planning_with_obstacles_avoidance_using_mpc_amd import _lib
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+SRC = os.path.join(HERE, "native", "fleet_tracks_host.cpp")
+DEPS = [SRC, os.path.join(core.CSRC, "obca_fleet_tracks_core.h")] + core.DEPS[1:]
+E_INVAL = core.E_INVAL
+RUN, GOAL, CAP, FAILED, COLLISION = core.RUN, core.GOAL, core.CAP, core.FAILED, core.COLLISION
+FILL_X, FILL_I = core.FILL_X, core.FILL_I
+READ = ("x0", "flags", "k", "xopt", "status")
+WRITTEN = ("track_A", "track_b", "track_ok")
+INT = ("flags", "k", "status", "track_ok")
+
+
+def load_host():
+    lib = native_build.build_shim("fleet_tracks_host", [SRC], DEPS)
+    lib.fleet_tracks_host.restype = ctypes.c_int
+    lib.fleet_tracks_host.argtypes = [ctypes.c_void_p]
+    lib.fleet_tracks_layout_host.restype = ctypes.c_int
+    return lib
+
+
+@pytest.fixture(scope="module")
+def host():
+    return load_host()
+
+
+@pytest.fixture(scope="module")
+def fleet_host():
+    return core.load_host()
+
+
+def shapes(G, V, N):
+    B = G * V
+    return {"x0": (B, 3), "flags": (B,), "k": (B,), "xopt": (B, 3, N + 1), "status": (B,), "track_A": (G, V, N + 1, 4, 2),
+            "track_b": (G, V, N + 1, 4), "track_ok": (B, V)}
+
+
+class Case:
+    """the buffers of one obca_fleet_tracks in host memory, every one between guard bands, and the scalars"""
+
+    def __init__(self, G, V, N=5, step=0, see=core.SEE_ALL, margin=0.0, far=100.0, ego=core.EGO, exact=False):
+        self.dims = dict(G=G, V=V, N=N, step=step, see=see)
+        self.margin, self.far, self.ego, self.exact = margin, far, tuple(ego), exact
+        self.whole, self.a = {}, {}
+        for name, shape in shapes(G, V, N).items():
+            dt, fill = (np.int32, FILL_I) if name in INT else (np.float64, FILL_X)
+            self.whole[name], self.a[name] = tsc.banded(shape, dt, fill)
+
+    def __getitem__(self, name):
+        return self.a[name]
+
+    def descriptor(self, null=(), **over):
+        d = _lib.ObcaFleetTracks()
+        for k, v in self.dims.items():
+            setattr(d, k, v)
+        d.margin, d.far = self.margin, self.far
+        d.ego = (ctypes.c_double * 4)(*self.ego)
+        for name, arr in self.a.items():
+            setattr(d, name, None if name in null else arr.ctypes.data)
+        for k, v in over.items():
+            setattr(d, k, v)
+        return d
+
+    def snapshot(self):
+        return {k: v.copy() for k, v in self.whole.items()}
+
+    def bands_clean(self):
+        return all(tsc.band_clean(w, FILL_I if k in INT else FILL_X) for k, w in self.whole.items())
+
+
+def tracks_host(host, case, rc=0, null=(), **over):
+    d = case.descriptor(null=null, **over)
+    assert host.fleet_tracks_host(ctypes.byref(d)) == rc
+
+
+# ------------------------------------------------------------------------------------------------ the numpy restatement
+def ref_usable(case):
+    a, dm = case.a, case.dims
+    return (a["flags"] == RUN) & (a["k"] == dm["step"] + 1) & np.isin(a["status"], (0, 1)) & \
+        np.all(np.isfinite(a["xopt"]), axis=(1, 2))
+
+
+def ref_stage_pose(xo, N, kk):
+    """the pose of stage kk of the next solve from the plan xo [3,N+1], one rounding per operation"""
+    if kk < N:
+        return xo[:, kk + 1].copy()
+    return np.array([xo[0, N] + (xo[0, N] - xo[0, N - 1]), xo[1, N] + (xo[1, N] - xo[1, N - 1]), xo[2, N]])
+
+
+def ref_tracks(case):
+    """what the call must leave in the written buffers; also ``_car`` [G,V] bool: the tracks that hold a car's rows (their
+    words involve sin / cos) and not the spare's"""
+    a, dm = case.a, case.dims
+    G, V, N = dm["G"], dm["V"], dm["N"]
+    use = ref_usable(case)
+    out = {k: a[k].copy() for k in WRITTEN}
+    car = np.zeros((G, V), bool)
+    sA, sb = core.ref_spare_rows(case.far)
+    for g in range(G):
+        for j in range(V):
+            q = g * V + j
+            fin = bool(np.all(np.isfinite(a["x0"][q])))
+            car[g, j] = use[q] or fin
+            for kk in range(N + 1):
+                if use[q]:
+                    out["track_A"][g, j, kk], out["track_b"][g, j, kk] = core.ref_car_rows(ref_stage_pose(a["xopt"][q], N, kk), case.ego,
+                                                                                         case.margin)
+                elif fin:
+                    out["track_A"][g, j, kk], out["track_b"][g, j, kk] = core.ref_car_rows(a["x0"][q], case.ego, case.margin)
+                else:
+                    out["track_A"][g, j, kk], out["track_b"][g, j, kk] = sA, sb
+        for i in range(V):
+            for j in range(V):
+                spare = j == i or (dm["see"] == core.SEE_LOWER and j > i) or not np.all(np.isfinite(a["x0"][g * V + j]))
+                out["track_ok"][g * V + i, j] = 1 if (use[g * V + j] and not spare) else 0
+    out["_car"] = car
+    return out
+
+
+def compare(case, got, want, label=""):
+    """``got`` against ``want`` (``ref_tracks``' dict, or another implementation's buffers with ``_car`` added): masks and
+    spares word for word, the rows of cars word for word on ``exact`` worlds and within A_TOL / ROW_TOL elsewhere.  Returns the
+    largest row deviation."""
+    assert core.same_words(got["track_ok"], want["track_ok"]), (label, "track_ok")
+    car = want["_car"]
+    worst = 0.0
+    for name, tol in (("track_A", core.A_TOL), ("track_b", core.ROW_TOL)):
+        g, w = got[name], want[name]
+        assert not np.isnan(g).any(), (label, name)
+        assert core.same_words(g[~car], w[~car]), (label, name, "spares")
+        if case.exact:
+            assert core.same_words(g[car], w[car]), (label, name, "cars")
+        elif car.any():
+            dev = float(np.max(np.abs(g[car] - w[car])))
+            worst = max(worst, dev)
+            assert dev <= tol, (label, name, dev)
+    return worst
+
+
+def car_mask(case):
+    """[G,V] bool: the tracks that hold a car's rows, from the buffers as they are"""
+    dm = case.dims
+    return (ref_usable(case) | np.all(np.isfinite(case["x0"]), axis=1)).reshape(dm["G"], dm["V"])
+
+
+def check_call(host, case, label=""):
+    """one call of the host core against ref_tracks; the read-only buffers and every guard band untouched"""
+    want = ref_tracks(case)
+    before = {k: case.a[k].copy() for k in READ}
+    tracks_host(host, case)
+    out = compare(case, case.a, want, label=label)
+    for name in READ:
+        assert core.same_words(case.a[name], before[name]), name
+    assert case.bands_clean()
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ worlds
+def fill_plans(case, rng, heading=np.pi):
+    """every car has just applied a feasible plan: N + 1 knots of about 0.5 m steps that turn gently, knot 1 copied to x0 (what
+    obca_pool_loop_advance does), k = step + 1, flags RUN, status 0 / 1.  ``exact`` worlds: heading 0 and dyadic numbers."""
+    dm = case.dims
+    G, V, N, step = dm["G"], dm["V"], dm["N"], dm["step"]
+    for g in range(G):
+        for j in range(V):
+            q = g * V + j
+            if case.exact:
+                xs = 4.0 * j + 0.25 * g + 0.5 * np.arange(N + 1) + 0.125 * (np.arange(N + 1) % 3)
+                case["xopt"][q] = np.stack([xs, np.full(N + 1, 5.0 + 0.125 * (j % 3)), np.zeros(N + 1)])
+            else:
+                th = rng.uniform(-heading, heading)
+                p = np.array([4.0 * (j % 8) + rng.uniform(-0.3, 0.3), 5.0 + rng.uniform(-0.5, 0.5)])
+                for t in range(N + 1):
+                    case["xopt"][q, :, t] = (p[0], p[1], th)
+                    th += rng.uniform(-0.1, 0.1)
+                    p = p + rng.uniform(0.05, 0.4) * np.array([np.cos(th), np.sin(th)])
+            case["x0"][q] = case["xopt"][q, :, 1]
+    case["flags"][...] = RUN
+    case["k"][...] = step + 1
+    case["status"][...] = (np.arange(G * V) % 2).astype(np.int32)
+    return case
+
+
+# ------------------------------------------------------------------------------------------------ tests
+@pytest.mark.parametrize("see", (core.SEE_ALL, core.SEE_LOWER), ids=("all", "lower"))
+@pytest.mark.parametrize("shape", [(1, 1, 1), (3, 3, 5), (2, 16, 7), (1, 16, 1), (1, 2, 127)], ids=lambda s: "G%d_V%d_N%d" % s)
+def test_tracks_match_numpy(host, shape, see):
+    """usable plans everywhere: word for word at heading 0, within the derived bounds elsewhere; V = 1 has no mask word set,
+    under "lower" only the lower triangle is"""
+    G, V, N = shape
+    rng = np.random.default_rng(10 * G + V + N)
+    worst = 0.0
+    for exact in (True, False):
+        case = fill_plans(Case(G, V, N, step=3, see=see, margin=0.25, exact=exact), rng)
+        worst = max(worst, check_call(host, case, label=(shape, see, exact)))
+        ok = case["track_ok"].reshape(G, V, V)
+        i, j = np.arange(V)[:, None], np.arange(V)[None, :]
+        want = (j != i) & ((j < i) | (see == core.SEE_ALL))
+        assert np.array_equal(ok, np.broadcast_to(want, (G, V, V)).astype(np.int32))
+    print("G %d V %d N %d: largest |b - numpy| %.3e (bound %.3e)" % (G, V, N, worst, core.ROW_TOL))
+
+
+def test_stage_zero_is_the_pool_slot_and_the_last_stage_is_extrapolated(host, fleet_host):
+    """stage 0 of a usable plan is fleet_car_rows_host at x0, word for word at every heading (knot 1 was copied to x0); stage N
+    is the rows at x_N + (x_N - x_N-1) with the heading of knot N, checked against fleet_car_rows_host on the pose computed
+    here, word for word"""
+    rng = np.random.default_rng(41)
+    for exact in (True, False):
+        case = fill_plans(Case(2, 3, 5, margin=0.1, exact=exact, ego=core.EGO_OFF), rng)
+        tracks_host(host, case)
+        e = np.array(case.ego, float)
+        for q in range(6):
+            g, j = divmod(q, 3)
+            A, b = np.zeros((4, 2)), np.zeros(4)
+            fleet_host.fleet_car_rows_host(case["x0"][q].ctypes.data, e.ctypes.data, 0.1, A.ctypes.data, b.ctypes.data)
+            assert core.same_words(case["track_A"][g, j, 0], A) and core.same_words(case["track_b"][g, j, 0], b)
+            xo = case["xopt"][q]
+            last = np.array([xo[0, 5] + (xo[0, 5] - xo[0, 4]), xo[1, 5] + (xo[1, 5] - xo[1, 4]), xo[2, 5]])
+            fleet_host.fleet_car_rows_host(last.ctypes.data, e.ctypes.data, 0.1, A.ctypes.data, b.ctypes.data)
+            assert core.same_words(case["track_A"][g, j, 5], A) and core.same_words(case["track_b"][g, j, 5], b)
+            assert not core.same_words(case["track_b"][g, j, 5], case["track_b"][g, j, 4])
+            for kk in range(5):                                                # knot kk + 1 is stage kk
+                pose = np.ascontiguousarray(xo[:, kk + 1])
+                fleet_host.fleet_car_rows_host(pose.ctypes.data, e.ctypes.data, 0.1, A.ctypes.data, b.ctypes.data)
+                assert core.same_words(case["track_A"][g, j, kk], A) and core.same_words(case["track_b"][g, j, kk], b)
+
+
+UNUSABLE = {"ended_goal": ("flags", GOAL), "ended_cap": ("flags", CAP), "ended_failed": ("flags", FAILED),
+            "ended_collision": ("flags", COLLISION), "did_not_step": ("k", 3), "stepped_twice": ("k", 5), "status_2": ("status", 2),
+            "status_skipped": ("status", -5)}
+
+
+@pytest.mark.parametrize("why", sorted(UNUSABLE) + ["nan_in_last_knot", "inf_in_first_knot"])
+@pytest.mark.parametrize("see", (core.SEE_ALL, core.SEE_LOWER), ids=("all", "lower"))
+def test_every_reason_a_plan_is_unusable(host, fleet_host, why, see):
+    """one reason at a time, on car 1 of world 0 of a 2 x 3 fleet at step 3: its mask column is 0 for every observer, every
+    stage of its track is the rows at x0 (word for word fleet_car_rows_host's), the other cars keep their plans"""
+    rng = np.random.default_rng(43)
+    case = fill_plans(Case(2, 3, 5, step=3, see=see, margin=0.1), rng)
+    if why in UNUSABLE:
+        name, val = UNUSABLE[why]
+        case[name][1] = val
+    elif why == "nan_in_last_knot":
+        case["xopt"][1, 2, 5] = np.nan
+    else:
+        case["xopt"][1, 0, 0] = np.inf
+    check_call(host, case, label=why)
+    ok = case["track_ok"].reshape(2, 3, 3)
+    assert np.all(ok[0, :, 1] == 0) and ok[1, 2, 1] == 1 and ok[0, 2, 0] == 1 and ok[0, 1, 0] == 1
+    A, b = np.zeros((4, 2)), np.zeros(4)
+    e = np.array(case.ego, float)
+    fleet_host.fleet_car_rows_host(case["x0"][1].ctypes.data, e.ctypes.data, 0.1, A.ctypes.data, b.ctypes.data)
+    for kk in range(6):
+        assert core.same_words(case["track_A"][0, 1, kk], A) and core.same_words(case["track_b"][0, 1, kk], b)
+    assert not core.same_words(case["track_b"][0, 0, 0], case["track_b"][0, 0, 5])
+
+
+def test_a_car_without_a_pose_is_a_spare_and_nothing_is_nan(host):
+    """a pose word that is not finite: with a usable plan the track is the plan's and nobody may use it (the slot is a spare
+    for every observer); without one every stage is the spare's rows"""
+    rng = np.random.default_rng(47)
+    sA, sb = core.ref_spare_rows(50.0)
+    for bad in (np.nan, np.inf, -np.inf):
+        for word in range(3):
+            for usable in (True, False):
+                case = fill_plans(Case(1, 3, 4, far=50.0), rng)
+                case["x0"][1, word] = bad
+                if not usable:
+                    case["status"][1] = 2
+                check_call(host, case)
+                assert np.all(case["track_ok"][:, 1] == 0) and case["track_ok"][1, 0] == 1
+                assert core.same_words(case["track_b"][0, 1], np.stack([sb] * 5)) == (not usable)
+                if not usable:
+                    assert core.same_words(case["track_A"][0, 1], np.stack([sA] * 5))
+                for name in WRITTEN:
+                    assert not np.isnan(case[name].astype(float)).any()
+
+
+def test_struct_mirror_matches_the_header(host):
+    out = (ctypes.c_longlong * 64)()
+    n = host.fleet_tracks_layout_host(out, 64)
+    fields = [f[0] for f in _lib.ObcaFleetTracks._fields_]
+    assert n == 1 + len(fields)
+    assert out[0] == ctypes.sizeof(_lib.ObcaFleetTracks)
+    assert [out[1 + i] for i in range(len(fields))] == [getattr(_lib.ObcaFleetTracks, f).offset for f in fields]
+    raw = _lib.ObcaFleetTracks()
+    ctypes.memset(ctypes.byref(raw), 0xff, ctypes.sizeof(raw))
+    host.fleet_tracks_init_host(ctypes.byref(raw))
+    assert bytes(raw) == bytes(_lib.ObcaFleetTracks())
+
+
+REFUSED = [dict(G=0), dict(V=0), dict(V=17), dict(N=0), dict(N=128), dict(step=-1), dict(see=-1), dict(see=2), dict(margin=-0.5),
+           dict(margin=float("inf")), dict(margin=float("nan")), dict(far=0.0), dict(far=-1.0), dict(far=float("inf")),
+           dict(far=float("nan")), dict(struct_size=0), dict(struct_size=ctypes.sizeof(_lib.ObcaFleetTracks) - 8),
+           dict(struct_size=ctypes.sizeof(_lib.ObcaFleetTracks) + 8)]
+
+
+def test_refused_calls_touch_nothing(host):
+    rng = np.random.default_rng(53)
+    case = fill_plans(Case(2, 2, 3), rng)
+    before = case.snapshot()
+    for over in REFUSED:
+        tracks_host(host, case, rc=E_INVAL, **over)
+    for q in range(4):
+        ego = list(case.ego)
+        ego[q] = float("nan")
+        tracks_host(host, case, rc=E_INVAL, ego=(ctypes.c_double * 4)(*ego))
+    for name in READ + WRITTEN:
+        tracks_host(host, case, rc=E_INVAL, null=(name,))
+    assert host.fleet_tracks_host(None) == E_INVAL
+    assert all(core.same_words(case.whole[k], before[k]) for k in before)

@@ -169,6 +169,101 @@ SC_FN void out_row(const double* pool_A, const double* pool_b, const double* poo
     *b = row_b(Ai, pool_b + (int64_t)i * E, pool_v ? pool_v + 2 * i : nullptr, Ts, r, kk);
 }
 
+// ---- obca_scene_select_staged: the last Kt pool slots may carry rows of their own per stage (a track), where stage_ok says
+// so.  Slot K - Kt + t of instance b reads stage_A / stage_b[b / stage_group, t, kk]; its pool_v plays no part in its rows
+// (its pool words are still checked).  Every other slot is obca_scene_select's.
+
+// the extra checks of obca_scene_select_staged, made with args_check before anything is read or written
+SC_FN int staged_args_check(int32_t B, int32_t K, int32_t Kt, int32_t stage_group, const double* stage_A, const double* stage_b,
+                            const int32_t* stage_ok) {
+    if (Kt < 0 || Kt > K || stage_group < 1 || B < 1 || B % stage_group != 0) return E_INVAL;
+    if (Kt > 0 && (!stage_A || !stage_b || !stage_ok)) return E_INVAL;
+    return 0;
+}
+
+// the track of staged slot t of block blk: sA [N+1,E,2], sb [N+1,E]
+SC_FN const double* track_A_of(const double* stage_A, int64_t blk, int Kt, int t, int N1, int E) {
+    return stage_A + ((blk * Kt + t) * N1) * E * 2;
+}
+SC_FN const double* track_b_of(const double* stage_b, int64_t blk, int Kt, int t, int N1, int E) {
+    return stage_b + ((blk * Kt + t) * N1) * E;
+}
+
+// is every word of a track finite and every row of every stage a half-plane
+SC_FN bool track_finite(const double* sA, const double* sb, int N1, int E) {
+    bool ok = true;
+    for (int q = 0; q < N1 * E; ++q)
+        ok = ok && finite_(sA[2 * q]) && finite_(sA[2 * q + 1]) && finite_(sb[q]) && (sA[2 * q] != 0.0 || sA[2 * q + 1] != 0.0);
+    return ok;
+}
+
+// score_rows for a track: the samples are the same; at sample j of interval s the rows are A and b interpolated entry by
+// entry between stages s and s + 1 (audit::lerp_end, obca_plan_sweep's rule for rows per stage), stage 0's at every sample
+// for variant 4.  A track whose A does not change gives score_rows' words: lerp_end of two equal words is that word.
+template <int E>
+SC_FN double score_track(const double* sA, const double* sb, const double* x, int N, const double* x0, int n_sub, bool stage0,
+                         const double* ego, int* n_pose) {
+    const int N1 = N + 1;
+    double a0[2 * E], a1[2 * E], aj[2 * E], b0[E], b1[E], bj[E], C[4][2];
+    for (int r = 0; r < E; ++r) { a0[2 * r] = sA[2 * r]; a0[2 * r + 1] = sA[2 * r + 1]; b0[r] = sb[r]; }
+    double best = INFINITY;
+    int np = 0;
+    if (x0 && finite_(x0[0]) && finite_(x0[1]) && finite_(x0[2])) {
+        audit::car_corners(x0[0], x0[1], x0[2], ego, C);
+        best = audit::min_nan(best, audit::signed_distance<4>(C, a0, b0, E));
+        ++np;
+    }
+    for (int s = 0; s < N; ++s) {
+        const double p0[3] = {x[s], x[N1 + s], x[2 * N1 + s]}, p1[3] = {x[s + 1], x[N1 + s + 1], x[2 * N1 + s + 1]};
+        if (!stage0) {
+            const double* nA = sA + 2 * (s + 1) * E;
+            const double* nb = sb + (s + 1) * E;
+            for (int r = 0; r < E; ++r) { a1[2 * r] = nA[2 * r]; a1[2 * r + 1] = nA[2 * r + 1]; b1[r] = nb[r]; }
+        } else {
+            for (int r = 0; r < E; ++r) { a1[2 * r] = a0[2 * r]; a1[2 * r + 1] = a0[2 * r + 1]; b1[r] = b0[r]; }
+        }
+        for (int j = s == 0 ? 0 : 1; j <= n_sub; ++j) {
+            double p[3];
+            audit::sample_pose(p0, p1, n_sub, j, p);
+            if (!(finite_(p[0]) && finite_(p[1]) && finite_(p[2]))) continue;
+            for (int r = 0; r < E; ++r) {
+                aj[2 * r] = audit::lerp_end(a0[2 * r], a1[2 * r], n_sub, j);
+                aj[2 * r + 1] = audit::lerp_end(a0[2 * r + 1], a1[2 * r + 1], n_sub, j);
+                bj[r] = audit::lerp_end(b0[r], b1[r], n_sub, j);
+            }
+            audit::car_corners(p[0], p[1], p[2], ego, C);
+            best = audit::min_nan(best, audit::signed_distance<4>(C, aj, bj, E));
+            ++np;
+        }
+        for (int r = 0; r < E; ++r) { a0[2 * r] = a1[2 * r]; a0[2 * r + 1] = a1[2 * r + 1]; b0[r] = b1[r]; }
+    }
+    *n_pose = np;
+    return best;
+}
+
+// the same for a run-time row count 1 <= E <= MAX_E
+template <int E = 1>
+SC_FN double score_track_obstacle(int e, const double* sA, const double* sb, const double* x, int N, const double* x0, int n_sub,
+                                  bool stage0, const double* ego, int* n_pose) {
+    if constexpr (E < MAX_E) {
+        if (e != E) return score_track_obstacle<E + 1>(e, sA, sb, x, N, x0, n_sub, stage0, ego, n_pose);
+    }
+    return score_track<E>(sA, sb, x, N, x0, n_sub, stage0, ego, n_pose);
+}
+
+// staged slot index of pool obstacle i (0 .. Kt-1), or -1 where it has pool rows: i below K - Kt, or stage_ok 0
+SC_FN int staged_slot(int i, int K, int Kt, const int32_t* ok /* [Kt] of the instance, or NULL */) {
+    const int t = i - (K - Kt);
+    return (ok && t >= 0 && ok[t] != 0) ? t : -1;
+}
+
+// out_row for a selected staged slot: stage kk's rows of the track as they are
+SC_FN void out_row_track(const double* sA, const double* sb, int E, int r, int kk, double a[2], double* b) {
+    const double* Ak = sA + 2 * (int64_t)kk * E;
+    a[0] = Ak[2 * r]; a[1] = Ak[2 * r + 1];
+    *b = sb[(int64_t)kk * E + r];
+}
+
 }  // namespace scene
 
 #endif

@@ -19,7 +19,9 @@ in csrc/obca_poolloop_core.h) records the step, measures the applied interval ag
 applied step length, advances the state, sets the flags and writes the next reference window from the route.  ``drive_maps``
 composes ``grid_pool``, ``openloop.route_search`` and ``PoolLoop``: B maps and B start/goal pairs in, B driven trajectories
 out.  ``FleetLoop`` puts V of those rollouts into one world: after every step obca_fleet_step (csrc/obca_fleet_core.h) writes
-the other cars of the world into the last V pool slots of each car and measures what the cars did to each other.  Not here: the reference's 4 -> 6 -> 8 dispatch, its lidar gate and its fixed-time reference preparation
+the other cars of the world into the last V pool slots of each car and measures what the cars did to each other; with predict="plan" obca_fleet_tracks
+(csrc/obca_fleet_tracks_core.h) then turns the plans just applied into rows per stage, which the next ``select`` reads through
+obca_scene_select_staged.  Not here: the reference's 4 -> 6 -> 8 dispatch, its lidar gate and its fixed-time reference preparation
 (``rollouts.DeviceRollouts`` has those, for at most 8 static obstacles).
 """
 import ctypes
@@ -39,7 +41,7 @@ def _dev_of(device, *tensors):
 
 
 def select(pool_A, pool_b, x, n_sel, pool_v=None, Ts=None, x0=None, variant=None, status=None, n_sub=1, state=None,
-           ego=DEFAULT_EGO, device=None):
+           ego=DEFAULT_EGO, device=None, stage_A=None, stage_b=None, stage_ok=None, stage_group=1):
     """pool_A [B,K,E,2], pool_b [B,K,E] (K <= 64 obstacles of E rows each), pool_v [B,K,2] m/s or None, Ts [B] or a float
     (needed with pool_v); x [B,3,N+1] the poses to measure (a reference window, or plans), x0 [B,3] or None one more pose
     against stage 0's rows; variant [B], an int or None (4: every sample against stage 0's rows), status [B] or None.
@@ -47,6 +49,11 @@ def select(pool_A, pool_b, x, n_sel, pool_v=None, Ts=None, x0=None, variant=None
     ``state=None``: scores are written from the samples and every usable instance counts as changed.  ``state`` = the dict a
     previous call returned: its ``score`` and ``sel`` are updated IN PLACE to the running minimum and the new selection, and
     only instances with variant != 0 and status 0 / 1 are measured.
+
+    ``stage_A`` [B/stage_group,Kt,N+1,E,2], ``stage_b`` [B/stage_group,Kt,N+1,E] and ``stage_ok`` [B,Kt] int32 (given together, or
+    not at all) make it obca_scene_select_staged: pool slot K - Kt + t of instance b has the rows stage_A / stage_b[b //
+    stage_group, t, kk] at stage kk where stage_ok[b,t] != 0 (a track, e.g. one of ``fleet_tracks``), in place of its pool rows moved by
+    pool_v.  Without them obca_scene_select is called.
 
     Returns a dict of device tensors on the current stream, no host synchronisation: A [B,N+1,n_sel E,2] and b [B,N+1,n_sel E]
     (rows for a handle with m = [E] * n_sel), sel [B,n_sel] int32 ascending pool indices, variant_out [B] (variant where the
@@ -94,15 +101,72 @@ def select(pool_A, pool_b, x, n_sel, pool_v=None, Ts=None, x0=None, variant=None
            "min_clear": torch.empty(B, dtype=torch.float64, device=dev)}
     ego_c = (ctypes.c_double * 4)(*[float(v) for v in ego])
     p = _lib.ptr
-    _lib.check(_lib.load().obca_scene_select(ego_c, B, K, E, N1 - 1, n_sel, int(n_sub), 0 if state is None else 1, p(pool_A),
-                                             p(pool_b), p(pool_v), p(Ts), p(x), p(x0), p(variant), p(status), p(score), p(sel),
-                                             p(out["A"]), p(out["b"]), p(out["variant_out"]), p(out["ok"]), p(out["min_clear"]),
-                                             _lib.device_index(dev), _lib.stream_ptr(dev)))
+    staged = (stage_A, stage_b, stage_ok)
+    if all(a is None for a in staged):
+        _lib.check(_lib.load().obca_scene_select(ego_c, B, K, E, N1 - 1, n_sel, int(n_sub), 0 if state is None else 1, p(pool_A),
+                                                 p(pool_b), p(pool_v), p(Ts), p(x), p(x0), p(variant), p(status), p(score), p(sel),
+                                                 p(out["A"]), p(out["b"]), p(out["variant_out"]), p(out["ok"]), p(out["min_clear"]),
+                                                 _lib.device_index(dev), _lib.stream_ptr(dev)))
+        staged = ()
+    else:
+        if any(a is None for a in staged):
+            raise ValueError("stage_A, stage_b and stage_ok are given together")
+        stage_ok = torch.as_tensor(stage_ok, dtype=torch.int32, device=dev).contiguous()
+        group = int(stage_group)
+        if stage_ok.dim() != 2 or stage_ok.shape[0] != B or group < 1 or B % group != 0:
+            raise ValueError("expected stage_ok [B,Kt] and a stage_group that divides B = %d" % B)
+        Kt = int(stage_ok.shape[1])
+        stage_A, stage_b = opt(stage_A, (B // group, Kt, N1, E, 2)), opt(stage_b, (B // group, Kt, N1, E))
+        staged = (stage_A, stage_b, stage_ok)
+        _lib.check(_lib.load().obca_scene_select_staged(ego_c, B, K, E, N1 - 1, n_sel, int(n_sub), 0 if state is None else 1,
+                                                        p(pool_A), p(pool_b), p(pool_v), p(Ts), p(x), p(x0), p(variant), p(status),
+                                                        Kt, group, p(stage_A), p(stage_b), p(stage_ok), p(score), p(sel),
+                                                        p(out["A"]), p(out["b"]), p(out["variant_out"]), p(out["ok"]),
+                                                        p(out["min_clear"]), _lib.device_index(dev), _lib.stream_ptr(dev)))
     # the launch is asynchronous: the tensors it reads are tied to the result and to the stream (see openloop.route_reference)
-    out["A"]._obca_keep = (pool_A, pool_b, pool_v, Ts, x, x0, variant, status)
+    out["A"]._obca_keep = (pool_A, pool_b, pool_v, Ts, x, x0, variant, status) + staged
     for a in out["A"]._obca_keep:
         if a is not None:
             a.record_stream(torch.cuda.current_stream(dev))
+    return out
+
+
+def fleet_tracks(x0, flags, k, xopt, status, V, step, see="all", margin=0.0, far=100.0, ego=DEFAULT_EGO, out=None, device=None):
+    """obca_fleet_tracks: the plans just applied as rows per stage.  x0 [B,3], flags [B], k [B] as they are after obca_fleet_step
+    of loop step ``step``, xopt [B,3,N+1] and status [B] the solve that was applied; B = G V.  Returns a dict of device tensors
+    on the current stream, no host synchronisation: track_A [G,V,N+1,4,2], track_b [G,V,N+1,4] and track_ok [B,V] int32 --
+    ``select``'s stage_A, stage_b and stage_ok with stage_group = V for pools whose last V slots are the cars.  ``out``: a dict
+    of such tensors to write into."""
+    import torch
+    if not torch.cuda.is_available():
+        raise RuntimeError("scene.fleet_tracks needs a ROCm GPU; there is no CPU fallback on the product path")
+    if see not in _lib.FLEET_SEE:
+        raise ValueError("see is one of %s" % sorted(_lib.FLEET_SEE))
+    dev = _dev_of(device, xopt, x0)
+    t = lambda a, dt=torch.float64: torch.as_tensor(a, dtype=dt, device=dev).contiguous()
+    x0, xopt, flags, k, status = t(x0), t(xopt), t(flags, torch.int32), t(k, torch.int32), t(status, torch.int32)
+    V = int(V)
+    if xopt.dim() != 3 or xopt.shape[1] != 3 or V < 1 or xopt.shape[0] % V != 0:
+        raise ValueError("expected xopt [B,3,N+1] with B a multiple of V")
+    B, N1 = int(xopt.shape[0]), int(xopt.shape[2])
+    for a, shape in ((x0, (B, 3)), (flags, (B,)), (k, (B,)), (status, (B,))):
+        if tuple(a.shape) != shape:
+            raise ValueError("expected shape %s, got %s" % (shape, tuple(a.shape)))
+    G = B // V
+    if out is None:
+        out = {"track_A": torch.empty(G, V, N1, 4, 2, dtype=torch.float64, device=dev),
+               "track_b": torch.empty(G, V, N1, 4, dtype=torch.float64, device=dev),
+               "track_ok": torch.empty(B, V, dtype=torch.int32, device=dev)}
+    d = _lib.ObcaFleetTracks()
+    d.G, d.V, d.N, d.step, d.see, d.margin, d.far = G, V, N1 - 1, int(step), _lib.FLEET_SEE[see], float(margin), float(far)
+    d.ego = (ctypes.c_double * 4)(*[float(v) for v in ego])
+    for name, a in (("x0", x0), ("flags", flags), ("k", k), ("xopt", xopt), ("status", status), ("track_A", out["track_A"]),
+                    ("track_b", out["track_b"]), ("track_ok", out["track_ok"])):
+        setattr(d, name, a.data_ptr())
+    _lib.check(_lib.load().obca_fleet_tracks(ctypes.byref(d), _lib.device_index(dev), _lib.stream_ptr(dev)))
+    out["track_A"]._obca_keep = (x0, flags, k, xopt, status)     # the launch is asynchronous: see ``select``
+    for a in out["track_A"]._obca_keep:
+        a.record_stream(torch.cuda.current_stream(dev))
     return out
 
 
@@ -371,11 +435,14 @@ class PoolLoop:
         self._advance(0)
         self.steps_enqueued = 0
 
+    def _select(self):
+        return select(self.pool_A, self.pool_b, self.xref, self.n_sel, pool_v=self.pool_v, Ts=self.Ts, x0=self.x0,
+                      variant=self.variant_out, n_sub=self.select_n_sub, ego=self.ego, device=self.device)
+
     def _step(self):
         torch, solver, d = self.torch, self.solver, self._desc
         if self.rounds == 0:
-            s = select(self.pool_A, self.pool_b, self.xref, self.n_sel, pool_v=self.pool_v, Ts=self.Ts, x0=self.x0,
-                       variant=self.variant_out, n_sub=self.select_n_sub, ego=self.ego, device=self.device)
+            s = self._select()
             var = torch.where(s["ok"] != 0, self.variant_out, 0).to(torch.int32)
             self._held = solver.solve(var, self.x0, self.u0, self.xref, s["A"], s["b"], self.Ts, self.term, self._cparams,
                                       out=self._held)
@@ -421,6 +488,14 @@ class FleetLoop(PoolLoop):
     (predict="velocity") or standing (predict="static"); a car that has ended is parked where it stands and stays an obstacle.
     see="all": every other car is an obstacle; see="lower": only the cars of lower index are (prioritised planning: car 0
     yields to nobody).  A spare slot (the car itself, a car not seen, a car without a pose) is ``grid_pool``'s spare at ``far``.
+    predict="plan": a car that has just applied a feasible plan is predicted by that plan -- after obca_fleet_step,
+    obca_fleet_tracks turns every such plan into rows per stage (knot kk + 1 is stage kk of the next solve, the last stage
+    extrapolated) and the next ``select`` is obca_scene_select_staged, which reads those rows for the agent slots in place of
+    the translating rectangle.  The pool slots themselves, and with them obca_pool_loop_advance's ``clear``, stay the velocity
+    prediction, which is also the fallback for a car without a usable plan (ended, masked, infeasible, or the first step).
+    Plans of cars of lower index are commitments under see="lower"; under see="all" every car plans against plans that are
+    being revised against it, which can be worse than velocities.  rounds >= 1 is refused with "plan":
+    ``solve_scene`` is not staged.
 
     The fleet's time is synchronous: variant 8 only, and Ts must be one value per world -- checked here when Ts is a float or a
     host array; a device tensor is taken at its word (checking it would cost a host synchronisation).
@@ -444,8 +519,10 @@ class FleetLoop(PoolLoop):
             raise RuntimeError("scene.FleetLoop needs a ROCm GPU; there is no CPU fallback on the product path")
         dev = solver.device
         V = self.V = int(V)
-        if see not in _lib.FLEET_SEE or predict not in _lib.FLEET_PREDICT:
-            raise ValueError("see is one of %s and predict one of %s" % (sorted(_lib.FLEET_SEE), sorted(_lib.FLEET_PREDICT)))
+        if see not in _lib.FLEET_SEE or (predict not in _lib.FLEET_PREDICT and predict != "plan"):
+            raise ValueError("see is one of %s and predict one of %s" % (sorted(_lib.FLEET_SEE), sorted(_lib.FLEET_PREDICT) + ["plan"]))
+        if predict == "plan" and int(kw.get("rounds", 0)) >= 1:
+            raise ValueError('predict="plan" needs rounds = 0: solve_scene is not staged')
         if kw.get("variant") not in (None, 8):
             raise ValueError("variant %r: a fleet's time is synchronous, the loop runs obca_mpc8 (8) only" % (kw["variant"],))
         kw["variant"] = 8
@@ -490,19 +567,46 @@ class FleetLoop(PoolLoop):
         self.agent_clear = torch.zeros(self.B, self.max_steps, dtype=torch.float64, device=self.device)
         d = self._fdesc = _lib.ObcaFleet()
         d.G, d.V, d.Ks, d.N, d.max_steps, d.n_sub = self.G, self.V, self.Ks, self.N, self.max_steps, self.agent_n_sub
-        d.see, d.predict = _lib.FLEET_SEE[self.see], _lib.FLEET_PREDICT[self.predict]
+        # "plan" is the loop's word: the C call writes the velocity prediction, the tracks replace it where there is a plan
+        d.see, d.predict = _lib.FLEET_SEE[self.see], _lib.FLEET_PREDICT["velocity" if self.predict == "plan" else self.predict]
         d.clearance, d.margin, d.far = self.agent_clearance, self.margin, self.far
         d.ego = (ctypes.c_double * 4)(*self.ego)
         for name, t in (("x_prev", self.x_prev), ("x0", self.x0), ("u0", self.u0), ("k", self.k), ("flags", self.flags),
                         ("pool_A", self.pool_A), ("pool_b", self.pool_b), ("pool_v", self.pool_v),
                         ("agent_clear_hist", self.agent_clear), ("xref_out", self.xref), ("variant_out", self.variant_out)):
             setattr(d, name, t.data_ptr())
+        if self.predict == "plan":
+            G, V, N1 = self.G, self.V, self.N + 1
+            self.track_A = torch.zeros(G, V, N1, 4, 2, dtype=torch.float64, device=self.device)
+            self.track_b = torch.zeros(G, V, N1, 4, dtype=torch.float64, device=self.device)
+            self.track_ok = torch.zeros(self.B, V, dtype=torch.int32, device=self.device)
+            t = self._tdesc = _lib.ObcaFleetTracks()
+            t.G, t.V, t.N, t.see, t.margin, t.far = G, V, self.N, _lib.FLEET_SEE[self.see], self.margin, self.far
+            t.ego = (ctypes.c_double * 4)(*self.ego)
+            for name, a in (("x0", self.x0), ("flags", self.flags), ("k", self.k), ("track_A", self.track_A),
+                            ("track_b", self.track_b), ("track_ok", self.track_ok)):
+                setattr(t, name, a.data_ptr())
 
     def _tensors(self):
         own = super()._tensors()
         if self._fdesc is not None:
             own += [self.x_prev, self.agent_clear]
+            if self.predict == "plan":
+                own += [self.track_A, self.track_b, self.track_ok]
         return own
+
+    def _select(self):
+        if self.predict != "plan":
+            return super()._select()
+        return select(self.pool_A, self.pool_b, self.xref, self.n_sel, pool_v=self.pool_v, Ts=self.Ts, x0=self.x0,
+                      variant=self.variant_out, n_sub=self.select_n_sub, ego=self.ego, device=self.device, stage_A=self.track_A,
+                      stage_b=self.track_b, stage_ok=self.track_ok, stage_group=self.V)
+
+    def _tracks(self, step):
+        """obca_fleet_tracks on the solve just applied (``self._last``), after obca_fleet_step on the same stream"""
+        r, t = self._last[0], self._tdesc
+        t.step, t.xopt, t.status = int(step), r.xopt.data_ptr(), r.status.data_ptr()
+        _lib.check(self.lib.obca_fleet_tracks(ctypes.byref(t), _lib.device_index(self.device), _lib.stream_ptr(self.device)))
 
     def _fleet_step(self, measure, step):
         self._fdesc.step = int(step)
@@ -517,6 +621,8 @@ class FleetLoop(PoolLoop):
         self.x_prev.copy_(self.x0)
         self.agent_clear.fill_(float("inf"))
         self._fleet_step(0, 0)
+        if self.predict == "plan":
+            self.track_ok.zero_()                            # no plan yet: the first select is the velocity loop's
 
     def _step(self):
         self.x_prev.copy_(self.x0)
@@ -526,6 +632,8 @@ class FleetLoop(PoolLoop):
             self._fleet_step(1, idx)
         else:                                                # beyond the cap nobody steps: the slots alone
             self._fleet_step(0, 0)
+        if self.predict == "plan":
+            self._tracks(idx)                                # beyond the cap k == step + 1 fails: every mask word 0
 
     def read(self):
         """``PoolLoop.read()``'s dict and agent_clear [B,S] (the smallest distance to another car of the world over every
