@@ -191,9 +191,54 @@ constexpr ObcaShapeSizes obca_shape_sizes(int N, int nO, int M) {
    The compile-time-shape kernels (ShapeIs) drop the bound loads and the equality / upper-bound / weight paths there; a value beyond
    the kernel's slots (or OBCA_NO_MU_SLOT, the generic kernels) changes nothing. */
 #define OBCA_NO_MU_SLOT (1 << 20)
-constexpr int obca_r_mu(int N, int nO, int M, int variant) {
-    return 3 + 3 * N + (variant == 4 ? 3 : 0) + 2 * (N + 1) + 2 * N + 2 * N + (variant == 4 ? 2 : 0) + (variant == 6 ? 2 : 0) +
-           2 * (N + 1) * nO + (N + 1) * M;
+/* The whole row layout of one variant as a constant: first row of every kind (a kind the variant lacks is empty: its first row
+   is the next kind's), number of rows R, number of variables n, free_T.  The same sums as csrc/obca_kernel.hip: obca_ipm_body
+   (`---- layout`) and csrc/obca_lpi_core.h: make_layout form at run time (tests/test_variant_layout.py compares them field by
+   field).  The one-wavefront compile-time-shape kernels run a body per variant (ShapeIs<N, nO, M, false, variant>) that takes
+   its layout from here, so that every row boundary is an immediate and every test of the variant folds. */
+struct ObcaRowLayout { int r_init, r_dyn, r_term, r_xb, r_ub, r_acc, r_T, r_tx, r_norm, r_dist, r_lam, r_mu, R, n, free_T; };
+constexpr ObcaRowLayout obca_row_layout(int N, int nO, int M, int variant) {
+    ObcaRowLayout l{};
+    l.free_T = variant == 4 ? 1 : 0;
+    l.n = (N + 1) * (3 + M + 4 * nO) + 2 * N + l.free_T;
+    l.r_init = 0; l.r_dyn = 3; l.r_term = 3 + 3 * N;
+    l.r_xb = l.r_term + (variant == 4 ? 3 : 0);
+    l.r_ub = l.r_xb + 2 * (N + 1);
+    l.r_acc = l.r_ub + 2 * N;
+    l.r_T = l.r_acc + 2 * N;
+    l.r_tx = l.r_T + (variant == 4 ? 2 : 0);
+    l.r_norm = l.r_tx + (variant == 6 ? 2 : 0);
+    l.r_dist = l.r_norm + (N + 1) * nO;
+    l.r_lam = l.r_dist + (N + 1) * nO;
+    l.r_mu = l.r_lam + (N + 1) * M;
+    l.R = l.r_mu + (N + 1) * 4 * nO;
+    return l;
+}
+constexpr int obca_r_mu(int N, int nO, int M, int variant) { return obca_row_layout(N, nO, M, variant).r_mu; }
+/* Kinds of rows, in the layout's order, as bits; obca_slot_kinds: the kinds that have a row in slot j (rows nt j .. nt j + nt - 1,
+   cut at R) of that layout -- 0 for a slot beyond the rows.  What the per-variant bodies' rolled row loops (row_value, row_jdx,
+   row_bounds; csrc/obca_kernel.hip: mixed_then_mu) are built from: obca_own_mu_slot, the first slot at or behind the variant's
+   r_mu -- its rounds and the ones behind it hold mu rows alone and go straight to the mu formula -- and obca_mixed_kinds, the kinds
+   of the rounds before it: the ladder there carries no test for a kind outside them. */
+enum { OBCA_KIND_BIT_INIT = 1, OBCA_KIND_BIT_DYN = 2, OBCA_KIND_BIT_TERM = 4, OBCA_KIND_BIT_XB = 8, OBCA_KIND_BIT_UB = 16, OBCA_KIND_BIT_ACC = 32,
+       OBCA_KIND_BIT_T = 64, OBCA_KIND_BIT_TX = 128, OBCA_KIND_BIT_NORM = 256, OBCA_KIND_BIT_DIST = 512, OBCA_KIND_BIT_LAM = 1024,
+       OBCA_KIND_BIT_MU = 2048, OBCA_KIND_BITS_ALL = 4095 };
+constexpr int obca_slot_kinds(int N, int nO, int M, int variant, int nt, int j) {
+    const ObcaRowLayout l = obca_row_layout(N, nO, M, variant);
+    const int first[13] = {l.r_init, l.r_dyn, l.r_term, l.r_xb, l.r_ub, l.r_acc, l.r_T, l.r_tx, l.r_norm, l.r_dist, l.r_lam, l.r_mu, l.R};
+    const int lo = nt * j, hi = nt * j + nt < l.R ? nt * j + nt : l.R;
+    int kinds = 0;
+    for (int k = 0; k < 12; ++k) {
+        const int a = first[k] > lo ? first[k] : lo, b = first[k + 1] < hi ? first[k + 1] : hi;
+        if (a < b) kinds |= 1 << k;
+    }
+    return kinds;
+}
+constexpr int obca_own_mu_slot(int N, int nO, int M, int variant, int nt) { return (obca_r_mu(N, nO, M, variant) + nt - 1) / nt; }
+constexpr int obca_mixed_kinds(int N, int nO, int M, int variant, int nt) {
+    int kinds = 0;
+    for (int j = 0; j < obca_own_mu_slot(N, nO, M, variant, nt); ++j) kinds |= obca_slot_kinds(N, nO, M, variant, nt, j);
+    return kinds;
 }
 constexpr int obca_mu_slot(int N, int nO, int M, int nt) {
     int r = obca_r_mu(N, nO, M, 4);

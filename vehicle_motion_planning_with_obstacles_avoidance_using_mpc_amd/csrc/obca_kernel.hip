@@ -16,6 +16,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <math.h>
+#include <type_traits>
 #include "obca_device.h"
 
 #define SYNC() __syncthreads()
@@ -203,12 +204,20 @@ __device__ __forceinline__ void eval_geom(const Lay& L, const Sh& S, const doubl
 }
 
 // value of elastic row r at iterate xv (geometry arrays must be current)
+// KM: the kinds of rows r can be (bits of csrc/obca_device.h: OBCA_KIND_BIT_*; every kind where the caller does not know).  A kind
+// outside KM has no test here, the last kind of KM needs none, and KM = mu rows alone is the mu formula without the preamble.
+#define OBCA_ROW_IS(K, bound) ((KM & (K)) != 0 && ((KM & ~(2 * (K) - 1)) == 0 || r < (bound)))
+template <int KM = OBCA_KIND_BITS_ALL>
 __device__ __forceinline__ double row_value(const Lay& L, const Sh& S, const Inst& in, const double* xv, const double* ct,
                             const double* st, const double* cc, int r) {
+    if constexpr (KM == OBCA_KIND_BIT_MU) {
+        const int q = r - L.r_mu, w4 = 4 * L.nO, k = q / w4, j = q - k * w4;
+        return xv[L.imu(k) + j];
+    }
     const double T = L.free_T ? xv[L.iT()] : 1.0;
     const double h = T * in.Ts, ih = rcp64(h);
-    if (r < L.r_dyn) return xv[r] - in.x0[r];
-    if (r < L.r_term) {
+    if (OBCA_ROW_IS(OBCA_KIND_BIT_INIT, L.r_dyn)) return xv[r] - in.x0[r];
+    if (OBCA_ROW_IS(OBCA_KIND_BIT_DYN, L.r_term)) {
         const int q = r - L.r_dyn, k = q / 3, j = q - 3 * k;
         const double* pk = xv + L.ip(k);
         const double* pn = xv + L.ip(k + 1);
@@ -216,30 +225,30 @@ __device__ __forceinline__ double row_value(const Lay& L, const Sh& S, const Ins
         const double f = (j == 0) ? u[0] * ct[k] : (j == 1) ? u[0] * st[k] : u[1];
         return pn[j] - pk[j] - h * f;
     }
-    if (r < L.r_xb) {
+    if (OBCA_ROW_IS(OBCA_KIND_BIT_TERM, L.r_xb)) {
         const int j = r - L.r_term;
         return xv[L.ip(L.N) + j] - S.xref[j * (L.N + 1) + L.N];
     }
-    if (r < L.r_ub) {
+    if (OBCA_ROW_IS(OBCA_KIND_BIT_XB, L.r_ub)) {
         const int q = r - L.r_xb;
         return xv[L.ip(q >> 1) + (q & 1)];
     }
-    if (r < L.r_acc) {
+    if (OBCA_ROW_IS(OBCA_KIND_BIT_UB, L.r_acc)) {
         const int q = r - L.r_ub;
         return xv[L.iu(q >> 1) + (q & 1)];
     }
-    if (r < L.r_T) {
+    if (OBCA_ROW_IS(OBCA_KIND_BIT_ACC, L.r_T)) {
         const int q = r - L.r_acc, k = q >> 1, c = q & 1;
         const double prev = (k == 0) ? in.u0[c] : xv[L.iu(k - 1) + c];
         return (prev - xv[L.iu(k) + c]) * ih;
     }
-    if (r < L.r_tx) return T;
-    if (r < L.r_norm) return xv[L.ip(L.N) + (r - L.r_tx)];
-    if (r < L.r_dist) {
+    if (OBCA_ROW_IS(OBCA_KIND_BIT_T, L.r_tx)) return T;
+    if (OBCA_ROW_IS(OBCA_KIND_BIT_TX, L.r_norm)) return xv[L.ip(L.N) + (r - L.r_tx)];
+    if (OBCA_ROW_IS(OBCA_KIND_BIT_NORM, L.r_dist)) {
         const int pr = r - L.r_norm;
         return cc[2 * pr] * cc[2 * pr] + cc[2 * pr + 1] * cc[2 * pr + 1];
     }
-    if (r < L.r_lam) {
+    if (OBCA_ROW_IS(OBCA_KIND_BIT_DIST, L.r_lam)) {
         const int pr = r - L.r_dist, k = pr / L.nO, i = pr - k * L.nO;
         const double* pk = xv + L.ip(k);
         const double tx = pk[0] + ct[k] * in.off, ty = pk[1] + st[k] * in.off;
@@ -251,7 +260,7 @@ __device__ __forceinline__ double row_value(const Lay& L, const Sh& S, const Ins
         for (int j = S.offm[i]; j < S.offm[i + 1]; ++j) v -= b[j] * lam[j];
         return v;
     }
-    if (r < L.r_mu) {
+    if (OBCA_ROW_IS(OBCA_KIND_BIT_LAM, L.r_mu)) {
         const int q = r - L.r_lam, k = q / L.M, j = q - k * L.M;
         return xv[L.il(k) + j];
     }
@@ -261,16 +270,18 @@ __device__ __forceinline__ double row_value(const Lay& L, const Sh& S, const Ins
     }
 }
 
+template <int KM = OBCA_KIND_BITS_ALL>
 __device__ __forceinline__ void row_bounds(const Lay& L, const Inst& in, int r, double& lo, double& up) {
     const double INF = INFINITY;
-    if (r < L.r_xb) { lo = 0.0; up = 0.0; return; }
-    if (r < L.r_ub) { const int j = (r - L.r_xb) & 1; lo = in.xL[j]; up = in.xU[j]; return; }
-    if (r < L.r_acc) { const int j = (r - L.r_ub) & 1; lo = in.uL[j]; up = in.uU[j]; return; }
-    if (r < L.r_T) { const int c = (r - L.r_acc) & 1; const double a = c ? OBCA_ACC_MAX1 : OBCA_ACC_MAX0; lo = -a; up = a; return; }
-    if (r < L.r_tx) { if (r == L.r_T) { lo = 0.0; up = INF; } else { lo = OBCA_T_MIN; up = in.Tmax; } return; }
-    if (r < L.r_norm) { if (r == L.r_tx) { lo = in.term[0]; up = INF; } else { lo = in.term[1]; up = in.term[2]; } return; }
-    if (r < L.r_dist) { lo = -INF; up = 1.0; return; }
-    if (r < L.r_lam) { lo = in.dmin; up = INF; return; }
+    constexpr int EQ = OBCA_KIND_BIT_INIT | OBCA_KIND_BIT_DYN | OBCA_KIND_BIT_TERM;
+    if ((KM & EQ) != 0 && ((KM & ~EQ) == 0 || r < L.r_xb)) { lo = 0.0; up = 0.0; return; }
+    if (OBCA_ROW_IS(OBCA_KIND_BIT_XB, L.r_ub)) { const int j = (r - L.r_xb) & 1; lo = in.xL[j]; up = in.xU[j]; return; }
+    if (OBCA_ROW_IS(OBCA_KIND_BIT_UB, L.r_acc)) { const int j = (r - L.r_ub) & 1; lo = in.uL[j]; up = in.uU[j]; return; }
+    if (OBCA_ROW_IS(OBCA_KIND_BIT_ACC, L.r_T)) { const int c = (r - L.r_acc) & 1; const double a = c ? OBCA_ACC_MAX1 : OBCA_ACC_MAX0; lo = -a; up = a; return; }
+    if (OBCA_ROW_IS(OBCA_KIND_BIT_T, L.r_tx)) { if (r == L.r_T) { lo = 0.0; up = INF; } else { lo = OBCA_T_MIN; up = in.Tmax; } return; }
+    if (OBCA_ROW_IS(OBCA_KIND_BIT_TX, L.r_norm)) { if (r == L.r_tx) { lo = in.term[0]; up = INF; } else { lo = in.term[1]; up = in.term[2]; } return; }
+    if (OBCA_ROW_IS(OBCA_KIND_BIT_NORM, L.r_dist)) { lo = -INF; up = 1.0; return; }
+    if (OBCA_ROW_IS(OBCA_KIND_BIT_DIST, L.r_lam)) { lo = in.dmin; up = INF; return; }
     lo = 0.0; up = INF;
 }
 
@@ -449,26 +460,29 @@ __device__ __forceinline__ void gather_grad(const Lay& L, const Sh& S, const Ins
 }
 
 // J_r dx for the condensed rows (soft rows get their dy from the Riccati sweep)
+// (KM as in row_value; the soft rows -- init, dyn -- never come here)
+template <int KM = OBCA_KIND_BITS_ALL>
 __device__ __forceinline__ double row_jdx(const Lay& L, const Sh& S, const Inst& in, int r) {
     const double* xv = S.x;
     const double* d = S.dx;
+    if constexpr (KM == OBCA_KIND_BIT_MU) { const int q = r - L.r_mu, w4 = 4 * L.nO, k = q / w4; return d[L.imu(k) + (q - k * w4)]; }
     const double T = L.free_T ? xv[L.iT()] : 1.0;
     const double dT = L.free_T ? d[L.iT()] : 0.0;
     const double h = T * in.Ts, ih = rcp64(h), iTh = ih * rcp64(T);
-    if (r < L.r_xb) return d[L.ip(L.N) + (r - L.r_term)];
-    if (r < L.r_ub) { const int q = r - L.r_xb; return d[L.ip(q >> 1) + (q & 1)]; }
-    if (r < L.r_acc) { const int q = r - L.r_ub; return d[L.iu(q >> 1) + (q & 1)]; }
-    if (r < L.r_T) {
+    if (OBCA_ROW_IS(OBCA_KIND_BIT_TERM, L.r_xb)) return d[L.ip(L.N) + (r - L.r_term)];
+    if (OBCA_ROW_IS(OBCA_KIND_BIT_XB, L.r_ub)) { const int q = r - L.r_xb; return d[L.ip(q >> 1) + (q & 1)]; }
+    if (OBCA_ROW_IS(OBCA_KIND_BIT_UB, L.r_acc)) { const int q = r - L.r_ub; return d[L.iu(q >> 1) + (q & 1)]; }
+    if (OBCA_ROW_IS(OBCA_KIND_BIT_ACC, L.r_T)) {
         const int q = r - L.r_acc, k = q >> 1, c = q & 1;
         const double prev = (k == 0) ? in.u0[c] : xv[L.iu(k - 1) + c];
         const double dprev = (k == 0) ? 0.0 : d[L.iu(k - 1) + c];
         const double qq = prev - xv[L.iu(k) + c];
         return (dprev - d[L.iu(k) + c]) * ih - qq * iTh * dT;
     }
-    if (r < L.r_tx) return dT;
-    if (r < L.r_norm) return d[L.ip(L.N) + (r - L.r_tx)];
-    if (r < L.r_lam) {
-        const bool isn = r < L.r_dist;
+    if (OBCA_ROW_IS(OBCA_KIND_BIT_T, L.r_tx)) return dT;
+    if (OBCA_ROW_IS(OBCA_KIND_BIT_TX, L.r_norm)) return d[L.ip(L.N) + (r - L.r_tx)];
+    if ((KM & (OBCA_KIND_BIT_NORM | OBCA_KIND_BIT_DIST)) != 0 && ((KM & (OBCA_KIND_BIT_LAM | OBCA_KIND_BIT_MU)) == 0 || r < L.r_lam)) {
+        const bool isn = (KM & OBCA_KIND_BIT_NORM) != 0 && ((KM & OBCA_KIND_BIT_DIST) == 0 || r < L.r_dist);
         const int pr = isn ? r - L.r_norm : r - L.r_dist;
         const int k = pr / L.nO, i = pr - k * L.nO;
         const double c0 = S.cc[2 * pr], c1 = S.cc[2 * pr + 1];
@@ -489,7 +503,7 @@ __device__ __forceinline__ double row_jdx(const Lay& L, const Sh& S, const Inst&
         return -(in.gego[0] * dm[0] + in.gego[1] * dm[1] + in.gego[2] * dm[2] + in.gego[3] * dm[3]) + tx * s0 +
                ty * s1 - sb + c0 * dp[0] + c1 * dp[1] + in.off * (-sn * c0 + cs * c1) * dp[2];
     }
-    if (r < L.r_mu) { const int q = r - L.r_lam, k = q / L.M; return d[L.il(k) + (q - k * L.M)]; }
+    if (OBCA_ROW_IS(OBCA_KIND_BIT_LAM, L.r_mu)) { const int q = r - L.r_lam, k = q / L.M; return d[L.il(k) + (q - k * L.M)]; }
     { const int q = r - L.r_mu, w4 = 4 * L.nO, k = q / w4; return d[L.imu(k) + (q - k * w4)]; }
 }
 
@@ -1782,13 +1796,25 @@ typedef const __attribute__((address_space(4))) ObcaLaunch ObcaLaunchConst;   //
 // The problem shape as the body sees it: ShapeAny -- read from the launch descriptor (any shape the kernel's limits allow);
 // ShapeIs<N, nO, M> -- compile-time constants (csrc/obca_device.h: OBCA_SHAPES): same code, same arithmetic, same results,
 // but every LDS offset, loop bound and index division folds.  The host only launches an instantiation for its own shape.
-struct ShapeAny { static constexpr bool fixed = false; static constexpr int N = 0, nO = 0, M = 0, n_max = 0, R_max = 0, inst_off = 0, soc_lds = 0, mu_slot = OBCA_NO_MU_SLOT; };
+struct ShapeAny {
+    static constexpr bool fixed = false, per_variant = false;
+    static constexpr int N = 0, nO = 0, M = 0, n_max = 0, R_max = 0, inst_off = 0, soc_lds = 0, mu_slot = OBCA_NO_MU_SLOT, variant = 0;
+};
 // FT: the fixed-time variants only (the closed loop's groups with sensed boxes: their layouts have three rows less than the
 // free-time layout the handle sizes for, csrc/obca_rollout.hip)
-template <int N_, int NO_, int M_, bool FT = false>
+// V_: the variant as a constant too (4, 6, 8), 0 = read per instance.  A wavefront is one instance, so the variant is
+// wave-uniform: the one-wavefront shape kernels' pass driver (solve_passes) branches ONCE per instance to a loop over the
+// passes that holds the body of the instance's variant (per_variant, with_variant, pass_loop).  That body takes its row layout from csrc/obca_device.h: obca_row_layout, so the row
+// boundaries, R, n and free_T are immediates and every test of the variant folds, and its rolled row loops go straight to the mu
+// formula in the rounds that hold mu rows alone (mixed_then_mu).  The four-wavefront kernels, the kernels with rows in memory, the fused closed
+// loop and the generic kernels keep the variant at run time.
+template <int N_, int NO_, int M_, bool FT = false, int V_ = 0>
 struct ShapeIs {
+    static_assert(V_ == 0 || V_ == 4 || V_ == 6 || V_ == 8, "variant: 4, 6, 8 or 0 (run time)");
     static constexpr bool fixed = true;
-    static constexpr int N = N_, nO = NO_, M = M_;
+    static constexpr int N = N_, nO = NO_, M = M_, variant = V_;
+    static constexpr bool per_variant = OBCA_NT == 64 && !FT && V_ == 0;     // the driver picks with_variant<v> per instance
+    template <int V> using with_variant = ShapeIs<N_, NO_, M_, FT, V>;
     // first row slot of mu rows only (csrc/obca_device.h).  One-wavefront kernels only: in the four-wavefront kernels the trait
     // (2 for (20, 3, 6), 3 for (20, 5, 14) at 256 threads) moved the gated half of C3 by less than its launch spread
     // (profiles/r21_row_kinds_ab.txt), so they keep the generic row loops
@@ -1805,6 +1831,21 @@ struct ShapeIs {
     static constexpr int soc_lds = obca_soc_lds_mw(N_, NO_, M_);
 #endif
 };
+
+// The rolled row loops of a body with a constant variant, f(kinds the row can be, as a type; row): first the rounds that hold other
+// kinds too, with the ladder against constant boundaries, then the rounds of mu rows alone -- from the first slot at or behind THIS
+// variant's r_mu -- which need neither ladder nor preamble.  Both stay rolled: one call per slot with that slot's kinds (the ladder
+// unrolled RPL times, each copy cut to its slot) cost the headline kernel 72 .. 168 B of scratch.
+template <class SHAPE, class F>
+__device__ __forceinline__ void mixed_then_mu(int lane, F f) {
+    constexpr ObcaRowLayout K = obca_row_layout(SHAPE::N, SHAPE::nO, SHAPE::M, SHAPE::variant);
+    constexpr int MUSV = obca_own_mu_slot(SHAPE::N, SHAPE::nO, SHAPE::M, SHAPE::variant, NT), MIXED = NT * MUSV < K.R ? NT * MUSV : K.R;
+    constexpr int MIX = obca_mixed_kinds(SHAPE::N, SHAPE::nO, SHAPE::M, SHAPE::variant, NT);
+#pragma unroll 1
+    for (int r = lane; r < MIXED; r += NT) f(std::integral_constant<int, MIX>{}, r);
+#pragma unroll 1
+    for (int r = lane + NT * MUSV; r < K.R; r += NT) f(std::integral_constant<int, OBCA_KIND_BIT_MU>{}, r);
+}
 
 template <int RPL, bool FROM_MEMORY = false, class DESC = const ObcaLaunch, class SHAPE = ShapeAny>
 __device__ __forceinline__ void obca_ipm_body(DESC& Ain, const int inst, const bool first) {
@@ -1830,15 +1871,22 @@ __device__ __forceinline__ void obca_ipm_body(DESC& Ain, const int inst, const b
 #ifdef OBCA_PROFILE
     const long long prof_body_t0 = wall_clock64();   // (prologue of a pass: descriptor, instance data, start point, scaling, row initialisation -> slot 10 of the one-wavefront kernels)
 #endif
-    if (A.variant[inst] == 0) {                      // masked out by the caller (device-side closed loop)
-        if (lane == 0) { A.status[inst] = OBCA_STATUS_SKIPPED; A.iters[inst] = 0; }
-        return;
-    }
-    {   // anything but obca_mpc4 / 6 / 8, or obca_mpc6 without its terminal set: a per-instance error, nothing is solved
-        const int v = A.variant[inst];
-        if ((v != 4 && v != 6 && v != 8) || (v == 6 && A.term == nullptr)) {
-            if (lane == 0 && first) { A.status[inst] = OBCA_STATUS_BAD_VARIANT; A.iters[inst] = 0; }
+    // (a body compiled for one variant is only entered for an instance of that variant: its driver has answered the masked
+    // instances and the per-instance errors below -- solve_passes)
+    // (the variant is read where it is used, as before there were bodies of one variant: held in a register instead, it changed the
+    // allocator's choices in the generic kernels -- obca_ipm_kernel_r5 88 -> 120 B of scratch, 2 % slower)
+    auto variant_of = [&]() __attribute__((always_inline)) -> int { if constexpr (SHAPE::variant != 0) return SHAPE::variant; else return A.variant[inst]; };
+    if constexpr (SHAPE::variant == 0) {
+        if (A.variant[inst] == 0) {                      // masked out by the caller (device-side closed loop)
+            if (lane == 0) { A.status[inst] = OBCA_STATUS_SKIPPED; A.iters[inst] = 0; }
             return;
+        }
+        {   // anything but obca_mpc4 / 6 / 8, or obca_mpc6 without its terminal set: a per-instance error, nothing is solved
+            const int v = A.variant[inst];
+            if ((v != 4 && v != 6 && v != 8) || (v == 6 && A.term == nullptr)) {
+                if (lane == 0 && first) { A.status[inst] = OBCA_STATUS_BAD_VARIANT; A.iters[inst] = 0; }
+                return;
+            }
         }
     }
     // The caller runs the body up to OBCA_MAX_PASSES times per instance: the start ladder (same rule in oracle/ipm_dense.py:solve
@@ -1863,7 +1911,7 @@ __device__ __forceinline__ void obca_ipm_body(DESC& Ain, const int inst, const b
     // is a bit of ladder_state[0].
     __shared__ int ladder_state[4];      // [0] bits 0-3: escalation level of the current start (0: base penalty), bit 4: the last pass converged with elastic variables left, bit 5: an answer is held, bits 8-11: 1 + the start whose converged-infeasible answer is held (0: the held one did not converge); [1] iterations, [2] factorisations so far, [3] index of the current start (nstarts, nstarts + 1: the dodge passes)
     __shared__ double ladder_f;          // objective of a feasible first dodge pass
-    const int order = OBCA_EFFECTIVE_ORDER(Ain.prm.opt.order, A.variant[inst], A.warm_z != nullptr && (A.warm_use == nullptr || A.warm_use[inst] != 0), Ain.prm.opt.nstarts == 1);
+    const int order = OBCA_EFFECTIVE_ORDER(Ain.prm.opt.order, variant_of(), A.warm_z != nullptr && (A.warm_use == nullptr || A.warm_use[inst] != 0), Ain.prm.opt.nstarts == 1);
     int start_s = 0, escalated = 0, held_bits = 0;
     if (!first) {
         const int st0 = __builtin_amdgcn_readfirstlane(A.status[inst]);     // wave-uniform: the flags below stay scalar
@@ -1871,8 +1919,8 @@ __device__ __forceinline__ void obca_ipm_body(DESC& Ain, const int inst, const b
         const int l0 = __builtin_amdgcn_readfirstlane(ladder_state[0]);
         escalated = l0 & 15; held_bits = l0 & 0xf20;
         start_s = __builtin_amdgcn_readfirstlane(ladder_state[3]);
-        if (A.variant[inst] == 4 && (l0 & 16) && escalated < OBCA_N_ESCALATIONS) ++escalated;
-        else { escalated = 0; if (++start_s >= Ain.prm.opt.nstarts + ((Ain.prm.opt.dodge && A.variant[inst] != 4) ? OBCA_DODGE_PASSES(A.variant[inst]) : 0)) return; }
+        if (variant_of() == 4 && (l0 & 16) && escalated < OBCA_N_ESCALATIONS) ++escalated;
+        else { escalated = 0; if (++start_s >= Ain.prm.opt.nstarts + ((Ain.prm.opt.dodge && variant_of() != 4) ? OBCA_DODGE_PASSES(variant_of()) : 0)) return; }
     }
     const double rho_mult = escalated ? OBCA_RHO_ESCALATION(escalated) : 1.0;
     // (dodge passes nstarts .. nstarts + 3: right, left at OBCA_RESTART_MU, then -- obca_mpc8 only, OBCA_DODGE_PASSES -- right, left at OBCA_DODGE_LEVEL2_MU)
@@ -1883,7 +1931,7 @@ __device__ __forceinline__ void obca_ipm_body(DESC& Ain, const int inst, const b
     // ---- layout ------------------------------------------------------------------------------------
     Lay L;
     L.N = A.N; L.nO = A.nO; L.M = A.M;
-    L.variant = A.variant[inst];
+    L.variant = variant_of();
     L.free_T = (L.variant == 4) ? 1 : 0;
     L.NS = 5 + L.M + 4 * L.nO;
     L.n = (L.N + 1) * (3 + L.M + 4 * L.nO) + 2 * L.N + L.free_T;
@@ -1899,6 +1947,12 @@ __device__ __forceinline__ void obca_ipm_body(DESC& Ain, const int inst, const b
     L.r_lam = L.r_dist + L.npair;
     L.r_mu = L.r_lam + (L.N + 1) * L.M;
     L.R = L.r_mu + (L.N + 1) * 4 * L.nO;
+    if constexpr (SHAPE::variant != 0) {             // the same layout as a constant (csrc/obca_device.h: obca_row_layout)
+        constexpr ObcaRowLayout K = obca_row_layout(SHAPE::N, SHAPE::nO, SHAPE::M, SHAPE::variant);
+        L.free_T = K.free_T; L.n = K.n;
+        L.r_init = K.r_init; L.r_dyn = K.r_dyn; L.r_term = K.r_term; L.r_xb = K.r_xb; L.r_ub = K.r_ub; L.r_acc = K.r_acc; L.r_T = K.r_T;
+        L.r_tx = K.r_tx; L.r_norm = K.r_norm; L.r_dist = K.r_dist; L.r_lam = K.r_lam; L.r_mu = K.r_mu; L.R = K.R;
+    }
 
     // ---- carve (sizes are the handle-wide maxima computed on the host the same way).  GM (rows in memory, RPL = 0): only what
     // the stage-serial sweep touches -- O(N) doubles -- lives in LDS, everything that grows with the number of rows or
@@ -2081,6 +2135,16 @@ __device__ __forceinline__ void obca_ipm_body(DESC& Ain, const int inst, const b
         int bb = 0;
         // heavy per-row code (the row-type switch) runs in rolled loops that stage through LDS; the unrolled
         // register loops below only do arithmetic -- unrolling the switch RPL times exploded register pressure
+        // (a body of one variant: the mixed rounds, then the rounds of mu rows alone -- mixed_then_mu)
+        if constexpr (SHAPE::variant != 0) {
+            mixed_then_mu<SHAPE>(lane, [&](auto km, int r) __attribute__((always_inline)) {
+                constexpr int KM = decltype(km)::value;
+                double lo, up;
+                row_bounds<KM>(L, in, r, lo, up);
+                S.Lb[r] = lo; S.Ub[r] = up;
+                S.tmp[r] = row_value<KM>(L, S, in, S.x, S.ct, S.st, S.cc, r);
+            });
+        } else
         for (int r = lane; r < L.R; r += NT) {
             double lo, up;
             row_bounds(L, in, r, lo, up);
@@ -2333,6 +2397,13 @@ __device__ __forceinline__ void obca_ipm_body(DESC& Ain, const int inst, const b
         const double phik = GET(IV_PHIK);
         const bool phi_known = !soc_pass && isfinite(phik);
         const double tau = GET(IV_TAU);
+        if constexpr (SHAPE::variant != 0) {
+            mixed_then_mu<SHAPE>(lane, [&](auto km, int r) __attribute__((always_inline)) {
+                constexpr int KM = decltype(km)::value, SOFT = OBCA_KIND_BIT_INIT | OBCA_KIND_BIT_DYN;
+                const bool soft = (KM & SOFT) != 0 && ((KM & ~SOFT) == 0 || row_soft(L, r));
+                S.tmp[r] = soft ? S.dy[r] : (row_jdx<KM>(L, S, in, r) + S.gh[r]) * S.Einv[r];
+            });
+        } else
         for (int r = lane; r < L.R; r += NT)
             S.tmp[r] = row_soft(L, r) ? S.dy[r] : (row_jdx(L, S, in, r) + S.gh[r]) * S.Einv[r];
 #if OBCA_NT == 64
@@ -2426,6 +2497,11 @@ __device__ __forceinline__ void obca_ipm_body(DESC& Ain, const int inst, const b
             eval_geom(L, S, S.xt, S.ctt, S.stt, S.cct, lane);
             f_t = eval_objective<true>(L, S, in, S.xt, sf, lane);     // gradient too: gf of the current point is spent
             double th_t = 0.0, phi_t = 0.0;
+            if constexpr (SHAPE::variant != 0) {
+                mixed_then_mu<SHAPE>(lane, [&](auto km, int r) __attribute__((always_inline)) {
+                    S.tmp[r] = row_value<decltype(km)::value>(L, S, in, S.xt, S.ctt, S.stt, S.cct, r);
+                });
+            } else
             for (int r = lane; r < L.R; r += NT) S.tmp[r] = row_value(L, S, in, S.xt, S.ctt, S.stt, S.cct, r);
 #pragma unroll
             for (int j = 0; j < W.slots(); ++j) {
@@ -2736,6 +2812,19 @@ __device__ __noinline__ int terminal_screen_dev(const ObcaLaunch* a, int inst, i
     return 1;
 }
 
+// The passes of the start ladder for ONE variant of a one-wavefront compile-time-shape kernel: a loop over one copy of that variant's
+// body (solve_passes, LOOP, whose own loop every other kernel keeps)
+template <int RPL, class DESC, class SHAPE>
+__device__ __forceinline__ void pass_loop(DESC& A, const int inst, const int* drv_scr) {
+#pragma clang loop unroll(disable)
+    for (int pass = 0; pass < OBCA_MAX_PASSES; ++pass) {
+        obca_ipm_body<RPL, false, DESC, SHAPE>(A, inst, pass == 0);
+        __syncthreads();                                        // status written by thread 0 of this workgroup
+        const int st = A.status[inst];
+        if (st == OBCA_STATUS_OK || st == OBCA_STATUS_ACCEPTABLE || st < OBCA_STATUS_NUMERIC) return;   // nothing (more) to recover
+        if (*drv_scr == 2 && pass + 1 == A.prm.opt.nstarts) return;      // obca_mpc6 without room to dodge: the order's starts were all
+    }
+}
 // rows per lane: 4 covers R <= 256 (N=5/6 with 3 obstacles), 6 covers R <= 384 (demo9, 4-5 obstacles)
 // The solve and, for the instances that need them, the further passes of the start ladder (penalty escalation, next starts).
 // Two forms, chosen per kernel by measurement (tools/build_variant.sh, tools/gpu_variant_bench.py, tools/kernel_resources.py):
@@ -2763,13 +2852,29 @@ __device__ __forceinline__ void solve_passes(DESC& A, DESC& A2, DESC& A3) {
     }
     if constexpr (LOOP) {
         if (inst >= A.B) return;
+        if constexpr (SHAPE::per_variant) {
+            // what the run-time-variant body answers before it solves: masked instances, per-instance errors (the host validates the
+            // variants; a word that is none of the three is not run)
+            const int v = A.variant[inst];
+            if (v == 0 || (v != 4 && v != 6 && v != 8) || (v == 6 && A.term == nullptr)) {
+                if (threadIdx.x == 0) { A.status[inst] = v == 0 ? OBCA_STATUS_SKIPPED : OBCA_STATUS_BAD_VARIANT; A.iters[inst] = 0; }
+                return;
+            }
+            // One wavefront = one instance: ONE wave-uniform branch to the passes of its variant, a loop over one copy of that
+            // variant's body each.  (The branch inside one loop over the passes -- three bodies in one loop -- cost the headline
+            // kernel 104 B of scratch and 437 scratch instructions: DESIGN.md section 9.)
+            if (v == 4) pass_loop<RPL, DESC, typename SHAPE::template with_variant<4>>(A, inst, &drv_scr);
+            else if (v == 6) pass_loop<RPL, DESC, typename SHAPE::template with_variant<6>>(A, inst, &drv_scr);
+            else pass_loop<RPL, DESC, typename SHAPE::template with_variant<8>>(A, inst, &drv_scr);
+        } else {
 #pragma clang loop unroll(disable)
-        for (int pass = 0; pass < OBCA_MAX_PASSES; ++pass) {
-            obca_ipm_body<RPL, false, DESC, SHAPE>(A, inst, pass == 0);
-            __syncthreads();                                        // status written by thread 0 of this workgroup
-            const int st = A.status[inst];
-            if (st == OBCA_STATUS_OK || st == OBCA_STATUS_ACCEPTABLE || st < OBCA_STATUS_NUMERIC) return;   // nothing (more) to recover
-            if (drv_scr == 2 && pass + 1 == A.prm.opt.nstarts) return;       // obca_mpc6 without room to dodge: the order's starts were all
+            for (int pass = 0; pass < OBCA_MAX_PASSES; ++pass) {
+                obca_ipm_body<RPL, false, DESC, SHAPE>(A, inst, pass == 0);
+                __syncthreads();                                        // status written by thread 0 of this workgroup
+                const int st = A.status[inst];
+                if (st == OBCA_STATUS_OK || st == OBCA_STATUS_ACCEPTABLE || st < OBCA_STATUS_NUMERIC) return;   // nothing (more) to recover
+                if (drv_scr == 2 && pass + 1 == A.prm.opt.nstarts) return;       // obca_mpc6 without room to dodge: the order's starts were all
+            }
         }
     } else {
         static_assert(OBCA_MAX_PASSES == 9, "one inlined copy of the body per pass");
@@ -2838,6 +2943,16 @@ OBCA_TU_SHAPE(OBCA_DEFINE_SHAPE_KERNEL)
 #elif OBCA_NT == 64
 // internal (not part of the C ABI; tests/test_row_kinds.py): the slot trait the compile-time-shape kernels are built with
 extern "C" int obca_internal_mu_slot(int N, int nO, int M, int nt) { return obca_mu_slot(N, nO, M, nt); }
+// ... and the constant row layout of a variant (out[15]: the fields of ObcaRowLayout in their order) and the kinds of rows of a slot,
+// as the per-variant bodies of those kernels are built with (tests/test_variant_layout.py)
+extern "C" void obca_internal_row_layout(int N, int nO, int M, int variant, int* out) {
+    const ObcaRowLayout l = obca_row_layout(N, nO, M, variant);
+    const int f[15] = {l.r_init, l.r_dyn, l.r_term, l.r_xb, l.r_ub, l.r_acc, l.r_T, l.r_tx, l.r_norm, l.r_dist, l.r_lam, l.r_mu, l.R, l.n, l.free_T};
+    for (int i = 0; i < 15; ++i) out[i] = f[i];
+}
+extern "C" int obca_internal_slot_kinds(int N, int nO, int M, int variant, int nt, int j) { return obca_slot_kinds(N, nO, M, variant, nt, j); }
+extern "C" int obca_internal_own_mu_slot(int N, int nO, int M, int variant, int nt) { return obca_own_mu_slot(N, nO, M, variant, nt); }
+extern "C" int obca_internal_mixed_kinds(int N, int nO, int M, int variant, int nt) { return obca_mixed_kinds(N, nO, M, variant, nt); }
 extern "C" __global__ void __launch_bounds__(64) obca_ipm_kernel_r4(ObcaLaunch A, ObcaLaunch A2, ObcaLaunch A3) { solve_with_escalation<4, OBCA_LOOP_R4>(A, A2, A3); }
 extern "C" __global__ void __launch_bounds__(64) obca_ipm_kernel_r5(ObcaLaunch A, ObcaLaunch A2, ObcaLaunch A3) { solve_with_escalation<5, OBCA_LOOP_R56>(A, A2, A3); }
 extern "C" __global__ void __launch_bounds__(64) obca_ipm_kernel_r6(ObcaLaunch A, ObcaLaunch A2, ObcaLaunch A3) { solve_with_escalation<6, OBCA_LOOP_R56>(A, A2, A3); }
