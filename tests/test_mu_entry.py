@@ -1,0 +1,124 @@
+"""The entry of x a mu row reads, as a constant (csrc/obca_device.h: obca_mu_entry): in a body of one variant the unrolled row-slot
+loops of the one-wavefront compile-time-shape kernels index the step S.dx and the trial point S.xt with it in the slots that hold mu
+rows alone (csrc/obca_kernel.hip: mu_direct), where the rolled loops staged a copy per row in S.tmp.  No GPU.
+
+The run-time side is the host core itself (csrc/obca_lpi_core.h through tests/native/mu_entry_host.cpp): make_layout, then
+row_value and row_jdx on vectors whose entry t holds t, so what they return is the entry they read.  Compared for every shape of
+OBCA_SHAPES, every variant, every slot from the variant's own first mu slot on and every lane below the ragged edge; the lanes at
+and beyond the edge (rows >= R) are never read by the kernels (`if (r < L.R)`), and every entry must lie inside x and be read by
+one row only.  The variant's own slot is at or before the trait the slot loops carry (obca_mu_slot, the latest of the three).
+
+The GPU cases of tests/test_gpu_mu_direct.py must re-enter the moved code: a line search with a second trial reads S.xt again,
+a second-order correction reads it for its residuals and runs the row steps again, a repeated factorisation rewrites S.tmp (the
+yhat staging) before the row steps.  WITNESS names one instance per case; the Python oracle's trace (oracle/ipm_dense.py, trace=)
+with a count of its trial evaluations per iteration shows on it at least two trials in one line search, a correction started and
+more factorisations than iterations.  Where the correction is not accepted (BACKTRACKS) the line search goes on to a halved step:
+three or more trial evaluations in that iteration."""
+import ctypes
+import functools
+import os
+
+import numpy as np
+import pytest
+
+from tests import native_build
+
+SHAPES = [(5, 2, 2), (5, 3, 6), (5, 4, 10), (5, 5, 14), (5, 6, 18), (6, 2, 2), (6, 3, 6), (6, 4, 10), (6, 5, 14)]      # csrc/obca_device.h: OBCA_SHAPES
+VARIANTS = (4, 6, 8)
+NT = 64
+SRC = os.path.join(native_build.HERE, "native", "mu_entry_host.cpp")
+DEPS = [SRC, os.path.join(native_build.CSRC, "obca_lpi_core.h"), os.path.join(native_build.CSRC, "obca_device.h"),
+        os.path.join(native_build.ROOT, "include", "obca_mpc.h")]
+
+# case of tests/test_gpu_row_kinds.py -> instance (found on the host with the Python oracle over the 32 instances of each case)
+WITNESS = {"s5_3_6_mpc4": 11, "s5_3_6_mpc6": 21, "s5_3_6_mpc8": 30, "s6_3_6": 4, "s5_2_2": 16, "s5_5_14_mpc6": 27}
+BACKTRACKS = ("s5_3_6_mpc4", "s5_3_6_mpc6", "s5_3_6_mpc8", "s5_2_2", "s5_5_14_mpc6")     # (s6_3_6: its one correction is accepted)
+
+
+@functools.lru_cache(maxsize=None)
+def host():
+    return native_build.build_shim("mu_entry_host", [SRC], DEPS)
+
+
+def run_time_entries(N, nO, M, variant):
+    """(first mu row, rows, variables, entry per mu row) from the host core"""
+    out = (ctypes.c_int * 2)()
+    r_mu = next(r for r in range(4096) if host().mu_entry_host_runtime(N, nO, M, variant, r, out) >= 0)
+    entries, n, r = [], 0, r_mu
+    while True:
+        n_r = host().mu_entry_host_runtime(N, nO, M, variant, r, out)
+        if n_r < 0:
+            break
+        assert out[0] == out[1]                    # row_value and row_jdx read the same entry (the Jacobian row is the unit vector there)
+        entries.append(out[0])
+        n, r = n_r, r + 1
+    return r_mu, r, n, np.array(entries)
+
+
+@pytest.mark.parametrize("variant", VARIANTS)
+@pytest.mark.parametrize("shape", SHAPES, ids=lambda s: "s%d_%d_%d" % s)
+def test_constant_entry_is_the_run_time_entry(shape, variant):
+    N, nO, M = shape
+    r_mu, R, n, entries = run_time_entries(N, nO, M, variant)
+    assert R - r_mu == (N + 1) * 4 * nO and len(set(entries.tolist())) == len(entries)
+    assert entries.min() >= 5 + M and entries.max() == (n - 1 if variant != 4 else n - 2)       # the last mu entry ends x (before Topt)
+    own = host().mu_entry_host_own_mu_slot(N, nO, M, variant, NT)
+    assert own == -(-r_mu // NT)
+    assert own <= host().mu_entry_host_mu_slot(N, nO, M, NT)
+    assert host().mu_entry_host_mu_slot(N, nO, M, NT) == max(host().mu_entry_host_own_mu_slot(N, nO, M, v, NT) for v in VARIANTS)
+    nslots = -(-R // NT)
+    assert own <= nslots
+    checked = 0
+    for j in range(own, nslots):
+        for lane in range(NT):
+            r = NT * j + lane
+            if r >= R:                             # beyond the ragged edge: no row, the kernels read nothing
+                continue
+            assert host().mu_entry_host_constant(N, nO, M, variant, NT, j, lane) == entries[r - r_mu], (j, lane)
+            checked += 1
+    assert checked == R - NT * own if NT * own < R else checked == 0
+    # a slot before `own` holds a row that is no mu row: the direct form must not reach it
+    assert NT * (own - 1) < r_mu
+
+
+def test_headline_entries():
+    """(5, 3, 6) under obca_mpc4: 23 entries per stage (pose 3, input 2, lambda 6, mu 12), the last stage without input; rows 128 .. 198
+    are slots 2 and 3, the last slot holds 7"""
+    h = host()
+    assert h.mu_entry_host_own_mu_slot(5, 3, 6, 4, NT) == 2
+    assert [h.mu_entry_host_constant(5, 3, 6, 4, NT, 2, lane) for lane in (0, 10, 11, 63)] == [12, 22, 34, 5 * 23 + 3 + 6 + 4]
+    assert [h.mu_entry_host_constant(5, 3, 6, 4, NT, 3, lane) for lane in (0, 6)] == [5 * 23 + 3 + 6 + 5, 135]
+
+
+@pytest.mark.parametrize("name", sorted(WITNESS))
+def test_witness_instances_reenter_the_moved_code(name):
+    import test_gpu_row_kinds as g
+    from oracle import ipm_dense
+    from oracle.obca_nlp import Problem
+    from vehicle_motion_planning_with_obstacles_avoidance_using_mpc_amd.solver import SolverParams
+    sp = SolverParams()
+    b, N, variant, specialised, _, _ = g.CASES[name]()
+    assert specialised
+    i = WITNESS[name]
+    v = int(b["variant"][i]) if variant is None else variant
+    W = (sp.Q_free, sp.R_free, sp.P_free) if v == 4 else (sp.Q_fix, sp.R_fix, sp.P_fix)
+    p = Problem(v, N, b["m"], b["x0"][i], b["u0"][i], b["xref"][i], b["A"][i], b["b"][i], b["Ts"][i], W[0], W[1][0], W[1][1], W[2],
+                sp.xL, sp.xU, sp.uL, sp.uU, sp.ego, sp.dmin, term=b["term"][i] if v == 6 else None)
+    trace, trials = [], []
+    objective = p.objective
+
+    def counted(z, grad=False, hess=False):        # a plain call is a trial evaluation (and, once, the final objective)
+        if not grad and not hess:
+            trials.append(len(trace) - 1)          # iteration it belongs to: the last one the trace holds
+        return objective(z, grad=grad, hess=hess)
+    p.objective = counted
+    r = ipm_dense.solve(p, trace=trace)
+    assert r.status in (0, 1) and getattr(r, "starts_used", 1) == 1
+    per_iteration = np.bincount(np.array(trials[:-1]), minlength=len(trace))
+    assert per_iteration[:r.iters].min() >= 1 and per_iteration.sum() == len(trials) - 1
+    assert per_iteration.max() >= 2                # a line search with a second trial
+    assert getattr(r, "soc_tried", 0) >= 1         # ... one that starts a second-order correction
+    assert r.nfact > r.iters                       # ... and a repeated factorisation
+    if name in BACKTRACKS:                         # the correction fails and the step is halved: first trial, corrected trial(s), halved trial(s)
+        assert getattr(r, "soc_tried", 0) > getattr(r, "soc_accepted", 0)
+        assert per_iteration.max() >= 3

@@ -235,6 +235,16 @@ constexpr int obca_slot_kinds(int N, int nO, int M, int variant, int nt, int j) 
     return kinds;
 }
 constexpr int obca_own_mu_slot(int N, int nO, int M, int variant, int nt) { return (obca_r_mu(N, nO, M, variant) + nt - 1) / nt; }
+/* The entry of x that mu row r = nt j + lane of that layout reads (its value IS that entry, its Jacobian row the unit vector there):
+   the formula at the end of csrc/obca_kernel.hip: row_value / row_jdx with the stage stride 5 + M + 4 nO and the last stage's
+   missing input (Lay::imu).  Meant for slots j >= obca_own_mu_slot and rows below R; with j and the shape constant it is
+   integer arithmetic on the lane with constant divisors, so that the unrolled slot loops of a body of one variant read x, the
+   trial point and the step at the entry itself where the rolled loops staged a copy per row (tests/test_mu_entry.py compares
+   it with the layout the host core builds at run time). */
+constexpr int obca_mu_entry(int N, int nO, int M, int variant, int nt, int j, int lane) {
+    const int q = nt * j + lane - obca_r_mu(N, nO, M, variant), w4 = 4 * nO, k = q / w4;
+    return k * (5 + M + w4) + (k < N ? 5 : 3) + M + (q - k * w4);
+}
 constexpr int obca_mixed_kinds(int N, int nO, int M, int variant, int nt) {
     int kinds = 0;
     for (int j = 0; j < obca_own_mu_slot(N, nO, M, variant, nt); ++j) kinds |= obca_slot_kinds(N, nO, M, variant, nt, j);

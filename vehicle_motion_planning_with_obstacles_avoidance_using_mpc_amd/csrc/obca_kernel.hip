@@ -574,12 +574,38 @@ struct Err { double E, dual, prim, comp; };
 template <int MUS>
 __device__ __forceinline__ constexpr bool mu_only(int j) { return MUS < OBCA_NO_MU_SLOT && j >= MUS; }
 
+// Slot j of a body of one variant holds mu rows alone -- from THIS variant's first such slot (csrc/obca_device.h: obca_own_mu_slot,
+// at or before the trait mu_slot, which is the latest over the three variants).  The value of such a row is one entry of x and
+// its Jacobian row a unit vector, and the entry is a function of (lane, j) with constant divisors (obca_mu_entry): the unrolled
+// slot loops read S.dx / S.xt there themselves, in one batch beside the other slots' arithmetic, where the rolled loops went
+// through S.tmp[r] -- index, load, store and load again, a dependent chain per round that a wavefront alone on its SIMD waits
+// out.  Writer and reader of S.tmp[r] were the same lane, so no barrier moves.  False wherever the variant is a run-time value.
+// (j is a constant after unrolling: the untaken side of `mu_direct<SHAPE>(j) ? ... : ...` is dropped.)
+template <class SHAPE>
+__device__ __forceinline__ constexpr bool mu_direct(int j) {
+    if constexpr (SHAPE::variant != 0) return j >= obca_own_mu_slot(SHAPE::N, SHAPE::nO, SHAPE::M, SHAPE::variant, NT);
+    else return false;
+}
+// The entry itself.  In the kernels with five or six slots per lane, which spill, the index is formed again at each use (the lane
+// is made opaque): held in registers across the iteration, the indices cost s5_5_14 and s5_6_18 16 B of scratch each over their
+// parents; the four-slot kernels have the registers and keep them.
+template <class SHAPE>
+__device__ __forceinline__ int mu_entry(int j, int lane) {
+    if constexpr (SHAPE::variant != 0) {
+        if constexpr (SHAPE::RPL > 4) __asm__ volatile("" : "+v"(lane));
+        return obca_mu_entry(SHAPE::N, SHAPE::nO, SHAPE::M, SHAPE::variant, NT, j, lane);
+    } else return 0;
+}
+
 // First evaluation of an iteration: the optimality error at mu = 0 (termination tests) and at the current mu (barrier
 // update) differ only in the complementarity term, and the constraint violation theta, the elastic sum and the largest
 // elastic variable read the same registers -- one pass over the rows instead of three.  nz / nrow (numbers of bound
 // multipliers and of rows) never change and are passed in.  th_lane carries the lane's rotation-row part of theta in.
+// FOLD (bodies of one variant): rxmax / crotmax come in as the LANE's parts and join the lane's dual / prim before the one
+// reduction each -- a maximum is exact in any order, so the words are those of two reductions joined afterwards; neither value
+// is read anywhere else.
 struct ErrFirst { Err e0, em; double th, pnsum, emax, dsd, sc; };
-template <int RPL, int MUS>
+template <int RPL, int MUS, bool FOLD = false>
 __device__ __forceinline__ ErrFirst ipm_errors_first(const Lay& L, const Sh& S, const Rows<RPL>& W, double mu, double rho, double rxmax,
                                      double crotmax, double nusum, double th_lane, double nz, double nrow, int lane) {
     double dual = 0.0, prim = 0.0, comp0 = 0.0, compm = 0.0, ysum = 0.0, zsum = 0.0, th = th_lane, pnsum = 0.0, emax = 0.0;
@@ -611,8 +637,13 @@ __device__ __forceinline__ ErrFirst ipm_errors_first(const Lay& L, const Sh& S, 
         }
     }
     ErrFirst o;
-    dual = fmax(red_max(dual), rxmax);
-    prim = fmax(red_max(prim), crotmax);
+    if constexpr (FOLD) {
+        dual = red_max(fmax(dual, rxmax));
+        prim = red_max(fmax(prim, crotmax));
+    } else {
+        dual = fmax(red_max(dual), rxmax);
+        prim = fmax(red_max(prim), crotmax);
+    }
     comp0 = red_max(comp0);
     compm = red_max(compm);
     ysum = red_sum(ysum) + nusum;
@@ -1836,15 +1867,19 @@ struct ShapeIs {
 // kinds too, with the ladder against constant boundaries, then the rounds of mu rows alone -- from the first slot at or behind THIS
 // variant's r_mu -- which need neither ladder nor preamble.  Both stay rolled: one call per slot with that slot's kinds (the ladder
 // unrolled RPL times, each copy cut to its slot) cost the headline kernel 72 .. 168 B of scratch.
-template <class SHAPE, class F>
+// MU_ROUNDS = false: the mixed rounds alone -- where the unrolled slot loop behind the call forms the mu rows' values itself
+// (mu_direct).
+template <class SHAPE, bool MU_ROUNDS = true, class F>
 __device__ __forceinline__ void mixed_then_mu(int lane, F f) {
     constexpr ObcaRowLayout K = obca_row_layout(SHAPE::N, SHAPE::nO, SHAPE::M, SHAPE::variant);
     constexpr int MUSV = obca_own_mu_slot(SHAPE::N, SHAPE::nO, SHAPE::M, SHAPE::variant, NT), MIXED = NT * MUSV < K.R ? NT * MUSV : K.R;
     constexpr int MIX = obca_mixed_kinds(SHAPE::N, SHAPE::nO, SHAPE::M, SHAPE::variant, NT);
 #pragma unroll 1
     for (int r = lane; r < MIXED; r += NT) f(std::integral_constant<int, MIX>{}, r);
+    if constexpr (MU_ROUNDS) {
 #pragma unroll 1
-    for (int r = lane + NT * MUSV; r < K.R; r += NT) f(std::integral_constant<int, OBCA_KIND_BIT_MU>{}, r);
+        for (int r = lane + NT * MUSV; r < K.R; r += NT) f(std::integral_constant<int, OBCA_KIND_BIT_MU>{}, r);
+    }
 }
 
 template <int RPL, bool FROM_MEMORY = false, class DESC = const ObcaLaunch, class SHAPE = ShapeAny>
@@ -2248,8 +2283,10 @@ __device__ __forceinline__ void obca_ipm_body(DESC& Ain, const int inst, const b
         double rxmax = 0.0, crotmax = 0.0, nusum = 0.0, pnsum = 0.0;
         for (int t = lane; t < L.n; t += NT) rxmax = dmaxabs(rxmax, S.bx[t]);
         for (int t = lane; t < 2 * L.npair; t += NT) { crotmax = dmaxabs(crotmax, S.crot[t]); nusum += fabs(S.nu[t]); th += fabs(S.crot[t]); }
-        rxmax = red_max(rxmax); crotmax = red_max(crotmax); nusum = red_sum(nusum);
-        const ErrFirst ef = ipm_errors_first<RPL, MUS>(L, S, W, mu, rho, rxmax, crotmax, nusum, th, GET(IV_CNTNZ), GET(IV_CNTROWS), lane);
+        constexpr bool FOLD = SHAPE::variant != 0;       // (the two maxima are reduced with dual / prim: ipm_errors_first)
+        if constexpr (!FOLD) { rxmax = red_max(rxmax); crotmax = red_max(crotmax); }
+        nusum = red_sum(nusum);
+        const ErrFirst ef = ipm_errors_first<RPL, MUS, FOLD>(L, S, W, mu, rho, rxmax, crotmax, nusum, th, GET(IV_CNTNZ), GET(IV_CNTROWS), lane);
         th = ef.th; pnsum = ef.pnsum; PUT(IV_EMAX, ef.emax);
         const Err e0 = ef.e0;
         const double E0 = e0.E;
@@ -2398,7 +2435,7 @@ __device__ __forceinline__ void obca_ipm_body(DESC& Ain, const int inst, const b
         const bool phi_known = !soc_pass && isfinite(phik);
         const double tau = GET(IV_TAU);
         if constexpr (SHAPE::variant != 0) {
-            mixed_then_mu<SHAPE>(lane, [&](auto km, int r) __attribute__((always_inline)) {
+            mixed_then_mu<SHAPE, false>(lane, [&](auto km, int r) __attribute__((always_inline)) {      // (mu rounds: in the slot loop, mu_direct)
                 constexpr int KM = decltype(km)::value, SOFT = OBCA_KIND_BIT_INIT | OBCA_KIND_BIT_DYN;
                 const bool soft = (KM & SOFT) != 0 && ((KM & ~SOFT) == 0 || row_soft(L, r));
                 S.tmp[r] = soft ? S.dy[r] : (row_jdx<KM>(L, S, in, r) + S.gh[r]) * S.Einv[r];
@@ -2417,7 +2454,7 @@ __device__ __forceinline__ void obca_ipm_body(DESC& Ain, const int inst, const b
                 const bool eq = muk ? false : row_iseq(L, r);
                 const double lo_ = muk ? 0.0 : S.Lb[r], up_ = muk ? INFINITY : S.Ub[r];
                 const bool hasL = !eq && lo_ > -INFINITY, hasU = !eq && up_ < INFINITY;
-                const double dy = S.tmp[r];
+                const double dy = mu_direct<SHAPE>(j) ? (S.dx[mu_entry<SHAPE>(j, lane)] + S.gh[r]) * S.Einv[r] : S.tmp[r];
                 W.dy(j) = dy;
                 {   // cached for the line search and the update (not kept live across the factorisation)
                     const Lin q = row_lin(lo_, up_, eq, W.s(j), W.p(j), W.n(j), S.y[r], W.zL(j), W.zU(j), W.zp(j),
@@ -2498,7 +2535,7 @@ __device__ __forceinline__ void obca_ipm_body(DESC& Ain, const int inst, const b
             f_t = eval_objective<true>(L, S, in, S.xt, sf, lane);     // gradient too: gf of the current point is spent
             double th_t = 0.0, phi_t = 0.0;
             if constexpr (SHAPE::variant != 0) {
-                mixed_then_mu<SHAPE>(lane, [&](auto km, int r) __attribute__((always_inline)) {
+                mixed_then_mu<SHAPE, false>(lane, [&](auto km, int r) __attribute__((always_inline)) {      // (mu rows: S.xt at their entry, mu_direct)
                     S.tmp[r] = row_value<decltype(km)::value>(L, S, in, S.xt, S.ctt, S.stt, S.cct, r);
                 });
             } else
@@ -2514,7 +2551,7 @@ __device__ __forceinline__ void obca_ipm_body(DESC& Ain, const int inst, const b
                     const double st = eq ? 0.0 : W.s(j) + a_try * (dy - W.rs(j)) * W.iDs(j);
                     const double pt = W.p(j) + a_try * (dy - W.rp(j)) * W.iDp(j);
                     const double nt = W.n(j) + a_try * (-dy - W.rn(j)) * W.iDn(j);
-                    const double gt = S.tmp[r];
+                    const double gt = mu_direct<SHAPE>(j) ? S.xt[mu_entry<SHAPE>(j, lane)] : S.tmp[r];
                     th_t += w * fabs(gt - st - pt + nt);
                     phi_t += w * row_barrier(lo_, up_, eq, st, pt, nt, mu, rho);
                 }
@@ -2575,7 +2612,8 @@ __device__ __forceinline__ void obca_ipm_body(DESC& Ain, const int inst, const b
                         const double st = eq ? 0.0 : W.s(j) + a_try * (dy - W.rs(j)) * W.iDs(j);
                         const double pt = W.p(j) + a_try * (dy - W.rp(j)) * W.iDp(j);
                         const double nt = W.n(j) + a_try * (-dy - W.rn(j)) * W.iDn(j);
-                        const double res = S.tmp[r] - st - pt + nt;
+                        const double gt = mu_direct<SHAPE>(j) ? S.xt[mu_entry<SHAPE>(j, lane)] : S.tmp[r];
+                        const double res = gt - st - pt + nt;
                         const double old = soc_start ? W.g(j) - (eq ? 0.0 : W.s(j)) - W.p(j) + W.n(j) : ws_gsoc[r];
                         ws_gsoc[r] = cf * old + res;
                         if (soc_start) ws_dyo[r] = dy;
@@ -2681,7 +2719,7 @@ __device__ __forceinline__ void obca_ipm_body(DESC& Ain, const int inst, const b
 #pragma unroll
         for (int j = 0; j < W.slots(); ++j) {
             const int r = lane + NT * j;
-            if (r < L.R) W.g(j) = S.tmp[r];
+            if (r < L.R) W.g(j) = mu_direct<SHAPE>(j) ? S.xt[mu_entry<SHAPE>(j, lane)] : S.tmp[r];     // (xt shares Y's storage: alive until the next local blocks)
         }
         PUT(IV_F, f_t);           // objective and its gradient (gf) came with the accepted trial as well
         PUT(IV_PHIK, phi_acc);    // and so did the barrier function's value there (valid until the barrier parameter changes)
