@@ -259,6 +259,17 @@ constexpr int obca_mu_slot(int N, int nO, int M, int nt) {
 static_assert(obca_mu_slot(5, 3, 6, 64) == 2 && obca_mu_slot(6, 3, 6, 64) == 3 && obca_mu_slot(5, 2, 2, 64) == 2 &&
               obca_mu_slot(5, 5, 14, 64) == 4 && obca_mu_slot(5, 6, 18, 64) == 4, "mu slots of the one-wavefront shapes");
 static_assert(obca_mu_slot(20, 3, 6, 256) == 2 && obca_mu_slot(20, 5, 14, 256) == 3, "mu slots of the four-wavefront shapes");
+/* Row slots of that layout in which EVERY thread has a row: slots j < R / nt hold rows nt j .. nt j + nt - 1, all below R; the slot
+   behind them is the ragged one (R % nt rows, none where nt divides R).  In a body of one variant the unrolled slot loops run
+   these slots without the test `r < R` (csrc/obca_kernel.hip: row_live): the compiler has no bound on the thread index, so the
+   test against a constant R did not fold there and every such slot kept a lane mask of its own. */
+constexpr int obca_full_slots(int N, int nO, int M, int variant, int nt) { return obca_row_layout(N, nO, M, variant).R / nt; }
+static_assert(obca_full_slots(5, 3, 6, 4, 64) == 3 && obca_full_slots(5, 3, 6, 6, 64) == 3 && obca_full_slots(5, 3, 6, 8, 64) == 3,
+              "full slots of the headline shape (199, 196, 194 rows)");
+static_assert(obca_full_slots(5, 4, 10, 4, 64) == 4 && obca_full_slots(5, 4, 10, 6, 64) == 4 && obca_full_slots(5, 4, 10, 8, 64) == 3,
+              "full slots of (5, 4, 10): 259, 256 (no ragged slot) and 254 rows");
+static_assert(obca_full_slots(5, 2, 2, 4, 64) == 2 && obca_full_slots(5, 2, 2, 6, 64) == 2 && obca_full_slots(5, 2, 2, 8, 64) == 2,
+              "full slots of (5, 2, 2)");
 /* Scratch of the second-order correction: the original direction (n_max + R_max + 2 npair doubles) and the accumulated residuals of
    the rows (R_max).  Where it costs no occupancy it lives in LDS BEHIND everything else the kernel carves -- the one-wavefront kernels
    keep as many workgroups per CU as without it (at most four: one wavefront per SIMD at 512 registers), the four-wavefront kernels

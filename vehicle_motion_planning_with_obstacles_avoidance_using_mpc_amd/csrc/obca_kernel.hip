@@ -597,6 +597,41 @@ __device__ __forceinline__ int mu_entry(int j, int lane) {
     } else return 0;
 }
 
+// Slot j of a body of one variant is FULL -- every lane has a row there -- below obca_full_slots (csrc/obca_device.h): R is an
+// immediate in such a body, but the compiler has no bound on the lane (threadIdx.x), so `lane + NT * j < R` did not fold in the
+// slots whose 64 rows all exist: each unrolled slot kept a lane mask of its own (hoisted out of the iteration loop, then
+// spilled), and every row-state register written under it was merged with its old value.  row_live<FS>(j, r, R) is the test of
+// the unrolled slot loops: true as a constant for j < FS (j is a constant after unrolling), `r < R` everywhere else -- FS = 0
+// wherever the variant is a run-time value (generic, fused, gm / gm1 and four-wavefront kernels), which is the old expression
+// itself.  The loops are numbered (FS_*): a kernel that cannot take one under the keep rule of DESIGN.md section 4 leaves it
+// out of its set (full_slot_sites) and keeps the masked form there.
+enum { FS_ERRORS = 1, FS_COMP = 2, FS_INIT = 4, FS_COUNT = 8, FS_LIN = 16, FS_ROWSTEPS = 32, FS_TRIAL = 64, FS_RESTORE = 128, FS_SOC = 256,
+       FS_ACCEPT = 512, FS_VALUES = 1024, FS_ALL = 2047 };
+#ifndef OBCA_FULL_SLOT_SITES        /* dev knob (tools/build_variant.sh): the set for every shape kernel, for A/B builds */
+#define OBCA_FULL_SLOT_SITES(N, nO, M) full_slot_sites_default(N, nO, M)
+#endif
+// The factorisation's linearisation loop (FS_LIN) is in no kernel's set: unmasked in any of its slots the headline kernel leaves
+// 8 B of scratch for 40 .. 56 B.  The four kernels that spill take the largest set found under which neither their Scratch_Size
+// nor their count of scratch instructions exceeds the parent's (parent -> tree per kernel).
+__host__ __device__ constexpr int full_slot_sites_default(int N, int nO, int M) {
+    if (N == 5 && nO == 4 && M == 10) return FS_ALL & ~(FS_LIN | FS_ACCEPT);
+    if (N == 5 && nO == 5 && M == 14) return FS_ERRORS | FS_COMP;
+    if (N == 5 && nO == 6 && M == 18) return FS_ALL & ~(FS_LIN | FS_COUNT);
+    if (N == 6 && nO == 4 && M == 10) return FS_INIT | FS_TRIAL;
+    // (6, 2, 2) does not spill; with all ten loops its obca_mpc4 copy timed at the parent's upper edge, with these six no variant is slower
+    if (N == 6 && nO == 2 && M == 2) return FS_ERRORS | FS_COMP | FS_ROWSTEPS | FS_TRIAL | FS_ACCEPT | FS_VALUES;
+    return FS_ALL & ~FS_LIN;
+}
+template <class SHAPE, int SITE>
+__device__ __forceinline__ constexpr int full_slots() {
+    if constexpr (SHAPE::variant != 0) return (OBCA_FULL_SLOT_SITES(SHAPE::N, SHAPE::nO, SHAPE::M) & SITE) ? obca_full_slots(SHAPE::N, SHAPE::nO, SHAPE::M, SHAPE::variant, NT) : 0;
+    else return 0;
+}
+template <int FS>
+__device__ __forceinline__ constexpr bool row_live(int j, int r, int R) {
+    if constexpr (FS > 0) return j < FS || r < R;
+    else return r < R;
+}
 // First evaluation of an iteration: the optimality error at mu = 0 (termination tests) and at the current mu (barrier
 // update) differ only in the complementarity term, and the constraint violation theta, the elastic sum and the largest
 // elastic variable read the same registers -- one pass over the rows instead of three.  nz / nrow (numbers of bound
@@ -605,14 +640,14 @@ __device__ __forceinline__ int mu_entry(int j, int lane) {
 // reduction each -- a maximum is exact in any order, so the words are those of two reductions joined afterwards; neither value
 // is read anywhere else.
 struct ErrFirst { Err e0, em; double th, pnsum, emax, dsd, sc; };
-template <int RPL, int MUS, bool FOLD = false>
+template <int RPL, int MUS, bool FOLD = false, int FS = 0>
 __device__ __forceinline__ ErrFirst ipm_errors_first(const Lay& L, const Sh& S, const Rows<RPL>& W, double mu, double rho, double rxmax,
                                      double crotmax, double nusum, double th_lane, double nz, double nrow, int lane) {
     double dual = 0.0, prim = 0.0, comp0 = 0.0, compm = 0.0, ysum = 0.0, zsum = 0.0, th = th_lane, pnsum = 0.0, emax = 0.0;
 #pragma unroll
     for (int j = 0; j < W.slots(); ++j) {
         const int r = lane + NT * j;
-        if (r < L.R) {
+        if (row_live<FS>(j, r, L.R)) {
             const bool muk = mu_only<MUS>(j);
             const double w = muk ? 1.0 : row_w(L, r);
             const bool eq = muk ? false : row_iseq(L, r);
@@ -660,13 +695,13 @@ __device__ __forceinline__ ErrFirst ipm_errors_first(const Lay& L, const Sh& S, 
 // The barrier update's re-check after a decrease.  Of the optimality error only the complementarity term depends on mu: dual,
 // prim and both scalings are those of ipm_errors_first at the same iterate.  One pass over the rows, one reduction; the caller
 // composes E by the same expression, fmax(fmax(dual / sd, prim), comp / sc).
-template <int RPL, int MUS>
+template <int RPL, int MUS, int FS = 0>
 __device__ __forceinline__ double ipm_comp(const Lay& L, const Sh& S, const Rows<RPL>& W, double mu, int lane) {
     double comp = 0.0;
 #pragma unroll
     for (int j = 0; j < W.slots(); ++j) {
         const int r = lane + NT * j;
-        if (r < L.R) {
+        if (row_live<FS>(j, r, L.R)) {
             const bool muk = mu_only<MUS>(j);
             const bool eq = muk ? false : row_iseq(L, r);
             const double lo_ = muk ? 0.0 : S.Lb[r], up_ = muk ? INFINITY : S.Ub[r];
@@ -2192,7 +2227,7 @@ __device__ __forceinline__ void obca_ipm_body(DESC& Ain, const int inst, const b
             W.s(j) = 0.0; W.p(j) = 1.0; W.n(j) = 1.0;
             W.zL(j) = 0.0; W.zU(j) = 0.0; W.zp(j) = 1.0; W.zn(j) = 1.0; W.g(j) = 0.0; W.dy(j) = 0.0;
             W.iDs(j) = 0.0; W.iDp(j) = 1.0; W.iDn(j) = 1.0; W.rs(j) = 0.0; W.rp(j) = 0.0; W.rn(j) = 0.0;
-            if (r < L.R) {
+            if (row_live<full_slots<SHAPE, FS_INIT>()>(j, r, L.R)) {
                 const bool muk = mu_only<MUS>(j);
                 const double lo = muk ? 0.0 : S.Lb[r], up = muk ? INFINITY : S.Ub[r];
                 const bool eq = muk ? false : row_iseq(L, r);
@@ -2232,7 +2267,7 @@ __device__ __forceinline__ void obca_ipm_body(DESC& Ain, const int inst, const b
 #pragma unroll
     for (int j = 0; j < W.slots(); ++j) {
         const int r = lane + NT * j;
-        if (r < L.R) {
+        if (row_live<full_slots<SHAPE, FS_COUNT>()>(j, r, L.R)) {
             if (mu_only<MUS>(j)) { cnt_nz += 3.0; cnt_rows += 1.0; continue; }      // a lower bound and the elastic pair, weight 1
             const double w = row_w(L, r);
             const bool eq = row_iseq(L, r);
@@ -2286,7 +2321,7 @@ __device__ __forceinline__ void obca_ipm_body(DESC& Ain, const int inst, const b
         constexpr bool FOLD = SHAPE::variant != 0;       // (the two maxima are reduced with dual / prim: ipm_errors_first)
         if constexpr (!FOLD) { rxmax = red_max(rxmax); crotmax = red_max(crotmax); }
         nusum = red_sum(nusum);
-        const ErrFirst ef = ipm_errors_first<RPL, MUS, FOLD>(L, S, W, mu, rho, rxmax, crotmax, nusum, th, GET(IV_CNTNZ), GET(IV_CNTROWS), lane);
+        const ErrFirst ef = ipm_errors_first<RPL, MUS, FOLD, full_slots<SHAPE, FS_ERRORS>()>(L, S, W, mu, rho, rxmax, crotmax, nusum, th, GET(IV_CNTNZ), GET(IV_CNTROWS), lane);
         th = ef.th; pnsum = ef.pnsum; PUT(IV_EMAX, ef.emax);
         const Err e0 = ef.e0;
         const double E0 = e0.E;
@@ -2309,7 +2344,7 @@ __device__ __forceinline__ void obca_ipm_body(DESC& Ain, const int inst, const b
             bool first_mu = true;
             while (mu > mu_floor) {
                 // (after a decrease only the complementarity term is formed again: nothing else of E depends on mu)
-                const double Em = first_mu ? ef.em.E : fmax(fmax(ef.dsd, ef.e0.prim), ipm_comp<RPL, MUS>(L, S, W, mu, lane) / ef.sc);
+                const double Em = first_mu ? ef.em.E : fmax(fmax(ef.dsd, ef.e0.prim), ipm_comp<RPL, MUS, full_slots<SHAPE, FS_COMP>()>(L, S, W, mu, lane) / ef.sc);
                 first_mu = false;
                 if (Em > OBCA_KAPPA_EPS * mu) break;
                 mu = fmax(mu_floor, fmin(OBCA_KAPPA_MU * mu, mu * sqrt(mu)));      // mu^theta_mu, theta_mu = 1.5
@@ -2342,7 +2377,7 @@ __device__ __forceinline__ void obca_ipm_body(DESC& Ain, const int inst, const b
 #pragma unroll
             for (int j = 0; j < W.slots(); ++j) {
                 const int r = lane + NT * j;
-                if (r < L.R) {
+                if (row_live<full_slots<SHAPE, FS_LIN>()>(j, r, L.R)) {      // (in no kernel's set: DESIGN.md section 9, round 25)
                     const bool muk = mu_only<MUS>(j);
                     const bool eq = muk ? false : row_iseq(L, r);
                     const double y = S.y[r];
@@ -2449,7 +2484,7 @@ __device__ __forceinline__ void obca_ipm_body(DESC& Ain, const int inst, const b
 #pragma unroll
         for (int j = 0; j < W.slots(); ++j) {
             const int r = lane + NT * j;
-            if (r < L.R) {
+            if (row_live<full_slots<SHAPE, FS_ROWSTEPS>()>(j, r, L.R)) {
                 const bool muk = mu_only<MUS>(j);
                 const bool eq = muk ? false : row_iseq(L, r);
                 const double lo_ = muk ? 0.0 : S.Lb[r], up_ = muk ? INFINITY : S.Ub[r];
@@ -2543,7 +2578,7 @@ __device__ __forceinline__ void obca_ipm_body(DESC& Ain, const int inst, const b
 #pragma unroll
             for (int j = 0; j < W.slots(); ++j) {
                 const int r = lane + NT * j;
-                if (r < L.R) {
+                if (row_live<full_slots<SHAPE, FS_TRIAL>()>(j, r, L.R)) {
                     const bool muk = mu_only<MUS>(j);
                     const bool eq = muk ? false : row_iseq(L, r);
                     const double dy = W.dy(j), w = muk ? 1.0 : row_w(L, r);
@@ -2592,7 +2627,7 @@ __device__ __forceinline__ void obca_ipm_body(DESC& Ain, const int inst, const b
 #pragma unroll
                     for (int j = 0; j < W.slots(); ++j) {
                         const int r = lane + NT * j;
-                        if (r < L.R) W.dy(j) = ws_dyo[r];
+                        if (row_live<full_slots<SHAPE, FS_RESTORE>()>(j, r, L.R)) W.dy(j) = ws_dyo[r];
                     }
                     use_soc = false;
                     SYNC();
@@ -2606,7 +2641,7 @@ __device__ __forceinline__ void obca_ipm_body(DESC& Ain, const int inst, const b
 #pragma unroll
                 for (int j = 0; j < W.slots(); ++j) {
                     const int r = lane + NT * j;
-                    if (r < L.R) {
+                    if (row_live<full_slots<SHAPE, FS_SOC>()>(j, r, L.R)) {
                         const bool eq = mu_only<MUS>(j) ? false : row_iseq(L, r);
                         const double dy = W.dy(j);
                         const double st = eq ? 0.0 : W.s(j) + a_try * (dy - W.rs(j)) * W.iDs(j);
@@ -2666,7 +2701,7 @@ __device__ __forceinline__ void obca_ipm_body(DESC& Ain, const int inst, const b
 #pragma unroll
         for (int j = 0; j < W.slots(); ++j) {
             const int r = lane + NT * j;
-            if (r < L.R) {
+            if (row_live<full_slots<SHAPE, FS_ACCEPT>()>(j, r, L.R)) {
                 const bool muk = mu_only<MUS>(j);
                 const bool eq = muk ? false : row_iseq(L, r);
                 const double lo_ = muk ? 0.0 : S.Lb[r], up_ = muk ? INFINITY : S.Ub[r];
@@ -2719,7 +2754,7 @@ __device__ __forceinline__ void obca_ipm_body(DESC& Ain, const int inst, const b
 #pragma unroll
         for (int j = 0; j < W.slots(); ++j) {
             const int r = lane + NT * j;
-            if (r < L.R) W.g(j) = mu_direct<SHAPE>(j) ? S.xt[mu_entry<SHAPE>(j, lane)] : S.tmp[r];     // (xt shares Y's storage: alive until the next local blocks)
+            if (row_live<full_slots<SHAPE, FS_VALUES>()>(j, r, L.R)) W.g(j) = mu_direct<SHAPE>(j) ? S.xt[mu_entry<SHAPE>(j, lane)] : S.tmp[r];     // (xt shares Y's storage: alive until the next local blocks)
         }
         PUT(IV_F, f_t);           // objective and its gradient (gf) came with the accepted trial as well
         PUT(IV_PHIK, phi_acc);    // and so did the barrier function's value there (valid until the barrier parameter changes)
@@ -2991,6 +3026,8 @@ extern "C" void obca_internal_row_layout(int N, int nO, int M, int variant, int*
 extern "C" int obca_internal_slot_kinds(int N, int nO, int M, int variant, int nt, int j) { return obca_slot_kinds(N, nO, M, variant, nt, j); }
 extern "C" int obca_internal_own_mu_slot(int N, int nO, int M, int variant, int nt) { return obca_own_mu_slot(N, nO, M, variant, nt); }
 extern "C" int obca_internal_mixed_kinds(int N, int nO, int M, int variant, int nt) { return obca_mixed_kinds(N, nO, M, variant, nt); }
+// ... and the number of slots the unrolled slot loops of such a body run without the row test (tests/test_full_slots.py)
+extern "C" int obca_internal_full_slots(int N, int nO, int M, int variant, int nt) { return obca_full_slots(N, nO, M, variant, nt); }
 extern "C" __global__ void __launch_bounds__(64) obca_ipm_kernel_r4(ObcaLaunch A, ObcaLaunch A2, ObcaLaunch A3) { solve_with_escalation<4, OBCA_LOOP_R4>(A, A2, A3); }
 extern "C" __global__ void __launch_bounds__(64) obca_ipm_kernel_r5(ObcaLaunch A, ObcaLaunch A2, ObcaLaunch A3) { solve_with_escalation<5, OBCA_LOOP_R56>(A, A2, A3); }
 extern "C" __global__ void __launch_bounds__(64) obca_ipm_kernel_r6(ObcaLaunch A, ObcaLaunch A2, ObcaLaunch A3) { solve_with_escalation<6, OBCA_LOOP_R56>(A, A2, A3); }
