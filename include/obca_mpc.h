@@ -915,9 +915,91 @@ int obca_scene_select_staged(const double ego[4], int32_t B, int32_t K, int32_t 
                              int32_t* variant_out /* [B] */, int32_t* ok_out /* [B] */, double* min_clear /* [B] or NULL */,
                              int32_t device, void* hip_stream);
 
+/* ------------------------------------------------------------------------------------------------------
+ * Closed loop over scene pools, obstacles on timed tracks (obca_mpc 0.20), on the device.  An obstacle of a pool either
+ * translates for ever at pool_v or is another car of a fleet; here the last Kt slots of every rollout's pool (K slots of
+ * E = 4 rows) follow TRACKS: timed pose sequences (recorded or scripted road users that turn, brake, stop or set off later).
+ * Every loop step this call turns the tracks into the rows of those slots now, their chord velocities and their rows at the
+ * N + 1 stage times of the next solve -- obca_scene_select_staged's stage_A / stage_b / stage_ok with Kt and stage_group = 1
+ * -- and measures what the car really kept from the tracked obstacles over the interval it has just driven.  One step of the
+ * loop: a copy of x0 to x_prev, obca_scene_select_staged, obca_solve_batch, obca_pool_loop_advance, then this call with
+ * measure = 1 and step = the loop step just applied; a start is obca_pool_loop_advance(solved = 0), then this call with
+ * measure = 0.  It has no handle; csrc/obca_pool_tracks_core.h holds the serial definition the kernel reproduces.
+ *
+ * Bt = B / group track blocks, rollout b reads block b / group; track j of a block is pool slot s = K - Kt + j.
+ *   track_state   [B,Kt]: 0 where track_len == 0 (a spare on request); 1 where the track is usable: 1 <= len <= L, the first
+ *                 len pose words and times finite, the times strictly increasing, the four size words finite with
+ *                 size0 + size2 and size1 + size3 finite and > 0, and the rollout's own time words usable (Ts[b] finite and > 0,
+ *                 t0[b] finite); -1 otherwise.  A slot that is not in state 1 is a spare and nothing read from its track
+ *                 reaches an output.
+ *   pose at t     before t_0, or with one knot: knot 0; at or after the last time: the last knot (the obstacle parks); else
+ *                 with i the largest index with t_i <= t (binary search) a = (t - t_i) / (t_i+1 - t_i) and every word is
+ *                 w_i + a (w_i+1 - w_i), each operation rounded on its own; t == t_i gives knot i's words.  Headings are
+ *                 interpolated as numbers: the caller unwraps them.
+ *   times         stage kk of the next solve of rollout b is at t0[b] + (double)(k[b] + kk) Ts[b] (one product, one sum), so
+ *                 stage kk now and stage kk - 1 one step later are one word, and so are their rows.
+ * measure = 1 and n_sub > 0, for every rollout that applied a step in this loop step (k[b] == step + 1), obca_fleet_step's
+ * rules: c = the smallest signed distance, over the n_sub + 1 samples j of the interval, between the car's footprint (ego) at
+ *   the pose interpolated between x_prev[b] and x0[b] and the margin-free rectangle of every usable track at the TRACK's pose
+ *   at the sample's time (the interval's end times interpolated as obca_plan_sweep interpolates: the track itself, across
+ *   knots and turning, not a chord); a pose word of the car that is not finite: +inf.  track_clear_hist[b,step] = c (not
+ *   written when c is NaN: a distance that overflowed).  c NaN: OBCA_DONE_FAILED; c < clearance and flags[b] == OBCA_RUN:
+ *   OBCA_DONE_COLLISION (OBCA_DONE_GOAL stays).  A car flagged here gets variant_out[b] = 0 and every column of xref_out[b] =
+ *   x0[b] (0 for a word that is not finite).  A car that did not step gets no history word and keeps its flag.
+ * Then, always, for every rollout b and every j < Kt, s = K - Kt + j, t = stage 0's time:
+ *   usable track  pool_A / pool_b[b,s] = obca_fleet_step's four rows of the rectangle track_size (in ego's convention) at
+ *                 the pose at t, grown by margin; pool_v[b,s] = (xy(stage 1) - xy(stage 0)) / Ts[b], the chord velocity (0
+ *                 for a word that is not finite), or 0 under OBCA_TRACK_PREDICT_STATIC; stage_A / stage_b[b,j,kk] = the rows
+ *                 at stage kk's pose, kk = 0 .. N; stage_ok[b,j] = 1 iff predict == OBCA_TRACK_PREDICT_TRACK
+ *   spare         obca_grid_pool's spare rows at `far` in the pool slot and at every stage, v = 0, stage_ok 0; also where an
+ *                 interpolated pose is not finite (knot words whose difference overflows)
+ * Nothing written is ever NaN.  Slots 0 .. K-Kt-1 are never touched.
+ * B >= 1, 1 <= Kt <= K <= 64, 1 <= N <= 127, 1 <= L <= 4096, group >= 1 and B % group == 0, 0 <= step < max_steps <= 1024,
+ * 0 <= n_sub <= 256 (0: not measured), measure 0 or 1, predict one of its three values, clearance finite (-1e300: measured,
+ * never stopped), margin >= 0, far > 0 and ego finite, struct_size == sizeof(struct obca_pool_tracks), device >= 0, no pointer
+ * NULL but t0 (NULL: 0 for every rollout).  Every argument is checked before the first HIP call; a refused call
+ * (OBCA_E_INVAL) has no side effect.  Asynchronous on hip_stream. */
+#define OBCA_TRACK_PREDICT_TRACK 0     /* the next solve reads the track's rows per stage (stage_ok = 1) */
+#define OBCA_TRACK_PREDICT_VELOCITY 1  /* the rectangle now, translating at the chord velocity of the next step */
+#define OBCA_TRACK_PREDICT_STATIC 2    /* the rectangle now, standing */
+struct obca_pool_tracks {
+    uint32_t struct_size;              /* sizeof(struct obca_pool_tracks): set by obca_pool_tracks_init() */
+    uint32_t reserved_;
+    int32_t B, K, Kt, N, L, group, max_steps, step, n_sub, predict;
+    double clearance, margin, far;     /* obca_pool_tracks_init: -1e300 (never stops), 0 and 100 */
+    double ego[4];                     /* the car's footprint; obca_pool_tracks_init: 1.7, 0.75, 1.7, 0.75 */
+    /* read-only, Bt = B / group */
+    const double* track_x;             /* [Bt,Kt,L,3] poses (x, y, heading) */
+    const double* track_t;             /* [Bt,Kt,L] */
+    const int32_t* track_len;          /* [Bt,Kt] */
+    const double* track_size;          /* [Bt,Kt,4] in ego's convention */
+    const double* t0;                  /* [B] or NULL */
+    const double* Ts;                  /* [B] */
+    const double* x_prev;              /* [B,3] the poses before the step */
+    const double* x0;                  /* [B,3] the poses now */
+    const int32_t* k;                  /* [B] */
+    /* in and out */
+    int32_t* flags;                    /* [B] */
+    double* pool_A;                    /* [B,K,4,2]: slots K-Kt .. K-1 written */
+    double* pool_b;                    /* [B,K,4] */
+    double* pool_v;                    /* [B,K,2] */
+    double* stage_A;                   /* [B,Kt,N+1,4,2] */
+    double* stage_b;                   /* [B,Kt,N+1,4] */
+    int32_t* stage_ok;                 /* [B,Kt] */
+    int32_t* track_state;              /* [B,Kt] */
+    double* track_clear_hist;          /* [B,max_steps] */
+    double* xref_out;                  /* [B,3,N+1] */
+    int32_t* variant_out;              /* [B] */
+};   /* no typedef: the call has the descriptor's name, so C and C++ say `struct obca_pool_tracks` */
+
+/* zero-fills *d and sets struct_size, clearance, far and ego: the one way to start filling an obca_pool_tracks */
+void obca_pool_tracks_init(struct obca_pool_tracks* d);
+int obca_pool_tracks(const struct obca_pool_tracks* d, int32_t measure, int32_t device, void* hip_stream);
+
 const char* obca_strerror(int code);
-/* "obca_mpc 0.18 (gfx950)" -- the string still reads 0.18: 0.19 adds calls and changes no existing word, and callers detect
- * it by the exported symbols obca_fleet_tracks / obca_scene_select_staged.
+/* "obca_mpc 0.18 (gfx950)" -- the string still reads 0.18: 0.19 and 0.20 add calls and change no existing word, and callers
+ * detect them by the exported symbols obca_fleet_tracks / obca_scene_select_staged and obca_pool_tracks.
+ * 0.20 = obstacles on timed tracks (obca_pool_tracks);
  * 0.19 = fleet prediction by plans (obca_fleet_tracks, obca_scene_select_staged);
  * 0.18 = fleet closed loop (obca_fleet_step);
  * 0.17 = opt-in path time bound of obca_mpc4 (obca_params.time_bound, OBCA_TIME_BOUND_PATH);

@@ -110,6 +110,29 @@ class ObcaFleetTracks(ctypes.Structure):
         self.ego = (ctypes.c_double * 4)(1.7, 0.75, 1.7, 0.75)
 
 
+# obca_pool_tracks.predict (include/obca_mpc.h)
+TRACK_PREDICT_TRACK, TRACK_PREDICT_VELOCITY, TRACK_PREDICT_STATIC = 0, 1, 2
+TRACK_PREDICT = {"track": TRACK_PREDICT_TRACK, "velocity": TRACK_PREDICT_VELOCITY, "static": TRACK_PREDICT_STATIC}
+
+
+class ObcaPoolTracks(ctypes.Structure):
+    """obca_pool_tracks (include/obca_mpc.h), the descriptor of the call of that name.  A new instance is what
+    obca_pool_tracks_init leaves: all zero (predict TRACK, margin 0, t0 NULL), struct_size set, clearance -1e300 (never
+    stops), far 100, the default ego."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("reserved_", ctypes.c_uint32)] + \
+               [(n, ctypes.c_int32) for n in ("B", "K", "Kt", "N", "L", "group", "max_steps", "step", "n_sub", "predict")] + \
+               [("clearance", ctypes.c_double), ("margin", ctypes.c_double), ("far", ctypes.c_double), ("ego", ctypes.c_double * 4)] + \
+               [(n, ctypes.c_void_p) for n in ("track_x", "track_t", "track_len", "track_size", "t0", "Ts", "x_prev", "x0", "k", "flags",
+                                               "pool_A", "pool_b", "pool_v", "stage_A", "stage_b", "stage_ok", "track_state",
+                                               "track_clear_hist", "xref_out", "variant_out")]
+
+    def __init__(self, *a, **kw):
+        super().__init__(*a, **kw)
+        self.struct_size = ctypes.sizeof(ObcaPoolTracks)
+        self.clearance, self.far = -1e300, 100.0
+        self.ego = (ctypes.c_double * 4)(1.7, 0.75, 1.7, 0.75)
+
+
 EXPORTS = ("obca_create", "obca_destroy", "obca_solve_batch", "obca_lds_bytes", "obca_strerror", "obca_version", "obca_params_init",
            "obca_set_profile_buffer", "obca_set_mode", "obca_set_two_sided_sweep", "obca_rollouts_create", "obca_rollouts_destroy", "obca_rollouts_debug_stats", "obca_rollouts_debug_harness",
            "obca_rollouts_reset", "obca_rollouts_step", "obca_rollouts_read", "obca_rollouts_run",
@@ -118,7 +141,8 @@ EXPORTS = ("obca_create", "obca_destroy", "obca_solve_batch", "obca_lds_bytes", 
            "obca_plan_clearance", "obca_plan_sweep", "obca_plan_tighten", "obca_rollouts_audit", "obca_rollouts_set_collision_stop", "obca_rollouts_set_exact_sensing",
            "obca_rollouts_read_clearance", "obca_rollouts_set_swept_rows", "obca_moving_rows_batch", "obca_plan_refine",
            "obca_grid_dilate_batch", "obca_route_resample", "obca_scene_select", "obca_grid_pool", "obca_pool_loop_init", "obca_pool_loop_advance",
-           "obca_fleet_init", "obca_fleet_step", "obca_fleet_tracks_init", "obca_fleet_tracks", "obca_scene_select_staged")
+           "obca_fleet_init", "obca_fleet_step", "obca_fleet_tracks_init", "obca_fleet_tracks", "obca_scene_select_staged",
+           "obca_pool_tracks_init", "obca_pool_tracks")
 
 OBCA_MAX_DYN = 4
 RUN, DONE_GOAL, DONE_CAP, DONE_FAILED, DONE_COLLISION = 0, 1, 2, 3, 4
@@ -271,6 +295,10 @@ def load():
         [vp, vp, vp, vp, vp, vp, i32p, i32p, ctypes.c_int32, ctypes.c_int32, vp, vp, i32p, vp, i32p, vp, vp, i32p, i32p, vp,
          ctypes.c_int32, vp]
     lib.obca_scene_select_staged.restype = ctypes.c_int
+    lib.obca_pool_tracks_init.argtypes = [ctypes.POINTER(ObcaPoolTracks)]
+    lib.obca_pool_tracks_init.restype = None
+    lib.obca_pool_tracks.argtypes = [ctypes.POINTER(ObcaPoolTracks), ctypes.c_int32, ctypes.c_int32, vp]
+    lib.obca_pool_tracks.restype = ctypes.c_int
     lib.obca_lds_bytes.argtypes = [ctypes.POINTER(ObcaDims)]
     lib.obca_lds_bytes.restype = ctypes.c_int64
     lib.obca_strerror.argtypes = [ctypes.c_int]

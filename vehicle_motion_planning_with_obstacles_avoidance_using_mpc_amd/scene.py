@@ -21,7 +21,10 @@ composes ``grid_pool``, ``openloop.route_search`` and ``PoolLoop``: B maps and B
 out.  ``FleetLoop`` puts V of those rollouts into one world: after every step obca_fleet_step (csrc/obca_fleet_core.h) writes
 the other cars of the world into the last V pool slots of each car and measures what the cars did to each other; with predict="plan" obca_fleet_tracks
 (csrc/obca_fleet_tracks_core.h) then turns the plans just applied into rows per stage, which the next ``select`` reads through
-obca_scene_select_staged.  Not here: the reference's 4 -> 6 -> 8 dispatch, its lidar gate and its fixed-time reference preparation
+obca_scene_select_staged.  ``TrackLoop`` gives a world obstacles that follow timed tracks -- recorded or scripted road users
+that turn, brake, stop or set off later: after every step obca_pool_tracks (csrc/obca_pool_tracks_core.h) writes the last Kt pool
+slots from the tracks' poses now, their rows at the stage times of the next solve for obca_scene_select_staged, and measures what
+the car kept from the tracks themselves.  Not here: the reference's 4 -> 6 -> 8 dispatch, its lidar gate and its fixed-time reference preparation
 (``rollouts.DeviceRollouts`` has those, for at most 8 static obstacles).
 """
 import ctypes
@@ -166,6 +169,103 @@ def fleet_tracks(x0, flags, k, xopt, status, V, step, see="all", margin=0.0, far
     _lib.check(_lib.load().obca_fleet_tracks(ctypes.byref(d), _lib.device_index(dev), _lib.stream_ptr(dev)))
     out["track_A"]._obca_keep = (x0, flags, k, xopt, status)     # the launch is asynchronous: see ``select``
     for a in out["track_A"]._obca_keep:
+        a.record_stream(torch.cuda.current_stream(dev))
+    return out
+
+
+def check_tracks(tracks, track_t, track_len, track_size):
+    """host arrays of tracks (``pool_tracks``' first four arguments) checked by obca_pool_tracks' own rules; raises ValueError for
+    the first track that is not usable.  A length of 0 (a spare on request) passes."""
+    import numpy as np
+    x, t, ln, size = np.asarray(tracks, float), np.asarray(track_t, float), np.asarray(track_len), np.asarray(track_size, float)
+    L = x.shape[2]
+    for bt in range(x.shape[0]):
+        for j in range(x.shape[1]):
+            n = int(ln[bt, j])
+            if n == 0:
+                continue
+            why = None
+            if not 1 <= n <= L:
+                why = "length %d outside 1 .. %d" % (n, L)
+            elif not (np.all(np.isfinite(x[bt, j, :n])) and np.all(np.isfinite(t[bt, j, :n]))):
+                why = "a pose word or a time that is not finite"
+            elif not np.all(np.diff(t[bt, j, :n]) > 0.0):
+                why = "times that do not increase strictly"
+            elif not (np.all(np.isfinite(size[bt, j])) and size[bt, j, 0] + size[bt, j, 2] > 0.0 and size[bt, j, 1] + size[bt, j, 3] > 0.0):
+                why = "a size that is no rectangle"
+            if why:
+                raise ValueError("track %d of block %d is not usable: %s" % (j, bt, why))
+
+
+def pool_tracks(tracks, track_t, track_len, track_size, Ts, k, x0, pool_A, pool_b, pool_v, N, group=1, t0=None, predict="track",
+                margin=0.0, far=100.0, measure=False, step=0, x_prev=None, flags=None, max_steps=1, n_sub=8, clearance=None,
+                ego=DEFAULT_EGO, out=None, device=None):
+    """obca_pool_tracks: timed tracks as the rows of the last Kt pool slots, now and at the N + 1 stage times of the next solve.
+    tracks [Bt,Kt,L,3] poses (x, y, heading; unwrapped), track_t [Bt,Kt,L], track_len [Bt,Kt] int32, track_size [Bt,Kt,4] in
+    ego's convention; rollout b of B = Bt * group reads block b // group.  Ts [B] or a float, k [B] int32 and x0 [B,3] the
+    loop's state, t0 [B] or None; pool_A [B,K,4,2], pool_b [B,K,4], pool_v [B,K,2] contiguous float64 DEVICE tensors, whose
+    slots K - Kt .. K - 1 are written IN PLACE.  measure=True also measures the interval x_prev -> x0 of every rollout with
+    k == step + 1 against the tracks themselves (n_sub + 1 samples) and may end it: flags [B] int32 is updated in place
+    (clearance=None: measured, never stopped).
+
+    Returns a dict of device tensors on the current stream, no host synchronisation: stage_A [B,Kt,N+1,4,2], stage_b
+    [B,Kt,N+1,4] and stage_ok [B,Kt] int32 -- ``select``'s arguments of those names with stage_group = 1 -- track_state [B,Kt]
+    int32 (1 usable, 0 a length of 0, -1 not usable: a spare), track_clear_hist [B,max_steps] (word ``step`` written where
+    measured), flags, xref_out [B,3,N+1] and variant_out [B] (written for a rollout that measure ended).  ``out``: a dict of
+    such tensors to write into."""
+    import torch
+    if not torch.cuda.is_available():
+        raise RuntimeError("scene.pool_tracks needs a ROCm GPU; there is no CPU fallback on the product path")
+    if predict not in _lib.TRACK_PREDICT:
+        raise ValueError("predict is one of %s" % sorted(_lib.TRACK_PREDICT))
+    dev = _dev_of(device, pool_A, tracks, x0)
+    t = lambda a, dt=torch.float64: torch.as_tensor(a, dtype=dt, device=dev).contiguous()
+    tracks, track_t, track_len, track_size = t(tracks), t(track_t), t(track_len, torch.int32), t(track_size)
+    if tracks.dim() != 4 or tracks.shape[3] != 3:
+        raise ValueError("expected tracks [Bt,Kt,L,3], got %s" % (tuple(tracks.shape),))
+    Bt, Kt, L = (int(v) for v in tracks.shape[:3])
+    group, N = int(group), int(N)
+    B = Bt * group
+    x0, k = t(x0), t(k, torch.int32)
+    Ts = torch.as_tensor(Ts, dtype=torch.float64, device=dev)
+    Ts = (Ts.expand(B) if Ts.dim() == 0 else Ts).contiguous()
+    t0 = None if t0 is None else t(t0)
+    x_prev = x0 if x_prev is None else t(x_prev)
+    flags = torch.zeros(B, dtype=torch.int32, device=dev) if flags is None else flags
+    for a in (pool_A, pool_b, pool_v, flags):
+        if not (isinstance(a, torch.Tensor) and a.device == dev and a.is_contiguous()):
+            raise ValueError("pool_A, pool_b, pool_v and flags are written in place: contiguous tensors on %s" % dev)
+    if pool_A.dtype != torch.float64 or pool_b.dtype != torch.float64 or pool_v.dtype != torch.float64 or flags.dtype != torch.int32:
+        raise ValueError("expected float64 pools and int32 flags")
+    K = int(pool_b.shape[1]) if pool_b.dim() == 3 else -1
+    for a, shape in ((track_t, (Bt, Kt, L)), (track_len, (Bt, Kt)), (track_size, (Bt, Kt, 4)), (Ts, (B,)), (k, (B,)), (x0, (B, 3)),
+                     (x_prev, (B, 3)), (flags, (B,)), (pool_A, (B, K, 4, 2)), (pool_b, (B, K, 4)), (pool_v, (B, K, 2))) + \
+            (() if t0 is None else ((t0, (B,)),)):
+        if tuple(a.shape) != shape:
+            raise ValueError("expected shape %s, got %s" % (shape, tuple(a.shape)))
+    S = int(max_steps)
+    if out is None:
+        out = {"stage_A": torch.empty(B, Kt, N + 1, 4, 2, dtype=torch.float64, device=dev),
+               "stage_b": torch.empty(B, Kt, N + 1, 4, dtype=torch.float64, device=dev),
+               "stage_ok": torch.empty(B, Kt, dtype=torch.int32, device=dev),
+               "track_state": torch.empty(B, Kt, dtype=torch.int32, device=dev),
+               "track_clear_hist": torch.full((B, max(S, 1)), float("inf"), dtype=torch.float64, device=dev),
+               "xref_out": torch.zeros(B, 3, N + 1, dtype=torch.float64, device=dev),
+               "variant_out": torch.zeros(B, dtype=torch.int32, device=dev)}
+    out["flags"] = flags
+    d = _lib.ObcaPoolTracks()
+    d.B, d.K, d.Kt, d.N, d.L, d.group, d.max_steps, d.step, d.n_sub = B, K, Kt, N, L, group, S, int(step), int(n_sub)
+    d.predict, d.margin, d.far = _lib.TRACK_PREDICT[predict], float(margin), float(far)
+    d.clearance = NEVER_STOP if clearance is None else float(clearance)
+    d.ego = (ctypes.c_double * 4)(*[float(v) for v in ego])
+    ins = (("track_x", tracks), ("track_t", track_t), ("track_len", track_len), ("track_size", track_size), ("t0", t0), ("Ts", Ts),
+           ("x_prev", x_prev), ("x0", x0), ("k", k))
+    for name, a in ins + (("flags", flags), ("pool_A", pool_A), ("pool_b", pool_b), ("pool_v", pool_v)) + \
+            tuple((n, out[n]) for n in ("stage_A", "stage_b", "stage_ok", "track_state", "track_clear_hist", "xref_out", "variant_out")):
+        setattr(d, name, None if a is None else a.data_ptr())
+    _lib.check(_lib.load().obca_pool_tracks(ctypes.byref(d), 1 if measure else 0, _lib.device_index(dev), _lib.stream_ptr(dev)))
+    out["stage_A"]._obca_keep = tuple(a for _, a in ins if a is not None)     # the launch is asynchronous: see ``select``
+    for a in out["stage_A"]._obca_keep:
         a.record_stream(torch.cuda.current_stream(dev))
     return out
 
@@ -640,6 +740,159 @@ class FleetLoop(PoolLoop):
         interval the car drove, +inf where nothing was measured), agent_min_clear [B]"""
         out = super().read()
         out.update(agent_clear=self.agent_clear.clone(), agent_min_clear=self.agent_clear.min(dim=1).values)
+        return out
+
+
+class TrackLoop(PoolLoop):
+    """``PoolLoop`` whose worlds also hold obstacles that follow timed tracks: recorded or scripted road users that turn, brake,
+    stop or set off later.  The caller's pool -- pool_A [B,Ks,4,2], pool_b [B,Ks,4] and optionally pool_v [B,Ks,2], or None for
+    Ks = 0 -- is the static part; the loop appends Kt slots, slot Ks + j being track j of the rollout's block: tracks
+    [Bt,Kt,L,3] poses (x, y, heading; unwrap the headings), track_t [Bt,Kt,L] strictly increasing times, track_len [Bt,Kt]
+    (0: the slot is a spare), track_size [Bt,Kt,4] in ego's convention (None: the ego's), rollout b of B = Bt * group reading
+    block b // group.  Before its first time an obstacle stands at its first knot, after its last it parks at the last one.
+    The clock of rollout b is t0[b] + k Ts[b] (t0 None: 0).  Tracks given as host arrays are checked here and an unusable one
+    raises; device tensors are taken at their word and an unusable track becomes a spare (``read()``'s track_state -1).
+
+    predict="track": the next solve reads the track's rows at its own stage times (obca_scene_select_staged, stage_group 1);
+    "velocity": the rectangle now, translating at the chord velocity of the next step; "static": the rectangle now.  The pool
+    slots themselves, and with them obca_pool_loop_advance's ``clear``, are the chord prediction under every word; what the
+    car really kept from the tracked obstacles is ``read()``'s track_clear [B,S], measured against the tracks themselves at
+    track_n_sub + 1 samples per driven interval (0: not measured); a car closer than ``track_clearance`` ends with flag
+    "collision" (None: measured, never stopped).  Variant 8 only: the clock needs a fixed step.  rounds >= 1 is refused under
+    "track": ``solve_scene`` is not staged.
+
+    One step: x_prev = x0, ``PoolLoop``'s step, then obca_pool_tracks (arithmetic and serial definition in
+    csrc/obca_pool_tracks_core.h) with measure = 1; ``reset()`` calls it with measure = 0.
+
+        loop = TrackLoop(solver, walls_A, walls_b, start, goal, path, path_len, 1.5, tracks, track_t, track_len, margin=0.1).run()
+        out = loop.read()                                         # out["flags"], out["track_min_clear"], out["track_state"], ...
+    """
+
+    def __init__(self, solver, pool_A, pool_b, start, goal, path, path_len, Ts, tracks, track_t, track_len, track_size=None,
+                 group=1, t0=None, predict="track", margin=0.0, far=100.0, track_clearance=None, track_n_sub=8, pool_v=None, **kw):
+        import numpy as np
+        import torch
+        if not torch.cuda.is_available():
+            raise RuntimeError("scene.TrackLoop needs a ROCm GPU; there is no CPU fallback on the product path")
+        dev = solver.device
+        if predict not in _lib.TRACK_PREDICT:
+            raise ValueError("predict is one of %s" % sorted(_lib.TRACK_PREDICT))
+        if predict == "track" and int(kw.get("rounds", 0)) >= 1:
+            raise ValueError('predict="track" needs rounds = 0: solve_scene is not staged')
+        if kw.get("variant") not in (None, 8):
+            raise ValueError("variant %r: the tracks' clock needs a fixed step, the loop runs obca_mpc8 (8) only" % (kw["variant"],))
+        kw["variant"] = 8
+        f64 = lambda a: torch.as_tensor(a, dtype=torch.float64, device=dev).contiguous()
+        on_host = lambda a: not (isinstance(a, torch.Tensor) and a.is_cuda)
+        shape = tuple(np.shape(tracks) if on_host(tracks) else tracks.shape)
+        if len(shape) != 4 or shape[3] != 3 or shape[1] < 1 or shape[2] < 1:
+            raise ValueError("expected tracks [Bt,Kt,L,3], got %s" % (shape,))
+        Bt, Kt, L = shape[:3]
+        if track_size is None:
+            track_size = np.tile(np.asarray(kw.get("ego", DEFAULT_EGO), float), (Bt, Kt, 1))
+        for a, want in ((track_t, (Bt, Kt, L)), (track_len, (Bt, Kt)), (track_size, (Bt, Kt, 4))):
+            if tuple(np.shape(a) if on_host(a) else a.shape) != want:
+                raise ValueError("expected shape %s next to tracks %s, got %s" % (want, shape, tuple(np.shape(a) if on_host(a) else a.shape)))
+        if all(on_host(a) for a in (tracks, track_t, track_len, track_size)):
+            check_tracks(tracks, track_t, track_len, track_size)
+        start = torch.as_tensor(start, dtype=torch.float64, device=dev)
+        B, group = int(start.shape[0]), int(group)
+        if group < 1 or Bt * group != B:
+            raise ValueError("B = %d rollouts are not %d track blocks of group = %d" % (B, Bt, group))
+        if pool_A is None or pool_b is None:
+            if pool_A is not None or pool_b is not None or pool_v is not None:
+                raise ValueError("pool_A and pool_b are given together; without them there is no pool_v")
+            sA, sb = torch.zeros(B, 0, 4, 2, dtype=torch.float64, device=dev), torch.zeros(B, 0, 4, dtype=torch.float64, device=dev)
+        else:
+            sA, sb = f64(pool_A), f64(pool_b)
+        if sA.dim() != 4 or sb.dim() != 3 or tuple(sA.shape) != tuple(sb.shape) + (2,) or sb.shape[0] != B or sb.shape[2] != 4:
+            raise ValueError("expected pool_A [B,Ks,4,2], pool_b [B,Ks,4] with B = %d" % B)
+        Ks = self.Ks = int(sb.shape[1])
+        if Ks + Kt > 64:
+            raise ValueError("Ks + Kt = %d slots: a pool holds 64 at the most" % (Ks + Kt))
+        sv = torch.zeros(B, Ks, 2, dtype=torch.float64, device=dev) if pool_v is None else solver._dev(pool_v, (B, Ks, 2))
+        # the tracked slots start as spares; obca_pool_tracks writes them at every reset and after every step
+        far = float(far)
+        spare_A = torch.tensor([[0.0, 1.0], [1.0, 0.0], [0.0, -1.0], [-1.0, 0.0]], dtype=torch.float64, device=dev)
+        spare_b = torch.tensor([-far, -far, far + 1.0, far + 1.0], dtype=torch.float64, device=dev)
+        full_A = torch.cat([sA, spare_A.expand(B, Kt, 4, 2)], dim=1).contiguous()
+        full_b = torch.cat([sb, spare_b.expand(B, Kt, 4)], dim=1).contiguous()
+        full_v = torch.cat([sv, torch.zeros(B, Kt, 2, dtype=torch.float64, device=dev)], dim=1).contiguous()
+        self.Kt, self.L, self.group, self.predict, self.margin, self.far = Kt, L, group, predict, float(margin), far
+        self.tracks, self.track_t, self.track_size = f64(tracks), f64(track_t), f64(track_size)
+        self.track_len = torch.as_tensor(track_len, dtype=torch.int32, device=dev).contiguous()
+        self.t0 = None if t0 is None else solver._dev(torch.as_tensor(t0, dtype=torch.float64).expand(B)
+                                                      if torch.as_tensor(t0).dim() == 0 else t0, (B,))
+        self.track_clearance = NEVER_STOP if track_clearance is None else float(track_clearance)
+        self.track_n_sub = int(track_n_sub)
+        self._tdesc = None                                   # made by the first reset, which PoolLoop's constructor ends with
+        super().__init__(solver, full_A, full_b, start, goal, path, path_len, Ts, pool_v=full_v, **kw)
+
+    def _make_tracks(self):
+        torch, dev, B, Kt, N1 = self.torch, self.device, self.B, self.Kt, self.N + 1
+        self.x_prev = torch.zeros(B, 3, dtype=torch.float64, device=dev)
+        self.track_clear = torch.zeros(B, self.max_steps, dtype=torch.float64, device=dev)
+        self.stage_A = torch.zeros(B, Kt, N1, 4, 2, dtype=torch.float64, device=dev)
+        self.stage_b = torch.zeros(B, Kt, N1, 4, dtype=torch.float64, device=dev)
+        self.stage_ok = torch.zeros(B, Kt, dtype=torch.int32, device=dev)
+        self.track_state = torch.zeros(B, Kt, dtype=torch.int32, device=dev)
+        d = self._tdesc = _lib.ObcaPoolTracks()
+        d.B, d.K, d.Kt, d.N, d.L, d.group, d.max_steps, d.n_sub = B, self.K, Kt, self.N, self.L, self.group, self.max_steps, self.track_n_sub
+        d.predict, d.clearance, d.margin, d.far = _lib.TRACK_PREDICT[self.predict], self.track_clearance, self.margin, self.far
+        d.ego = (ctypes.c_double * 4)(*self.ego)
+        for name, t in (("track_x", self.tracks), ("track_t", self.track_t), ("track_len", self.track_len),
+                        ("track_size", self.track_size), ("t0", self.t0), ("Ts", self.Ts), ("x_prev", self.x_prev), ("x0", self.x0),
+                        ("k", self.k), ("flags", self.flags), ("pool_A", self.pool_A), ("pool_b", self.pool_b), ("pool_v", self.pool_v),
+                        ("stage_A", self.stage_A), ("stage_b", self.stage_b), ("stage_ok", self.stage_ok),
+                        ("track_state", self.track_state), ("track_clear_hist", self.track_clear), ("xref_out", self.xref),
+                        ("variant_out", self.variant_out)):
+            setattr(d, name, None if t is None else t.data_ptr())
+
+    def _tensors(self):
+        own = super()._tensors() + [self.tracks, self.track_t, self.track_len, self.track_size]
+        if self.t0 is not None:
+            own.append(self.t0)
+        if self._tdesc is not None:
+            own += [self.x_prev, self.track_clear, self.stage_A, self.stage_b, self.stage_ok, self.track_state]
+        return own
+
+    def _select(self):
+        if self.predict != "track":
+            return super()._select()
+        return select(self.pool_A, self.pool_b, self.xref, self.n_sel, pool_v=self.pool_v, Ts=self.Ts, x0=self.x0,
+                      variant=self.variant_out, n_sub=self.select_n_sub, ego=self.ego, device=self.device, stage_A=self.stage_A,
+                      stage_b=self.stage_b, stage_ok=self.stage_ok, stage_group=1)
+
+    def _pool_tracks(self, measure, step):
+        self._tdesc.step = int(step)
+        _lib.check(self.lib.obca_pool_tracks(ctypes.byref(self._tdesc), int(measure), _lib.device_index(self.device),
+                                             _lib.stream_ptr(self.device)))
+
+    def reset(self):
+        super().reset()
+        if self._tdesc is None:
+            self._make_tracks()
+            self._on_stream()
+        self.x_prev.copy_(self.x0)
+        self.track_clear.fill_(float("inf"))
+        self._pool_tracks(0, 0)
+
+    def _step(self):
+        self.x_prev.copy_(self.x0)
+        super()._step()
+        idx = self.steps_enqueued - 1
+        if idx < self.max_steps:
+            self._pool_tracks(1, idx)
+        else:                                                # beyond the cap nobody steps: the rows alone
+            self._pool_tracks(0, 0)
+
+    def read(self):
+        """``PoolLoop.read()``'s dict and track_clear [B,S] (the smallest distance to a tracked obstacle over every interval the
+        car drove, measured against the tracks themselves; +inf where nothing was measured), track_min_clear [B] and
+        track_state [B,Kt] (1 usable, 0 a length of 0, -1 not usable: a spare)"""
+        out = super().read()
+        out.update(track_clear=self.track_clear.clone(), track_min_clear=self.track_clear.min(dim=1).values,
+                   track_state=self.track_state.clone())
         return out
 
 
