@@ -632,6 +632,32 @@ __device__ __forceinline__ constexpr bool row_live(int j, int r, int R) {
     if constexpr (FS > 0) return j < FS || r < R;
     else return r < R;
 }
+// The eight step-length guards of the rowsteps slot loop as selects.  `if (ds < 0.0) a_max = fmin(a_max, v);` guards two or three
+// VALU instructions behind a test that, with 64 rows in flight, some lane almost always passes: the wavefront runs the guarded
+// code anyway and pays the compare, the exec save, the branch and the restore on top, and every such frame holds an SGPR pair
+// and makes the allocator merge what is written under it.  The select form feeds the running minimum its NEUTRAL operand where
+// the guard fails, `a_max = fmin(a_max, ds < 0.0 ? v : INFINITY)`: a_max and a_z start at 1.0 and only pass through fmin, so they
+// are never NaN, and fmin(a, +inf) == a; where the guard holds the operand is the guarded expression itself -- every word is the
+// guarded form's.  What a lane whose guard fails computes (the reciprocal of a non-negative step) is discarded by the select.
+// A kernel takes the form under the keep rule of DESIGN.md section 4 (guard_selects_default: in the manner of
+// full_slot_sites_default); it is off wherever the variant is a run-time value (generic, fused, gm / gm1 and four-wavefront
+// kernels), whose device code is the guarded form's.  STEP_MIN spells both forms out at the site: the guarded one is the old
+// statement, token for token.
+#ifndef OBCA_GUARD_SELECTS          /* dev knob (tools/build_variant.sh): the same answer for every shape kernel, for A/B builds */
+#define OBCA_GUARD_SELECTS(N, nO, M) guard_selects_default(N, nO, M)
+#endif
+// Taken where neither Scratch_Size nor the count of scratch instructions exceeds the parent's and no variant is slower beyond its
+// spread: (5, 4, 10), (5, 6, 18), (6, 4, 10) and (6, 5, 14) gain 16 .. 32 B of scratch with it,
+// (6, 2, 2) is 1 % slower under obca_mpc4, (5, 5, 14) 0.4 % under obca_mpc6.
+__host__ __device__ constexpr bool guard_selects_default(int N, int nO, int M) {
+    return (N == 5 && nO == 3 && M == 6) || (N == 5 && nO == 2 && M == 2) || (N == 6 && nO == 3 && M == 6);
+}
+template <class SHAPE>
+__device__ __forceinline__ constexpr bool guard_selects() {
+    if constexpr (SHAPE::variant != 0) return OBCA_GUARD_SELECTS(SHAPE::N, SHAPE::nO, SHAPE::M);
+    else return false;
+}
+#define STEP_MIN(SEL, acc, cond, val) { if constexpr (SEL) acc = fmin(acc, (cond) ? (val) : INFINITY); else if (cond) acc = fmin(acc, val); }
 // First evaluation of an iteration: the optimality error at mu = 0 (termination tests) and at the current mu (barrier
 // update) differ only in the complementarity term, and the constraint violation theta, the elastic sum and the largest
 // elastic variable read the same registers -- one pass over the rows instead of three.  nz / nrow (numbers of bound
@@ -2503,24 +2529,25 @@ __device__ __forceinline__ void obca_ipm_body(DESC& Ain, const int inst, const b
                 const double s = W.s(j), p = W.p(j), n = W.n(j);
                 double gs = eq ? 0.0 : W.rs(j) + S.y[r];
                 const double ids = rcp64(ds), ip = rcp64(p), inn = rcp64(n);     // (ids only used under ds != 0)
+                constexpr bool GSEL = guard_selects<SHAPE>();      // (the eight step-length guards: STEP_MIN)
                 if (hasL) {
                     const double sl = s - lo_, zL = W.zL(j);
-                    if (ds < 0.0) a_max = fmin(a_max, -tau * sl * ids);
+                    STEP_MIN(GSEL, a_max, ds < 0.0, -tau * sl * ids)
                     const double dz = (mu - zL * ds) * rcp64(sl) - zL;
-                    if (dz < 0.0) a_z = fmin(a_z, -tau * zL * rcp64(dz));
+                    STEP_MIN(GSEL, a_z, dz < 0.0, -tau * zL * rcp64(dz))
                 }
                 if (hasU) {
                     const double su = up_ - s, zU = W.zU(j);
-                    if (ds > 0.0) a_max = fmin(a_max, tau * su * ids);
+                    STEP_MIN(GSEL, a_max, ds > 0.0, tau * su * ids)
                     const double dz = (mu + zU * ds) * rcp64(su) - zU;
-                    if (dz < 0.0) a_z = fmin(a_z, -tau * zU * rcp64(dz));
+                    STEP_MIN(GSEL, a_z, dz < 0.0, -tau * zU * rcp64(dz))
                 }
-                if (dp < 0.0) a_max = fmin(a_max, -tau * p * rcp64(dp));
-                if (dn < 0.0) a_max = fmin(a_max, -tau * n * rcp64(dn));
+                STEP_MIN(GSEL, a_max, dp < 0.0, -tau * p * rcp64(dp))
+                STEP_MIN(GSEL, a_max, dn < 0.0, -tau * n * rcp64(dn))
                 const double zp = W.zp(j), zn = W.zn(j);
                 const double dzp = (mu - zp * dp) * ip - zp, dzn = (mu - zn * dn) * inn - zn;
-                if (dzp < 0.0) a_z = fmin(a_z, -tau * zp * rcp64(dzp));
-                if (dzn < 0.0) a_z = fmin(a_z, -tau * zn * rcp64(dzn));
+                STEP_MIN(GSEL, a_z, dzp < 0.0, -tau * zp * rcp64(dzp))
+                STEP_MIN(GSEL, a_z, dzn < 0.0, -tau * zn * rcp64(dzn))
                 if (!phi_known) phi += w * row_barrier(lo_, up_, eq, s, p, n, mu, rho);
                 dphi += w * (gs * ds + (rho - mu * ip) * dp + (rho - mu * inn) * dn);
             }

@@ -32,6 +32,17 @@
 #define LPI_TRACE_LINE(...)
 #endif
 
+/* Observation points of the fraction-to-the-boundary rule, for a host exerciser that defines them before this header
+   (tests/native/step_guards_host.cpp): OBCA_LPI_STEP_GUARD(k, v) where guard k -- 0 / 1 lower / upper slack, 2 / 3 p / n,
+   4 .. 7 their multipliers -- held and offered v; OBCA_LPI_STEP_LENGTHS(a_max, a_z) once per iteration with the results.
+   Nothing by default: the device code and every other host build are those without them. */
+#ifndef OBCA_LPI_STEP_GUARD
+#define OBCA_LPI_STEP_GUARD(k, v) ((void)0)
+#endif
+#ifndef OBCA_LPI_STEP_LENGTHS
+#define OBCA_LPI_STEP_LENGTHS(a_max, a_z) ((void)0)
+#endif
+
 namespace lpi {
 
 constexpr int MW = OBCA_MAX_EDGES + 6;
@@ -1252,25 +1263,26 @@ LPI_FN Out solve_instance(const Lay& L, const Sh& S, const Inst& in, const ObcaO
             const double gs = eq ? 0.0 : q.rs + y;
             if (hasL) {
                 const double sl = s - lo;
-                if (ds < 0.0) a_max = fmin(a_max, -tau * sl / ds);
+                if (ds < 0.0) { a_max = fmin(a_max, -tau * sl / ds); OBCA_LPI_STEP_GUARD(0, -tau * sl / ds); }
                 const double dz = (mu - zL * ds) / sl - zL;
-                if (dz < 0.0) a_z = fmin(a_z, -tau * zL / dz);
+                if (dz < 0.0) { a_z = fmin(a_z, -tau * zL / dz); OBCA_LPI_STEP_GUARD(4, -tau * zL / dz); }
             }
             if (hasU) {
                 const double su = up - s;
-                if (ds > 0.0) a_max = fmin(a_max, tau * su / ds);
+                if (ds > 0.0) { a_max = fmin(a_max, tau * su / ds); OBCA_LPI_STEP_GUARD(1, tau * su / ds); }
                 const double dz = (mu + zU * ds) / su - zU;
-                if (dz < 0.0) a_z = fmin(a_z, -tau * zU / dz);
+                if (dz < 0.0) { a_z = fmin(a_z, -tau * zU / dz); OBCA_LPI_STEP_GUARD(5, -tau * zU / dz); }
             }
-            if (dp < 0.0) a_max = fmin(a_max, -tau * p / dp);
-            if (dn < 0.0) a_max = fmin(a_max, -tau * n / dn);
+            if (dp < 0.0) { a_max = fmin(a_max, -tau * p / dp); OBCA_LPI_STEP_GUARD(2, -tau * p / dp); }
+            if (dn < 0.0) { a_max = fmin(a_max, -tau * n / dn); OBCA_LPI_STEP_GUARD(3, -tau * n / dn); }
             const double dzp = (mu - zp * dp) / p - zp, dzn = (mu - zn * dn) / n - zn;
-            if (dzp < 0.0) a_z = fmin(a_z, -tau * zp / dzp);
-            if (dzn < 0.0) a_z = fmin(a_z, -tau * zn / dzn);
+            if (dzp < 0.0) { a_z = fmin(a_z, -tau * zp / dzp); OBCA_LPI_STEP_GUARD(6, -tau * zp / dzp); }
+            if (dzn < 0.0) { a_z = fmin(a_z, -tau * zn / dzn); OBCA_LPI_STEP_GUARD(7, -tau * zn / dzn); }
             phi += w * row_barrier_lpi(lo, up, eq, s, p, n, mu, rho);
             dphi += w * (gs * ds + (rho - mu / p) * dp + (rho - mu / n) * dn);
         }
         for (int t = 0; t < L.n; ++t) dphi += S.gf[t] * S.dx[t];
+        OBCA_LPI_STEP_LENGTHS(a_max, a_z);
         double alpha_min;
         if (dphi < 0.0) {
             double c = fmin(OBCA_GAMMA_THETA, OBCA_GAMMA_PHI * th / (-dphi));
