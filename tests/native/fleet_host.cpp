@@ -1,7 +1,6 @@
 // CPU exercise of the fleet closed loop (csrc/obca_fleet_core.h) -- tests only.  The serial definition of obca_fleet_step,
 // run for one world after the other; the descriptor is the C ABI's, its pointers host memory.
 #include <cstddef>
-#include <cstring>
 #include "../../vehicle_motion_planning_with_obstacles_avoidance_using_mpc_amd/csrc/obca_fleet_core.h"
 
 // obca_fleet_step without device and stream: the same checks, the same return codes
@@ -12,14 +11,8 @@ extern "C" int fleet_step_host(const obca_fleet* d, int measure) {
     return 0;
 }
 
-// obca_fleet_init's words (the library's own is in csrc/obca_fleet.hip)
-extern "C" void fleet_init_host(obca_fleet* d) {
-    std::memset(d, 0, sizeof(*d));
-    d->struct_size = (unsigned)sizeof(*d);
-    d->clearance = -1e300;
-    d->far = 100.0;
-    d->ego[0] = 1.7; d->ego[1] = 0.75; d->ego[2] = 1.7; d->ego[3] = 0.75;
-}
+// obca_fleet_init behind its NULL check: the core's fleet::init, which the library calls too
+extern "C" void fleet_init_host(obca_fleet* d) { fleet::init(d); }
 
 // the pieces on their own
 extern "C" void fleet_car_rows_host(const double* pose, const double* ego, double margin, double* A, double* b) {

@@ -1,7 +1,6 @@
 // CPU exercise of the fleet tracks (csrc/obca_fleet_tracks_core.h) -- tests only.  The serial definition of
 // obca_fleet_tracks, run for one world after the other; the descriptor is the C ABI's, its pointers host memory.
 #include <cstddef>
-#include <cstring>
 #include "../../vehicle_motion_planning_with_obstacles_avoidance_using_mpc_amd/csrc/obca_fleet_tracks_core.h"
 
 // obca_fleet_tracks without device and stream: the same checks, the same return codes
@@ -12,13 +11,8 @@ extern "C" int fleet_tracks_host(const struct obca_fleet_tracks* d) {
     return 0;
 }
 
-// obca_fleet_tracks_init's words (the library's own is in csrc/obca_fleet_tracks.hip)
-extern "C" void fleet_tracks_init_host(struct obca_fleet_tracks* d) {
-    std::memset(d, 0, sizeof(*d));
-    d->struct_size = (unsigned)sizeof(*d);
-    d->far = 100.0;
-    d->ego[0] = 1.7; d->ego[1] = 0.75; d->ego[2] = 1.7; d->ego[3] = 0.75;
-}
+// obca_fleet_tracks_init behind its NULL check: the core's tracks::init, which the library calls too
+extern "C" void fleet_tracks_init_host(struct obca_fleet_tracks* d) { tracks::init(d); }
 
 // the header's layout, for the ctypes mirror: sizeof, then the offset of every member in declaration order
 extern "C" int fleet_tracks_layout_host(long long* out, int cap) {

@@ -1,7 +1,6 @@
 // CPU exercise of the closed loop over scene pools (csrc/obca_poolloop_core.h) -- tests only.  The serial definition of
 // obca_pool_loop_advance, run for one rollout after the other; the descriptor is the C ABI's, its pointers host memory.
 #include <cstddef>
-#include <cstring>
 #include "../../vehicle_motion_planning_with_obstacles_avoidance_using_mpc_amd/csrc/obca_poolloop_core.h"
 
 // obca_pool_loop_advance without device and stream: the same checks, the same return codes
@@ -12,14 +11,8 @@ extern "C" int pool_loop_advance_host(const obca_pool_loop* d, int solved) {
     return 0;
 }
 
-// obca_pool_loop_init's words (the library's own is in csrc/obca_poolloop.hip)
-extern "C" void pool_loop_init_host(obca_pool_loop* d) {
-    std::memset(d, 0, sizeof(*d));
-    d->struct_size = (unsigned)sizeof(*d);
-    d->clearance = -1e300;
-    d->goal_tol2 = 0.1;
-    d->ego[0] = 1.7; d->ego[1] = 0.75; d->ego[2] = 1.7; d->ego[3] = 0.75;
-}
+// obca_pool_loop_init behind its NULL check: the core's poolloop::init, which the library calls too
+extern "C" void pool_loop_init_host(obca_pool_loop* d) { poolloop::init(d); }
 
 // the header's layout, for the ctypes mirror: sizeof, then the offset of every member in declaration order
 extern "C" int pool_loop_layout_host(long long* out, int cap) {

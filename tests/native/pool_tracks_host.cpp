@@ -1,7 +1,6 @@
 // CPU exercise of the obstacles on timed tracks (csrc/obca_pool_tracks_core.h) -- tests only.  The serial definition of
 // obca_pool_tracks, run for one rollout after the other; the descriptor is the C ABI's, its pointers host memory.
 #include <cstddef>
-#include <cstring>
 #include "../../vehicle_motion_planning_with_obstacles_avoidance_using_mpc_amd/csrc/obca_pool_tracks_core.h"
 
 // obca_pool_tracks without device and stream: the same checks, the same return codes
@@ -12,14 +11,8 @@ extern "C" int pool_tracks_host(const struct obca_pool_tracks* d, int measure) {
     return 0;
 }
 
-// obca_pool_tracks_init's words (the library's own is in csrc/obca_pool_tracks.hip)
-extern "C" void pool_tracks_init_host(struct obca_pool_tracks* d) {
-    std::memset(d, 0, sizeof(*d));
-    d->struct_size = (unsigned)sizeof(*d);
-    d->clearance = -1e300;
-    d->far = 100.0;
-    d->ego[0] = 1.7; d->ego[1] = 0.75; d->ego[2] = 1.7; d->ego[3] = 0.75;
-}
+// obca_pool_tracks_init behind its NULL check: the core's ptracks::init, which the library calls too
+extern "C" void pool_tracks_init_host(struct obca_pool_tracks* d) { ptracks::init(d); }
 
 // the pose of a track at a time, on its own: x [len,3], t [len]
 extern "C" void pool_tracks_pose_host(const double* x, const double* t, int len, double when, double* p) {

@@ -15,7 +15,8 @@ import os
 import numpy as np
 import pytest
 
-from tests import native_build, test_fleet_core as core, test_scene_core as tsc
+from tests import native_build, test_fleet_core as core
+from tests.descriptor_case import DescriptorCase, check_struct_mirror
 from vehicle_motion_planning_with_obstacles_avoidance_using_mpc_amd import _lib
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -53,37 +54,14 @@ def shapes(G, V, N):
             "track_b": (G, V, N + 1, 4), "track_ok": (B, V)}
 
 
-class Case:
+class Case(DescriptorCase):
     """the buffers of one obca_fleet_tracks in host memory, every one between guard bands, and the scalars"""
+    SCALARS = ("margin", "far")
 
     def __init__(self, G, V, N=5, step=0, see=core.SEE_ALL, margin=0.0, far=100.0, ego=core.EGO, exact=False):
         self.dims = dict(G=G, V=V, N=N, step=step, see=see)
         self.margin, self.far, self.ego, self.exact = margin, far, tuple(ego), exact
-        self.whole, self.a = {}, {}
-        for name, shape in shapes(G, V, N).items():
-            dt, fill = (np.int32, FILL_I) if name in INT else (np.float64, FILL_X)
-            self.whole[name], self.a[name] = tsc.banded(shape, dt, fill)
-
-    def __getitem__(self, name):
-        return self.a[name]
-
-    def descriptor(self, null=(), **over):
-        d = _lib.ObcaFleetTracks()
-        for k, v in self.dims.items():
-            setattr(d, k, v)
-        d.margin, d.far = self.margin, self.far
-        d.ego = (ctypes.c_double * 4)(*self.ego)
-        for name, arr in self.a.items():
-            setattr(d, name, None if name in null else arr.ctypes.data)
-        for k, v in over.items():
-            setattr(d, k, v)
-        return d
-
-    def snapshot(self):
-        return {k: v.copy() for k, v in self.whole.items()}
-
-    def bands_clean(self):
-        return all(tsc.band_clean(w, FILL_I if k in INT else FILL_X) for k, w in self.whole.items())
+        super().__init__(_lib.ObcaFleetTracks, shapes(G, V, N), INT)
 
 
 def tracks_host(host, case, rc=0, null=(), **over):
@@ -295,16 +273,7 @@ def test_a_car_without_a_pose_is_a_spare_and_nothing_is_nan(host):
 
 
 def test_struct_mirror_matches_the_header(host):
-    out = (ctypes.c_longlong * 64)()
-    n = host.fleet_tracks_layout_host(out, 64)
-    fields = [f[0] for f in _lib.ObcaFleetTracks._fields_]
-    assert n == 1 + len(fields)
-    assert out[0] == ctypes.sizeof(_lib.ObcaFleetTracks)
-    assert [out[1 + i] for i in range(len(fields))] == [getattr(_lib.ObcaFleetTracks, f).offset for f in fields]
-    raw = _lib.ObcaFleetTracks()
-    ctypes.memset(ctypes.byref(raw), 0xff, ctypes.sizeof(raw))
-    host.fleet_tracks_init_host(ctypes.byref(raw))
-    assert bytes(raw) == bytes(_lib.ObcaFleetTracks())
+    check_struct_mirror(host.fleet_tracks_layout_host, host.fleet_tracks_init_host, _lib.ObcaFleetTracks)
 
 
 REFUSED = [dict(G=0), dict(V=0), dict(V=17), dict(N=0), dict(N=128), dict(step=-1), dict(see=-1), dict(see=2), dict(margin=-0.5),

@@ -9,19 +9,16 @@ against the host libm's) elsewhere; the pair distance is audit::plan_distance as
 at TOL = 1e-9 m, the bound tests/test_gpu_pool_loop.py uses for its rotated-rectangle measurement.  Which history words are
 written, the flags and the masked windows are exact everywhere: the worlds keep every distance 1e-3 m and more from the
 threshold."""
-import ctypes
-
 import numpy as np
 import pytest
 import torch
 
 from tests import test_fleet_core as core
+from tests.descriptor_case import TOL, _np, check_struct_mirror, device_descriptor_call
 from vehicle_motion_planning_with_obstacles_avoidance_using_mpc_amd import _lib
 
 pytestmark = pytest.mark.gpu
 
-TOL = 1e-9                        # tests/test_gpu_pool_loop.py: TOL
-PAD = 32                          # sentinel words on either side of every buffer
 RUN, GOAL, CAP, FAILED, COLLISION = core.RUN, core.GOAL, core.CAP, core.FAILED, core.COLLISION
 
 
@@ -30,36 +27,11 @@ def host():
     return core.load_host()
 
 
-def _np(t):
-    return t.cpu().numpy()
-
-
 # ------------------------------------------------------------------------------------------------ 1. kernel against host core
 def device_step(case, measure, rc=0, null=(), device=None, **over):
-    """obca_fleet_step itself on the buffers of ``case`` uploaded between sentinels: returns name -> numpy of every buffer
-    after the call (the sentinels are checked here; a refused call must leave every word as uploaded)"""
-    bufs, d = {}, case.descriptor(null=null, **over)
-    for name, arr in case.a.items():
-        is_int = name in core.INT
-        buf = torch.full((arr.size + 2 * PAD,), core.FILL_I if is_int else core.FILL_X, dtype=torch.int32 if is_int else torch.float64,
-                         device="cuda")
-        buf[PAD:PAD + arr.size] = torch.as_tensor(np.ascontiguousarray(arr).reshape(-1), device="cuda")
-        bufs[name] = buf
-        if getattr(d, name) is not None:
-            setattr(d, name, buf.data_ptr() + PAD * buf.element_size())
-    before = {k: v.clone() for k, v in bufs.items()}
-    got = _lib.load().obca_fleet_step(ctypes.byref(d), measure, torch.cuda.current_device() if device is None else device,
-                                      _lib.stream_ptr(torch.device("cuda")))
-    assert got == rc
-    torch.cuda.synchronize()
-    out = {}
-    for name, buf in bufs.items():
-        fill = core.FILL_I if name in core.INT else core.FILL_X
-        assert (buf[:PAD] == fill).all() and (buf[-PAD:] == fill).all(), name
-        if rc != 0 or name in core.READ:
-            assert torch.equal(buf.view(torch.int32), before[name].view(torch.int32)), name
-        out[name] = _np(buf[PAD:PAD + case.a[name].size]).reshape(case.a[name].shape)
-    return out
+    """obca_fleet_step itself on the buffers of ``case`` uploaded between sentinels (``device_descriptor_call``)"""
+    return device_descriptor_call(case, _lib.load().obca_fleet_step, (measure,), core.READ, core.INT, rc=rc, null=null, device=device,
+                                  **over)
 
 
 def both(host, case, measure, label=""):
@@ -137,10 +109,7 @@ def test_refused_calls_launch_nothing(host):
     device_step(c, 2, rc=core.E_INVAL)
     device_step(c, 1, rc=core.E_INVAL, device=-1)
     assert _lib.load().obca_fleet_step(None, 0, 0, None) == core.E_INVAL
-    raw = _lib.ObcaFleet()
-    ctypes.memset(ctypes.byref(raw), 0xff, ctypes.sizeof(raw))
-    _lib.load().obca_fleet_init(ctypes.byref(raw))
-    assert bytes(raw) == bytes(_lib.ObcaFleet())
+    check_struct_mirror(None, _lib.load().obca_fleet_init, _lib.ObcaFleet)
     assert b"0.18" in _lib.load().obca_version()
 
 

@@ -20,6 +20,7 @@ import torch
 from tests import native_build
 from tests import test_pool_loop_core as core
 from tests import test_scene_core as scene_core
+from tests.descriptor_case import TOL, _np, check_struct_mirror, device_descriptor_call
 from vehicle_motion_planning_with_obstacles_avoidance_using_mpc_amd import _lib, scenarios, scene
 from vehicle_motion_planning_with_obstacles_avoidance_using_mpc_amd.model_obstacle import obstacleModel, rectangle_vertices
 from vehicle_motion_planning_with_obstacles_avoidance_using_mpc_amd.openloop import route_search
@@ -28,8 +29,6 @@ from vehicle_motion_planning_with_obstacles_avoidance_using_mpc_amd.solver impor
 
 pytestmark = pytest.mark.gpu
 
-TOL = 1e-9                        # tests/test_gpu_scene.py: TOL
-PAD = 32                          # sentinel words on either side of every buffer
 N, S, TS = 5, 12, 0.1
 RUN, GOAL, CAP, FAILED, COLLISION = core.RUN, core.GOAL, core.CAP, core.FAILED, core.COLLISION
 HISTORY = ("x_closed", "u_closed", "T_closed", "status", "iters", "clear", "sel")
@@ -45,39 +44,14 @@ def scene_host():
     return scene_core.load_host()
 
 
-def _np(t):
-    return t.cpu().numpy()
-
-
 def same(a, b):
     return core.same_words(_np(a) if isinstance(a, torch.Tensor) else a, _np(b) if isinstance(b, torch.Tensor) else b)
 
 
 # ------------------------------------------------------------------------------------------------ 1. kernel against host core
 def device_advance(case, solved, rc=0, null=(), **over):
-    """obca_pool_loop_advance itself on the buffers of ``case`` uploaded between sentinels: returns name -> numpy of every
-    buffer after the call (the sentinels are checked here; a refused call must leave every word as uploaded)"""
-    bufs, d = {}, case.descriptor(null=null, **over)
-    for name, arr in case.a.items():
-        is_int = name in core.INT
-        buf = torch.full((arr.size + 2 * PAD,), core.FILL_I if is_int else core.FILL_X, dtype=torch.int32 if is_int else torch.float64,
-                         device="cuda")
-        buf[PAD:PAD + arr.size] = torch.as_tensor(np.ascontiguousarray(arr).reshape(-1), device="cuda")
-        bufs[name] = buf
-        if getattr(d, name) is not None:
-            setattr(d, name, buf.data_ptr() + PAD * buf.element_size())
-    before = {k: v.clone() for k, v in bufs.items()}
-    got = _lib.load().obca_pool_loop_advance(ctypes.byref(d), solved, torch.cuda.current_device(), _lib.stream_ptr(torch.device("cuda")))
-    assert got == rc
-    torch.cuda.synchronize()
-    out = {}
-    for name, buf in bufs.items():
-        fill = core.FILL_I if name in core.INT else core.FILL_X
-        assert (buf[:PAD] == fill).all() and (buf[-PAD:] == fill).all(), name
-        if rc != 0:
-            assert torch.equal(buf.view(torch.int32), before[name].view(torch.int32)), name
-        out[name] = _np(buf[PAD:PAD + case.a[name].size]).reshape(case.a[name].shape)
-    return out
+    """obca_pool_loop_advance itself on the buffers of ``case`` uploaded between sentinels (``device_descriptor_call``)"""
+    return device_descriptor_call(case, _lib.load().obca_pool_loop_advance, (solved,), (), core.INT, rc=rc, null=null, **over)
 
 
 def both(host, case, solved, clear_tol=None):
@@ -241,10 +215,7 @@ def test_refused_calls_launch_nothing(host):
     assert _lib.load().obca_pool_loop_advance(None, 0, 0, None) == core.E_INVAL
     d = c.descriptor()
     assert _lib.load().obca_pool_loop_advance(ctypes.byref(d), 0, -1, None) == core.E_INVAL
-    raw = _lib.ObcaPoolLoop()
-    ctypes.memset(ctypes.byref(raw), 0xff, ctypes.sizeof(raw))
-    _lib.load().obca_pool_loop_init(ctypes.byref(raw))
-    assert bytes(raw) == bytes(_lib.ObcaPoolLoop())
+    check_struct_mirror(None, _lib.load().obca_pool_loop_init, _lib.ObcaPoolLoop)
 
 
 # ------------------------------------------------------------------------------------------------ worlds for the loop

@@ -8,8 +8,6 @@ its own on host and device); rows word for word at heading 0 and within tests/te
 (the device's sin / cos against the host libm's); distances within its DIST_TOL = 1e-12 m (the device contracts the
 measurement's products, coordinates stay below 100 m).  The loop: every solve within TOL = 1e-9 of the host yardstick,
 re-seeded from the device's state before each step (tests/test_gpu_fleet_plan.py's tolerance for the same comparison)."""
-import ctypes
-
 import numpy as np
 import pytest
 import torch
@@ -19,16 +17,14 @@ from tests import test_fleet_loop_host as fl
 from tests import test_gpu_fleet as tgf
 from tests import test_pool_tracks_core as ptc
 from tests import test_track_loop_host as tlh
+from tests.descriptor_case import TOL, _np, check_struct_mirror, device_descriptor_call
 from vehicle_motion_planning_with_obstacles_avoidance_using_mpc_amd import _lib, scene
 from vehicle_motion_planning_with_obstacles_avoidance_using_mpc_amd.solver import BatchSolver
 
 pytestmark = pytest.mark.gpu
 
-TOL = tgf.TOL
-PAD = tgf.PAD
 RUN, GOAL, CAP, FAILED, COLLISION = core.RUN, core.GOAL, core.CAP, core.FAILED, core.COLLISION
 N, S, TS, N_SEL, KS = fl.N, fl.S, fl.TS, fl.N_SEL, fl.KS
-_np = tgf._np
 
 
 @pytest.fixture(scope="module")
@@ -38,34 +34,9 @@ def host():
 
 # ------------------------------------------------------------------------------------------------ 1. kernel against host core
 def device_call(case, measure, rc=0, null=(), device=None, stream=None, **over):
-    """obca_pool_tracks itself on the buffers of ``case`` uploaded between sentinels: name -> numpy of every buffer after the
-    call (the sentinels are checked here; a refused call must leave every word as uploaded)"""
-    bufs, d = {}, case.descriptor(null=null, **over)
-    for name, arr in case.a.items():
-        is_int = name in ptc.INT
-        buf = torch.full((arr.size + 2 * PAD,), ptc.FILL_I if is_int else ptc.FILL_X, dtype=torch.int32 if is_int else torch.float64,
-                         device="cuda")
-        buf[PAD:PAD + arr.size] = torch.as_tensor(np.ascontiguousarray(arr).reshape(-1), device="cuda")
-        bufs[name] = buf
-        if getattr(d, name) is not None:
-            setattr(d, name, buf.data_ptr() + PAD * buf.element_size())
-    before = {k: v.clone() for k, v in bufs.items()}
-    torch.cuda.synchronize()
-    if stream is None:
-        got = _lib.load().obca_pool_tracks(ctypes.byref(d), measure, torch.cuda.current_device() if device is None else device,
-                                           _lib.stream_ptr(torch.device("cuda")))
-    else:
-        got = _lib.load().obca_pool_tracks(ctypes.byref(d), measure, torch.cuda.current_device(), ctypes.c_void_p(stream.cuda_stream))
-    assert got == rc
-    torch.cuda.synchronize()
-    out = {}
-    for name, buf in bufs.items():
-        fill = ptc.FILL_I if name in ptc.INT else ptc.FILL_X
-        assert (buf[:PAD] == fill).all() and (buf[-PAD:] == fill).all(), name
-        if rc != 0 or name in ptc.READ:
-            assert torch.equal(buf.view(torch.int32), before[name].view(torch.int32)), name
-        out[name] = _np(buf[PAD:PAD + case.a[name].size]).reshape(case.a[name].shape)
-    return out
+    """obca_pool_tracks itself on the buffers of ``case`` uploaded between sentinels (``device_descriptor_call``)"""
+    return device_descriptor_call(case, _lib.load().obca_pool_tracks, (measure,), ptc.READ, ptc.INT, rc=rc, null=null, device=device,
+                                  stream=stream, **over)
 
 
 def both(host, case, measure, label="", **kw):
@@ -163,10 +134,7 @@ def test_refused_calls_launch_nothing():
             device_call(c, 1, rc=ptc.E_INVAL, null=(name,))
     device_call(c, 1, rc=ptc.E_INVAL, device=-1)
     assert _lib.load().obca_pool_tracks(None, 0, 0, None) == ptc.E_INVAL
-    raw = _lib.ObcaPoolTracks()
-    ctypes.memset(ctypes.byref(raw), 0xff, ctypes.sizeof(raw))
-    _lib.load().obca_pool_tracks_init(ctypes.byref(raw))
-    assert bytes(raw) == bytes(_lib.ObcaPoolTracks())
+    check_struct_mirror(None, _lib.load().obca_pool_tracks_init, _lib.ObcaPoolTracks)
 
 
 def test_a_side_stream_and_a_null_t0_give_the_same_words():

@@ -55,21 +55,51 @@ class ObcaRolloutDims(ctypes.Structure):
                 ("max_steps", ctypes.c_int32), ("device", ctypes.c_int32), ("N_fix", ctypes.c_int32)]
 
 
-class ObcaPoolLoop(ctypes.Structure):
-    """obca_pool_loop (include/obca_mpc.h), the descriptor of obca_pool_loop_advance.  A new instance is what
-    obca_pool_loop_init leaves: all zero, struct_size set, clearance -1e300 (never stops), goal_tol2 0.1, the default ego."""
-    _fields_ = [("struct_size", ctypes.c_uint32), ("reserved_", ctypes.c_uint32)] + \
-               [(n, ctypes.c_int32) for n in ("B", "K", "E", "N", "n_sel", "path_max", "max_steps", "variant", "n_sub", "reserved2_")] + \
-               [("clearance", ctypes.c_double), ("goal_tol2", ctypes.c_double), ("ego", ctypes.c_double * 4)] + \
-               [(n, ctypes.c_void_p) for n in ("pool_A", "pool_v", "goal", "path", "path_len", "status", "iters", "ts_opt", "xopt", "uopt",
-                                               "sel", "x0", "u0", "pool_b", "k", "flags", "x_closed", "u_closed", "T_closed",
-                                               "status_hist", "iters_hist", "clear_hist", "sel_hist", "xref_out", "variant_out")]
+# what every obca_*_init writes besides zeros and struct_size (csrc/obca_loop_core.h); a descriptor has those it names
+DESCRIPTOR_DEFAULTS = {"clearance": -1e300, "far": 100.0, "goal_tol2": 0.1, "ego": (1.7, 0.75, 1.7, 0.75)}
+
+
+class Descriptor(ctypes.Structure):
+    """The base of the loop-step descriptors of include/obca_mpc.h.  A subclass states its members in header order through
+    ``members`` and names its defaults; a new instance is what its obca_*_init leaves: all zero, struct_size set, the named
+    words of DESCRIPTOR_DEFAULTS."""
+    DEFAULTS = ()
+
+    @staticmethod
+    def members(ints, doubles, pointers):
+        """_fields_ of a descriptor: struct_size, reserved_, the int32 members, the doubles (``ego`` is double[4]), the pointers"""
+        return [("struct_size", ctypes.c_uint32), ("reserved_", ctypes.c_uint32)] + [(n, ctypes.c_int32) for n in ints] + \
+               [(n, ctypes.c_double * 4 if n == "ego" else ctypes.c_double) for n in doubles] + [(n, ctypes.c_void_p) for n in pointers]
 
     def __init__(self, *a, **kw):
         super().__init__(*a, **kw)
-        self.struct_size = ctypes.sizeof(ObcaPoolLoop)
-        self.clearance, self.goal_tol2 = -1e300, 0.1
-        self.ego = (ctypes.c_double * 4)(1.7, 0.75, 1.7, 0.75)
+        self.struct_size = ctypes.sizeof(type(self))
+        self.set(**{n: DESCRIPTOR_DEFAULTS[n] for n in self.DEFAULTS})
+
+    def set(self, **members):
+        """scalar members from an int or float, ``ego`` from a 4-sequence, pointer members from None, a torch tensor, a numpy
+        array or an integer address"""
+        kinds = dict(self._fields_)
+        for name, v in members.items():
+            if name not in kinds:
+                raise AttributeError("%s has no member %r" % (type(self).__name__, name))
+            if kinds[name] is ctypes.c_void_p and v is not None:
+                v = v.data_ptr() if hasattr(v, "data_ptr") else (v.ctypes.data if hasattr(v, "ctypes") else int(v))
+            elif name == "ego":
+                v = (ctypes.c_double * 4)(*[float(q) for q in v])
+            setattr(self, name, v)
+        return self
+
+
+class ObcaPoolLoop(Descriptor):
+    """obca_pool_loop (include/obca_mpc.h), the descriptor of obca_pool_loop_advance.  A new instance is what
+    obca_pool_loop_init leaves: all zero, struct_size set, clearance -1e300 (never stops), goal_tol2 0.1, the default ego."""
+    _fields_ = Descriptor.members(("B", "K", "E", "N", "n_sel", "path_max", "max_steps", "variant", "n_sub", "reserved2_"),
+                                  ("clearance", "goal_tol2", "ego"),
+                                  ("pool_A", "pool_v", "goal", "path", "path_len", "status", "iters", "ts_opt", "xopt", "uopt", "sel", "x0",
+                                   "u0", "pool_b", "k", "flags", "x_closed", "u_closed", "T_closed", "status_hist", "iters_hist",
+                                   "clear_hist", "sel_hist", "xref_out", "variant_out"))
+    DEFAULTS = ("clearance", "goal_tol2", "ego")
 
 
 # obca_fleet.see / obca_fleet.predict (include/obca_mpc.h)
@@ -79,35 +109,22 @@ FLEET_PREDICT_VELOCITY, FLEET_PREDICT_STATIC = 0, 1
 FLEET_PREDICT = {"velocity": FLEET_PREDICT_VELOCITY, "static": FLEET_PREDICT_STATIC}
 
 
-class ObcaFleet(ctypes.Structure):
+class ObcaFleet(Descriptor):
     """obca_fleet (include/obca_mpc.h), the descriptor of obca_fleet_step.  A new instance is what obca_fleet_init leaves: all
     zero (see ALL, predict VELOCITY, margin 0), struct_size set, clearance -1e300 (never stops), far 100, the default ego."""
-    _fields_ = [("struct_size", ctypes.c_uint32), ("reserved_", ctypes.c_uint32)] + \
-               [(n, ctypes.c_int32) for n in ("G", "V", "Ks", "N", "max_steps", "step", "n_sub", "see", "predict", "reserved2_")] + \
-               [("clearance", ctypes.c_double), ("margin", ctypes.c_double), ("far", ctypes.c_double), ("ego", ctypes.c_double * 4)] + \
-               [(n, ctypes.c_void_p) for n in ("x_prev", "x0", "u0", "k", "flags", "pool_A", "pool_b", "pool_v", "agent_clear_hist",
-                                               "xref_out", "variant_out")]
-
-    def __init__(self, *a, **kw):
-        super().__init__(*a, **kw)
-        self.struct_size = ctypes.sizeof(ObcaFleet)
-        self.clearance, self.far = -1e300, 100.0
-        self.ego = (ctypes.c_double * 4)(1.7, 0.75, 1.7, 0.75)
+    _fields_ = Descriptor.members(("G", "V", "Ks", "N", "max_steps", "step", "n_sub", "see", "predict", "reserved2_"),
+                                  ("clearance", "margin", "far", "ego"),
+                                  ("x_prev", "x0", "u0", "k", "flags", "pool_A", "pool_b", "pool_v", "agent_clear_hist", "xref_out",
+                                   "variant_out"))
+    DEFAULTS = ("clearance", "far", "ego")
 
 
-class ObcaFleetTracks(ctypes.Structure):
+class ObcaFleetTracks(Descriptor):
     """obca_fleet_tracks (include/obca_mpc.h), the descriptor of the call of that name.  A new instance is what
     obca_fleet_tracks_init leaves: all zero (see ALL, margin 0), struct_size set, far 100, the default ego."""
-    _fields_ = [("struct_size", ctypes.c_uint32), ("reserved_", ctypes.c_uint32)] + \
-               [(n, ctypes.c_int32) for n in ("G", "V", "N", "step", "see", "reserved2_")] + \
-               [("margin", ctypes.c_double), ("far", ctypes.c_double), ("ego", ctypes.c_double * 4)] + \
-               [(n, ctypes.c_void_p) for n in ("x0", "flags", "k", "xopt", "status", "track_A", "track_b", "track_ok")]
-
-    def __init__(self, *a, **kw):
-        super().__init__(*a, **kw)
-        self.struct_size = ctypes.sizeof(ObcaFleetTracks)
-        self.far = 100.0
-        self.ego = (ctypes.c_double * 4)(1.7, 0.75, 1.7, 0.75)
+    _fields_ = Descriptor.members(("G", "V", "N", "step", "see", "reserved2_"), ("margin", "far", "ego"),
+                                  ("x0", "flags", "k", "xopt", "status", "track_A", "track_b", "track_ok"))
+    DEFAULTS = ("far", "ego")
 
 
 # obca_pool_tracks.predict (include/obca_mpc.h)
@@ -115,22 +132,16 @@ TRACK_PREDICT_TRACK, TRACK_PREDICT_VELOCITY, TRACK_PREDICT_STATIC = 0, 1, 2
 TRACK_PREDICT = {"track": TRACK_PREDICT_TRACK, "velocity": TRACK_PREDICT_VELOCITY, "static": TRACK_PREDICT_STATIC}
 
 
-class ObcaPoolTracks(ctypes.Structure):
+class ObcaPoolTracks(Descriptor):
     """obca_pool_tracks (include/obca_mpc.h), the descriptor of the call of that name.  A new instance is what
     obca_pool_tracks_init leaves: all zero (predict TRACK, margin 0, t0 NULL), struct_size set, clearance -1e300 (never
     stops), far 100, the default ego."""
-    _fields_ = [("struct_size", ctypes.c_uint32), ("reserved_", ctypes.c_uint32)] + \
-               [(n, ctypes.c_int32) for n in ("B", "K", "Kt", "N", "L", "group", "max_steps", "step", "n_sub", "predict")] + \
-               [("clearance", ctypes.c_double), ("margin", ctypes.c_double), ("far", ctypes.c_double), ("ego", ctypes.c_double * 4)] + \
-               [(n, ctypes.c_void_p) for n in ("track_x", "track_t", "track_len", "track_size", "t0", "Ts", "x_prev", "x0", "k", "flags",
-                                               "pool_A", "pool_b", "pool_v", "stage_A", "stage_b", "stage_ok", "track_state",
-                                               "track_clear_hist", "xref_out", "variant_out")]
-
-    def __init__(self, *a, **kw):
-        super().__init__(*a, **kw)
-        self.struct_size = ctypes.sizeof(ObcaPoolTracks)
-        self.clearance, self.far = -1e300, 100.0
-        self.ego = (ctypes.c_double * 4)(1.7, 0.75, 1.7, 0.75)
+    _fields_ = Descriptor.members(("B", "K", "Kt", "N", "L", "group", "max_steps", "step", "n_sub", "predict"),
+                                  ("clearance", "margin", "far", "ego"),
+                                  ("track_x", "track_t", "track_len", "track_size", "t0", "Ts", "x_prev", "x0", "k", "flags", "pool_A",
+                                   "pool_b", "pool_v", "stage_A", "stage_b", "stage_ok", "track_state", "track_clear_hist", "xref_out",
+                                   "variant_out"))
+    DEFAULTS = ("clearance", "far", "ego")
 
 
 EXPORTS = ("obca_create", "obca_destroy", "obca_solve_batch", "obca_lds_bytes", "obca_strerror", "obca_version", "obca_params_init",
@@ -331,3 +342,26 @@ def device_index(dev):
 def check(code):
     if code != 0:
         raise RuntimeError("libobca_mpc: %s (code %d)" % (load().obca_strerror(code).decode(), code))
+
+
+def launch(fn, *args, dev):
+    """the call ``fn(*args, device, stream)`` on torch device ``dev`` and its current stream; raises on an error code"""
+    check(fn(*args, device_index(dev), stream_ptr(dev)))
+
+
+def keep_alive(anchor, tensors, dev):
+    """a launch is asynchronous: the tensors it reads must outlive it.  They are tied to ``anchor`` (the result: a second call
+    before the stream drains must not free the first call's inputs) and recorded on the current stream of ``dev`` (the caching
+    allocator keeps a freed block out of other streams' hands until this stream has passed the free point).  None is skipped."""
+    import torch
+    anchor._obca_keep = tuple(tensors)
+    s = torch.cuda.current_stream(dev)
+    for t in anchor._obca_keep:
+        if t is not None:
+            t.record_stream(s)
+
+
+def require_gpu(who):
+    import torch
+    if not torch.cuda.is_available():
+        raise RuntimeError("%s needs a ROCm GPU; there is no CPU fallback on the product path" % who)

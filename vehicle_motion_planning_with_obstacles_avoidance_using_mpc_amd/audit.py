@@ -24,8 +24,8 @@ def _device_tensor(a, dtype, device):
 def _plan_batch(x, A, b, m, ego, variant, device, status=None, tighten=False):
     """The batch the three plan calls share, on the device: resolves the device (``device``, else x's if x is a device
     tensor, else the current one), moves and reshapes x, A, b, variant (None: NULL unless ``tighten``) and, for
-    ``tighten``, status.  Returns (dev, B, N1, m, keep, head, tail): head = the leading arguments of the C call up to b,
-    tail = its device and stream, keep = the tensors head points into, to be held until the call is made."""
+    ``tighten``, status.  Returns (dev, B, N1, m, keep, head): head = the leading arguments of the C call up to b, keep = the
+    tensors head points into, to be held until the call is made."""
     import torch
     dev = torch.device(device) if device is not None else (x.device if isinstance(x, torch.Tensor) and x.is_cuda else
                                                            torch.device("cuda", torch.cuda.current_device()))
@@ -42,7 +42,7 @@ def _plan_batch(x, A, b, m, ego, variant, device, status=None, tighten=False):
     m_c = (ctypes.c_int32 * max(len(m), 1))(*m)
     keep = ints + [x, A, b]
     head = [ego_c, len(m), m_c, N1 - 1, B] + [_lib.ptr(t) for t in keep]
-    return dev, B, N1, m, keep, head, [_lib.device_index(dev), _lib.stream_ptr(dev)]
+    return dev, B, N1, m, keep, head
 
 
 def plan_clearance(x, A, b, m, ego=DEFAULT_EGO, variant=None, per_stage=False, device=None):
@@ -50,15 +50,15 @@ def plan_clearance(x, A, b, m, ego=DEFAULT_EGO, variant=None, per_stage=False, d
     (4: every stage against stage 0's rows, as obca_mpc4 reads them).  Returns a dict of device tensors on the current
     stream: min_clear [B], arg_stage [B], arg_obst [B] and, with per_stage, stage_obst [B,N+1,n_obs]."""
     import torch
-    dev, B, N1, m, keep, head, tail = _plan_batch(x, A, b, m, ego, variant, device)
+    dev, B, N1, m, keep, head = _plan_batch(x, A, b, m, ego, variant, device)
     out = {"min_clear": torch.empty(B, dtype=torch.float64, device=dev),
            "arg_stage": torch.empty(B, dtype=torch.int32, device=dev),
            "arg_obst": torch.empty(B, dtype=torch.int32, device=dev)}
     if per_stage:
         out["stage_obst"] = torch.empty(B, N1, len(m), dtype=torch.float64, device=dev)
     p = _lib.ptr
-    _lib.check(_lib.load().obca_plan_clearance(*head, p(out["min_clear"]), p(out["arg_stage"]), p(out["arg_obst"]),
-                                               p(out.get("stage_obst")), *tail))
+    _lib.launch(_lib.load().obca_plan_clearance, *head, p(out["min_clear"]), p(out["arg_stage"]), p(out["arg_obst"]),
+                p(out.get("stage_obst")), dev=dev)
     return out
 
 
@@ -68,7 +68,7 @@ def plan_sweep(x, A, b, m, n_sub=16, ego=DEFAULT_EGO, variant=None, per_interval
     min_clear, lower_bound (certified for translating obstacles, else NaN), arg_interval, arg_obst, first_collision [B]
     and, with per_interval, interval_min [B,N]."""
     import torch
-    dev, B, N1, m, keep, head, tail = _plan_batch(x, A, b, m, ego, variant, device)
+    dev, B, N1, m, keep, head = _plan_batch(x, A, b, m, ego, variant, device)
     out = {"min_clear": torch.empty(B, dtype=torch.float64, device=dev),
            "lower_bound": torch.empty(B, dtype=torch.float64, device=dev),
            "arg_interval": torch.empty(B, dtype=torch.int32, device=dev),
@@ -77,8 +77,8 @@ def plan_sweep(x, A, b, m, n_sub=16, ego=DEFAULT_EGO, variant=None, per_interval
     if per_interval:
         out["interval_min"] = torch.empty(B, max(N1 - 1, 0), dtype=torch.float64, device=dev)
     p = _lib.ptr
-    _lib.check(_lib.load().obca_plan_sweep(*head, int(n_sub), p(out["min_clear"]), p(out["lower_bound"]), p(out["arg_interval"]),
-                                           p(out["arg_obst"]), p(out["first_collision"]), p(out.get("interval_min")), *tail))
+    _lib.launch(_lib.load().obca_plan_sweep, *head, int(n_sub), p(out["min_clear"]), p(out["lower_bound"]), p(out["arg_interval"]),
+                p(out["arg_obst"]), p(out["first_collision"]), p(out.get("interval_min")), dev=dev)
     return out
 
 
@@ -92,7 +92,7 @@ def plan_tighten(x, A, b, m, variant, status, grow=None, b_out=None, n_sub=16, c
     b_out if given, which must not be b), variant_out [B] (variant where grow rose, else 0: the variant argument of the
     next solve) and min_clear [B] (NaN: not measured, or not finite)."""
     import torch
-    dev, B, N1, m, keep, head, tail = _plan_batch(x, A, b, m, ego, variant, device, status, tighten=True)
+    dev, B, N1, m, keep, head = _plan_batch(x, A, b, m, ego, variant, device, status, tighten=True)
     M = sum(m)
     if grow is None:
         grow = torch.zeros(B, N1, len(m), dtype=torch.float64, device=dev)
@@ -105,8 +105,8 @@ def plan_tighten(x, A, b, m, variant, status, grow=None, b_out=None, n_sub=16, c
     out = {"grow": grow, "b_out": b_out, "variant_out": torch.empty(B, dtype=torch.int32, device=dev),
            "min_clear": torch.empty(B, dtype=torch.float64, device=dev)}
     p = _lib.ptr
-    _lib.check(_lib.load().obca_plan_tighten(*head, int(n_sub), int(bool(certified)), float(target), float(gain), float(grow_max),
-                                             p(grow), p(b_out), p(out["variant_out"]), p(out["min_clear"]), *tail))
+    _lib.launch(_lib.load().obca_plan_tighten, *head, int(n_sub), int(bool(certified)), float(target), float(gain), float(grow_max),
+                p(grow), p(b_out), p(out["variant_out"]), p(out["min_clear"]), dev=dev)
     return out
 
 

@@ -17,7 +17,6 @@
 // only its lane 0 writes it, after the read: no word is read by one wavefront and written by another.
 #include <hip/hip_runtime.h>
 #include <math.h>
-#include <string.h>
 #include "obca_device.h"
 #include "obca_fleet_core.h"
 
@@ -46,11 +45,8 @@ __global__ void __launch_bounds__(MAX_BLOCK) fleet_kernel(obca_fleet D, int32_t 
         const int now = fleet::flag_after(D, flag, c);
         if (lane == 0 && c == c) D.agent_clear_hist[b * S + D.step] = c;
         if (now != flag) {                                           // wave-uniform
-            if (lane == 0) { D.flags[b] = now; D.variant_out[b] = 0; }
-            const double qx = fleet::finite_or_zero(D.x0[3 * b]), qy = fleet::finite_or_zero(D.x0[3 * b + 1]),
-                         qt = fleet::finite_or_zero(D.x0[3 * b + 2]);
-            double* xr = D.xref_out + b * 3 * N1;
-            for (int t = lane; t < N1; t += WAVE) { xr[t] = qx; xr[N1 + t] = qy; xr[2 * N1 + t] = qt; }
+            if (lane == 0) D.flags[b] = now;
+            loop::mask_rollout_wave(D.variant_out, D.xref_out, b, N1, D.x0[3 * b], D.x0[3 * b + 1], D.x0[3 * b + 2], lane);
         }
         flag = now;
     }
@@ -75,12 +71,7 @@ __global__ void __launch_bounds__(MAX_BLOCK) fleet_kernel(obca_fleet D, int32_t 
 }  // namespace
 
 extern "C" void obca_fleet_init(obca_fleet* d) {
-    if (!d) return;
-    memset(d, 0, sizeof(*d));
-    d->struct_size = (uint32_t)sizeof(*d);
-    d->clearance = -1e300;
-    d->far = 100.0;
-    d->ego[0] = 1.7; d->ego[1] = 0.75; d->ego[2] = 1.7; d->ego[3] = 0.75;
+    if (d) fleet::init(d);
 }
 
 extern "C" int obca_fleet_step(const obca_fleet* d, int32_t measure, int32_t device, void* hip_stream) {

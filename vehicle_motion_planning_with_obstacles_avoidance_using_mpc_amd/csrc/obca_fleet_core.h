@@ -30,6 +30,7 @@
 #include <stdint.h>
 #include "../../include/obca_mpc.h"
 #include "obca_audit_core.h"
+#include "obca_loop_core.h"
 #include "obca_gridpool_core.h"
 
 #if defined(__HIPCC__)
@@ -56,7 +57,9 @@ constexpr int E_INVAL = -22;               // OBCA_E_INVAL
 
 FL_FN bool finite_(double v) { return v - v == 0.0; }          // false for NaN and +-inf, no libm call
 FL_FN bool pose_finite(const double* p) { return finite_(p[0]) && finite_(p[1]) && finite_(p[2]); }
-FL_FN double finite_or_zero(double v) { return finite_(v) ? v : 0.0; }
+
+// obca_fleet_init's words
+inline void init(obca_fleet* d) { loop::init_common(d); d->clearance = loop::NEVER_STOP; d->far = loop::DEFAULT_FAR; }
 
 // the checks of obca_fleet_step, made before anything is read or written (the host build makes the same ones)
 FL_FN int args_check(const obca_fleet* d, int32_t measure) {
@@ -102,7 +105,7 @@ FL_FN void car_rows(double x, double y, double th, const double* ego, double mar
 // the speed other cars assume of a car: its last applied one while it runs, 0 once it has ended (it is parked where it
 // stands) or under a static prediction; never a word that is not finite
 FL_FN double agent_speed(int predict, int flag, double u_speed) {
-    return (predict == OBCA_FLEET_PREDICT_VELOCITY && flag == OBCA_RUN) ? finite_or_zero(u_speed) : 0.0;
+    return (predict == OBCA_FLEET_PREDICT_VELOCITY && flag == OBCA_RUN) ? loop::finite_or_zero(u_speed) : 0.0;
 }
 
 // is slot Ks + j of car a's pool a spare
@@ -180,9 +183,7 @@ inline void measure_world(const obca_fleet& d, int64_t g) {
         const int was = d.flags[b], now = flag_after(d, was, fold[a]);
         if (now == was) continue;
         d.flags[b] = now;
-        d.variant_out[b] = 0;
-        for (int q = 0; q < 3; ++q)
-            for (int t = 0; t < N1; ++t) d.xref_out[b * 3 * N1 + q * N1 + t] = finite_or_zero(d.x0[3 * b + q]);
+        loop::mask_rollout(d.variant_out, d.xref_out, d.x0, b, N1);
     }
 }
 

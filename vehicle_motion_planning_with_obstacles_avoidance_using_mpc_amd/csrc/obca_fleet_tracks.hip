@@ -12,7 +12,6 @@
 // of the launch writes, except through the LDS flags behind the barrier.
 #include <hip/hip_runtime.h>
 #include <math.h>
-#include <string.h>
 #include "obca_device.h"
 #include "obca_fleet_tracks_core.h"
 
@@ -57,11 +56,7 @@ __global__ void __launch_bounds__(BLOCK) tracks_kernel(struct obca_fleet_tracks 
 }  // namespace
 
 extern "C" void obca_fleet_tracks_init(struct obca_fleet_tracks* d) {
-    if (!d) return;
-    memset(d, 0, sizeof(*d));
-    d->struct_size = (uint32_t)sizeof(*d);
-    d->far = 100.0;
-    d->ego[0] = 1.7; d->ego[1] = 0.75; d->ego[2] = 1.7; d->ego[3] = 0.75;
+    if (d) tracks::init(d);
 }
 
 extern "C" int obca_fleet_tracks(const struct obca_fleet_tracks* d, int32_t device, void* hip_stream) {

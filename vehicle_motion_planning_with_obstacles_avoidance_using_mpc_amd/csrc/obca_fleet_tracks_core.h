@@ -21,6 +21,9 @@ namespace tracks {
 
 constexpr int E = fleet::E;
 
+// obca_fleet_tracks_init's words
+inline void init(struct obca_fleet_tracks* d) { loop::init_common(d); d->far = loop::DEFAULT_FAR; }
+
 // the checks of obca_fleet_tracks, made before anything is read or written (the host build makes the same ones)
 FL_FN int args_check(const struct obca_fleet_tracks* d) {
     if (!d || d->struct_size != (uint32_t)sizeof(struct obca_fleet_tracks)) return fleet::E_INVAL;

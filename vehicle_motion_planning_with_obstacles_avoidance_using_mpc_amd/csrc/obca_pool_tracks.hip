@@ -18,7 +18,6 @@
 // rollout's, and only its lane 0 writes it, after the read.
 #include <hip/hip_runtime.h>
 #include <math.h>
-#include <string.h>
 #include "obca_device.h"
 #include "obca_pool_tracks_core.h"
 
@@ -61,11 +60,8 @@ __global__ void __launch_bounds__(BLOCK) pool_tracks_kernel(struct obca_pool_tra
         const int was = D.flags[b], now = ptracks::flag_after(D, was, cur);
         if (lane == 0 && cur == cur) D.track_clear_hist[b * S + D.step] = cur;
         if (now != was) {                                            // wave-uniform
-            if (lane == 0) { D.flags[b] = now; D.variant_out[b] = 0; }
-            const double qx = fleet::finite_or_zero(D.x0[3 * b]), qy = fleet::finite_or_zero(D.x0[3 * b + 1]),
-                         qt = fleet::finite_or_zero(D.x0[3 * b + 2]);
-            double* xr = D.xref_out + b * 3 * N1;
-            for (int t = lane; t < N1; t += WAVE) { xr[t] = qx; xr[N1 + t] = qy; xr[2 * N1 + t] = qt; }
+            if (lane == 0) D.flags[b] = now;
+            loop::mask_rollout_wave(D.variant_out, D.xref_out, b, N1, D.x0[3 * b], D.x0[3 * b + 1], D.x0[3 * b + 2], lane);
         }
     }
 
@@ -104,12 +100,7 @@ __global__ void __launch_bounds__(BLOCK) pool_tracks_kernel(struct obca_pool_tra
 }  // namespace
 
 extern "C" void obca_pool_tracks_init(struct obca_pool_tracks* d) {
-    if (!d) return;
-    memset(d, 0, sizeof(*d));
-    d->struct_size = (uint32_t)sizeof(*d);
-    d->clearance = -1e300;
-    d->far = 100.0;
-    d->ego[0] = 1.7; d->ego[1] = 0.75; d->ego[2] = 1.7; d->ego[3] = 0.75;
+    if (d) ptracks::init(d);
 }
 
 extern "C" int obca_pool_tracks(const struct obca_pool_tracks* d, int32_t measure, int32_t device, void* hip_stream) {

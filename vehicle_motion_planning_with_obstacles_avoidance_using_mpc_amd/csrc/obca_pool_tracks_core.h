@@ -28,6 +28,9 @@ namespace ptracks {
 constexpr int E = fleet::E;
 constexpr int MAX_L = 4096;
 
+// obca_pool_tracks_init's words
+inline void init(struct obca_pool_tracks* d) { loop::init_common(d); d->clearance = loop::NEVER_STOP; d->far = loop::DEFAULT_FAR; }
+
 // the checks of obca_pool_tracks, made before anything is read or written (the host build makes the same ones)
 FL_FN int args_check(const struct obca_pool_tracks* d, int32_t measure) {
     if (!d || d->struct_size != (uint32_t)sizeof(struct obca_pool_tracks)) return fleet::E_INVAL;
@@ -157,8 +160,8 @@ FL_FN void chord_velocity(const struct obca_pool_tracks& d, int64_t b, bool usab
     v[0] = 0.0; v[1] = 0.0;
     if (!usable || d.predict == OBCA_TRACK_PREDICT_STATIC || !fleet::pose_finite(p0)) return;
     const double dx = p1[0] - p0[0], dy = p1[1] - p0[1];
-    v[0] = fleet::finite_or_zero(dx / d.Ts[b]);
-    v[1] = fleet::finite_or_zero(dy / d.Ts[b]);
+    v[0] = loop::finite_or_zero(dx / d.Ts[b]);
+    v[1] = loop::finite_or_zero(dy / d.Ts[b]);
 }
 
 FL_FN int ok_word(const struct obca_pool_tracks& d, bool usable) { return (usable && d.predict == OBCA_TRACK_PREDICT_TRACK) ? 1 : 0; }
@@ -209,9 +212,7 @@ inline void rollout(const struct obca_pool_tracks& d, int32_t measure, int64_t b
         const int was = d.flags[b], now = flag_after(d, was, fold);
         if (now != was) {
             d.flags[b] = now;
-            d.variant_out[b] = 0;
-            for (int q = 0; q < 3; ++q)
-                for (int t = 0; t < N1; ++t) d.xref_out[b * 3 * N1 + q * N1 + t] = fleet::finite_or_zero(d.x0[3 * b + q]);
+            loop::mask_rollout(d.variant_out, d.xref_out, d.x0, b, N1);
         }
     }
     for (int j = 0; j < Kt; ++j) {

@@ -15,7 +15,6 @@
 // stores is picked with selects from scalars: no local array is indexed with a lane number (that is a stack frame).
 #include <hip/hip_runtime.h>
 #include <math.h>
-#include <string.h>
 #include "obca_device.h"
 #include "obca_poolloop_core.h"
 
@@ -132,13 +131,11 @@ __global__ void __launch_bounds__(BLOCK) poolloop_kernel(obca_pool_loop D, int32
     }
 
     // ---- prepare
-    double* xr = D.xref_out + b * 3 * N1;
     if (flag != OBCA_RUN) {                                          // wave-uniform
-        if (lane == 0) D.variant_out[b] = 0;
-        const double qx = poolloop::finite_or_zero(px), qy = poolloop::finite_or_zero(py), qt = poolloop::finite_or_zero(pt);
-        for (int t = lane; t < N1; t += WAVE) { xr[t] = qx; xr[N1 + t] = qy; xr[2 * N1 + t] = qt; }
+        loop::mask_rollout_wave(D.variant_out, D.xref_out, b, N1, px, py, pt, lane);
         return;
     }
+    double* xr = D.xref_out + b * 3 * N1;
     if (lane == 0) D.variant_out[b] = D.variant;
     const double* path = D.path + b * 3 * P;
     const int len = poolloop::safe_len(D.path_len[b], P);
@@ -160,12 +157,7 @@ __global__ void __launch_bounds__(BLOCK) poolloop_kernel(obca_pool_loop D, int32
 }  // namespace
 
 extern "C" void obca_pool_loop_init(obca_pool_loop* d) {
-    if (!d) return;
-    memset(d, 0, sizeof(*d));
-    d->struct_size = (uint32_t)sizeof(*d);
-    d->clearance = -1e300;
-    d->goal_tol2 = 0.1;
-    d->ego[0] = 1.7; d->ego[1] = 0.75; d->ego[2] = 1.7; d->ego[3] = 0.75;
+    if (d) poolloop::init(d);
 }
 
 extern "C" int obca_pool_loop_advance(const obca_pool_loop* d, int32_t solved, int32_t device, void* hip_stream) {

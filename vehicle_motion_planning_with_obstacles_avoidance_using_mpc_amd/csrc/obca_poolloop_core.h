@@ -25,6 +25,7 @@
 #include <math.h>
 #include <stdint.h>
 #include "../../include/obca_mpc.h"
+#include "obca_loop_core.h"
 #include "obca_scene_core.h"
 
 #if defined(__HIPCC__)
@@ -43,6 +44,9 @@ namespace poolloop {
 
 constexpr int MAX_STEPS = 1024;
 constexpr double WINDOW_FAR = 100000.0;       // rollout::prepare's H4: no point at or beyond this squared distance is taken
+
+// obca_pool_loop_init's words
+inline void init(obca_pool_loop* d) { loop::init_common(d); d->clearance = loop::NEVER_STOP; d->goal_tol2 = loop::DEFAULT_GOAL_TOL2; }
 
 // the checks of obca_pool_loop_advance, made before anything is read or written (the host build makes the same ones)
 PL_FN int args_check(const obca_pool_loop* d, int32_t solved) {
@@ -127,8 +131,6 @@ PL_FN int safe_len(int len, int P) { return len < 1 ? 1 : (len > P ? P : len); }
 // may step kb be written into histories of S steps (true for every RUN rollout since its start)
 PL_FN bool step_in_range(int kb, int S) { return kb >= 0 && kb < S; }
 
-PL_FN double finite_or_zero(double v) { return scene::finite_(v) ? v : 0.0; }
-
 // ---- the serial definition: one call of obca_pool_loop_advance for rollout b
 inline void finish(const obca_pool_loop& d, int64_t b) {
     if (d.flags[b] != OBCA_RUN) return;
@@ -194,12 +196,7 @@ inline void prepare(const obca_pool_loop& d, int64_t b) {
     const int N1 = d.N + 1, P = d.path_max;
     const double* p = d.x0 + 3 * b;
     double* xr = d.xref_out + b * 3 * N1;
-    if (d.flags[b] != OBCA_RUN) {
-        d.variant_out[b] = 0;
-        for (int j = 0; j < 3; ++j)
-            for (int t = 0; t < N1; ++t) xr[j * N1 + t] = finite_or_zero(p[j]);
-        return;
-    }
+    if (d.flags[b] != OBCA_RUN) { loop::mask_rollout(d.variant_out, d.xref_out, d.x0, b, N1); return; }
     d.variant_out[b] = d.variant;
     const double* path = d.path + b * 3 * P;
     const int len = safe_len(d.path_len[b], P);

@@ -29,8 +29,7 @@ def refine(x, ts, ratio, status=None, variant_ok=6, device=None):
     ts <= 0), knot 0 at every point (zeros where it is not finite), ts / ratio (0 where not finite) and variant 0, which
     ``BatchSolver.solve`` skips.  On the current stream, no host synchronisation."""
     import torch
-    if not torch.cuda.is_available():
-        raise RuntimeError("refine needs a ROCm GPU; there is no CPU fallback on the product path")
+    _lib.require_gpu("refine")
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     lib = _lib.load()
     x = torch.as_tensor(x, dtype=torch.float64, device=dev).contiguous()
@@ -48,8 +47,8 @@ def refine(x, ts, ratio, status=None, variant_ok=6, device=None):
     ts_out = torch.empty(B, dtype=torch.float64, device=dev)
     variant_out = torch.empty(B, dtype=torch.int32, device=dev)
     ptr = _lib.ptr
-    _lib.check(lib.obca_plan_refine(B, N, ratio, ptr(x), ptr(ts), ptr(status), int(variant_ok), ptr(xref), ptr(ts_out),
-                                    ptr(variant_out), _lib.device_index(dev), _lib.stream_ptr(dev)))
+    _lib.launch(lib.obca_plan_refine, B, N, ratio, ptr(x), ptr(ts), ptr(status), int(variant_ok), ptr(xref), ptr(ts_out),
+                ptr(variant_out), dev=dev)
     return xref, ts_out, variant_out
 
 
@@ -61,8 +60,7 @@ def route_reference(path, path_len, N, start=None, goal=None, device=None):
     point not finite, zero length), ok = 0 and the start/goal-only reference where both pins are given, else point 0 of the
     path at every knot (zeros where it is not finite).  On the current stream, no host synchronisation."""
     import torch
-    if not torch.cuda.is_available():
-        raise RuntimeError("route_reference needs a ROCm GPU; there is no CPU fallback on the product path")
+    _lib.require_gpu("route_reference")
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     lib = _lib.load()
     path = torch.as_tensor(path, dtype=torch.float64, device=dev).contiguous()
@@ -82,13 +80,9 @@ def route_reference(path, path_len, N, start=None, goal=None, device=None):
     xref = torch.empty(B, 3, max(N, 0) + 1, dtype=torch.float64, device=dev)
     ok = torch.empty(B, dtype=torch.int32, device=dev)
     ptr = _lib.ptr
-    _lib.check(lib.obca_route_resample(B, P, N, ptr(path), ptr(path_len), ptr(pins[0]), ptr(pins[1]), ptr(xref), ptr(ok),
-                                       _lib.device_index(dev), _lib.stream_ptr(dev)))
-    # the launch is asynchronous: the tensors it reads are tied to the result and to the stream (see planner.plan_batch)
-    xref._obca_keep = (path, path_len, pins[0], pins[1])
-    for t in xref._obca_keep:
-        if t is not None:
-            t.record_stream(torch.cuda.current_stream(dev))
+    _lib.launch(lib.obca_route_resample, B, P, N, ptr(path), ptr(path_len), ptr(pins[0]), ptr(pins[1]), ptr(xref), ptr(ok), dev=dev)
+    # the launch is asynchronous: the tensors it reads are tied to the result and to the stream (see _lib.keep_alive)
+    _lib.keep_alive(xref, (path, path_len, pins[0], pins[1]), dev)
     return xref, ok
 
 

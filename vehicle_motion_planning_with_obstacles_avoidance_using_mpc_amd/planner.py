@@ -25,8 +25,7 @@ def plan_batch(grids, starts, goals, path_max=None, device=None):
     path_len [B] (negative: -1 no route, -2 open list overflow, -3 path_max too small, -4 start or goal outside the
     grid; the path of an instance with a negative code is left unwritten)."""
     import torch
-    if not torch.cuda.is_available():
-        raise RuntimeError("plan_batch needs a ROCm GPU; there is no CPU fallback on the product path")
+    _lib.require_gpu("plan_batch")
     lib = _lib.load()
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     if isinstance(grids, torch.Tensor):                      # e.g. the output of rasterise_batch: stays on the device
@@ -47,12 +46,8 @@ def plan_batch(grids, starts, goals, path_max=None, device=None):
     ptr = _lib.ptr
     _lib.check(lib.obca_astar_batch(ptr(g), B, rows, cols, ptr(st), ptr(go), yaw, P, ptr(path), ptr(plen), ptr(work),
                                     need, _lib.stream_ptr(dev)))
-    # the launch is asynchronous: the tensors it reads must outlive it.  They are tied to the RESULT (a second call
-    # before the stream drains must not free the first call's workspace), and the caching allocator keeps a freed block
-    # out of other streams' hands until this stream has passed the free point.
-    path._obca_keep = (g, st, go, work)
-    for t in (g, st, go, work):
-        t.record_stream(torch.cuda.current_stream(dev))
+    # the launch is asynchronous: the tensors it reads, the workspace among them, are tied to the RESULT (see _lib.keep_alive)
+    _lib.keep_alive(path, (g, st, go, work), dev)
     return path, plen
 
 
@@ -61,8 +56,7 @@ def rasterise_batch(obstacle_lists, map_size, resolution=1.0, device=None):
     obstacle_lists: per world a list of polygons (vertex lists, e.g. ``setting.static_gridlObs``); map_size = (x, y) as in
     ``problemSetting`` (src/demo_setting.py:67-68).  Returns a device tensor [B, rows, cols] uint8 = ``org_gridMap``."""
     import torch
-    if not torch.cuda.is_available():
-        raise RuntimeError("rasterise_batch needs a ROCm GPU; there is no CPU fallback on the product path")
+    _lib.require_gpu("rasterise_batch")
     lib = _lib.load()
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     B = len(obstacle_lists)
@@ -77,7 +71,7 @@ def rasterise_batch(obstacle_lists, map_size, resolution=1.0, device=None):
     bx = torch.as_tensor(boxes, device=dev)
     grid = torch.empty(B, rows, cols, dtype=torch.uint8, device=dev)
     _lib.check(lib.obca_rasterise_batch(_lib.ptr(bx), B, K, float(resolution), rows, cols, _lib.ptr(grid), _lib.stream_ptr(dev)))
-    bx.record_stream(torch.cuda.current_stream(dev))
+    _lib.keep_alive(grid, (bx,), dev)                        # the launch is asynchronous: see plan_batch
     return grid
 
 
@@ -87,8 +81,7 @@ def dilate_batch(grids, level, device=None):
     device tensor, e.g. ``rasterise_batch``'s, stays on the device), 0 <= level <= 16.  Returns a device tensor
     [B,rows,cols] uint8 of 0 / 1, which ``plan_batch`` takes."""
     import torch
-    if not torch.cuda.is_available():
-        raise RuntimeError("dilate_batch needs a ROCm GPU; there is no CPU fallback on the product path")
+    _lib.require_gpu("dilate_batch")
     lib = _lib.load()
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     if isinstance(grids, torch.Tensor):
@@ -99,8 +92,6 @@ def dilate_batch(grids, level, device=None):
         raise ValueError("expected grids [B,rows,cols], got %s" % (tuple(g.shape),))
     B, rows, cols = g.shape
     out = torch.empty(B, rows, cols, dtype=torch.uint8, device=dev)
-    _lib.check(lib.obca_grid_dilate_batch(_lib.ptr(g), B, rows, cols, int(level), _lib.ptr(out), _lib.device_index(dev),
-                                          _lib.stream_ptr(dev)))
-    out._obca_keep = (g,)                                    # the launch is asynchronous: see plan_batch
-    g.record_stream(torch.cuda.current_stream(dev))
+    _lib.launch(lib.obca_grid_dilate_batch, _lib.ptr(g), B, rows, cols, int(level), _lib.ptr(out), dev=dev)
+    _lib.keep_alive(out, (g,), dev)                          # the launch is asynchronous: see plan_batch
     return out

@@ -222,8 +222,7 @@ class DeviceRollouts:
         obca_rollouts_set_swept_rows; needs exact_sensing)."""
         self.swept_rows = _swept_options(swept_rows, exact_sensing)     # (checked before anything is created)
         import torch
-        if not torch.cuda.is_available():
-            raise RuntimeError("DeviceRollouts needs a ROCm GPU; there is no CPU fallback on the product path")
+        _lib.require_gpu("DeviceRollouts")
         self.torch = torch
         self.lib = _lib.load()
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)

@@ -63,8 +63,7 @@ def select(pool_A, pool_b, x, n_sel, pool_v=None, Ts=None, x0=None, variant=None
     selection changed, else 0), ok [B] (0: unusable pool or poses, filled rows a = (1, 0), b = -1e6), score [B,K] (NaN where
     never written) and min_clear [B] (this call's smallest distance over the whole pool, NaN where not measured)."""
     import torch
-    if not torch.cuda.is_available():
-        raise RuntimeError("scene.select needs a ROCm GPU; there is no CPU fallback on the product path")
+    _lib.require_gpu("scene.select")
     dev = _dev_of(device, x, pool_A)
     t = lambda a, dt=torch.float64: torch.as_tensor(a, dtype=dt, device=dev).contiguous()
     pool_A, pool_b, x = t(pool_A), t(pool_b), t(x)
@@ -106,10 +105,9 @@ def select(pool_A, pool_b, x, n_sel, pool_v=None, Ts=None, x0=None, variant=None
     p = _lib.ptr
     staged = (stage_A, stage_b, stage_ok)
     if all(a is None for a in staged):
-        _lib.check(_lib.load().obca_scene_select(ego_c, B, K, E, N1 - 1, n_sel, int(n_sub), 0 if state is None else 1, p(pool_A),
-                                                 p(pool_b), p(pool_v), p(Ts), p(x), p(x0), p(variant), p(status), p(score), p(sel),
-                                                 p(out["A"]), p(out["b"]), p(out["variant_out"]), p(out["ok"]), p(out["min_clear"]),
-                                                 _lib.device_index(dev), _lib.stream_ptr(dev)))
+        _lib.launch(_lib.load().obca_scene_select, ego_c, B, K, E, N1 - 1, n_sel, int(n_sub), 0 if state is None else 1, p(pool_A),
+                    p(pool_b), p(pool_v), p(Ts), p(x), p(x0), p(variant), p(status), p(score), p(sel), p(out["A"]), p(out["b"]),
+                    p(out["variant_out"]), p(out["ok"]), p(out["min_clear"]), dev=dev)
         staged = ()
     else:
         if any(a is None for a in staged):
@@ -121,17 +119,18 @@ def select(pool_A, pool_b, x, n_sel, pool_v=None, Ts=None, x0=None, variant=None
         Kt = int(stage_ok.shape[1])
         stage_A, stage_b = opt(stage_A, (B // group, Kt, N1, E, 2)), opt(stage_b, (B // group, Kt, N1, E))
         staged = (stage_A, stage_b, stage_ok)
-        _lib.check(_lib.load().obca_scene_select_staged(ego_c, B, K, E, N1 - 1, n_sel, int(n_sub), 0 if state is None else 1,
-                                                        p(pool_A), p(pool_b), p(pool_v), p(Ts), p(x), p(x0), p(variant), p(status),
-                                                        Kt, group, p(stage_A), p(stage_b), p(stage_ok), p(score), p(sel),
-                                                        p(out["A"]), p(out["b"]), p(out["variant_out"]), p(out["ok"]),
-                                                        p(out["min_clear"]), _lib.device_index(dev), _lib.stream_ptr(dev)))
-    # the launch is asynchronous: the tensors it reads are tied to the result and to the stream (see openloop.route_reference)
-    out["A"]._obca_keep = (pool_A, pool_b, pool_v, Ts, x, x0, variant, status) + staged
-    for a in out["A"]._obca_keep:
-        if a is not None:
-            a.record_stream(torch.cuda.current_stream(dev))
+        _lib.launch(_lib.load().obca_scene_select_staged, ego_c, B, K, E, N1 - 1, n_sel, int(n_sub), 0 if state is None else 1,
+                    p(pool_A), p(pool_b), p(pool_v), p(Ts), p(x), p(x0), p(variant), p(status), Kt, group, p(stage_A), p(stage_b),
+                    p(stage_ok), p(score), p(sel), p(out["A"]), p(out["b"]), p(out["variant_out"]), p(out["ok"]), p(out["min_clear"]),
+                    dev=dev)
+    # the launch is asynchronous: the tensors it reads are tied to the result and to the stream (see _lib.keep_alive)
+    _lib.keep_alive(out["A"], (pool_A, pool_b, pool_v, Ts, x, x0, variant, status) + staged, dev)
     return out
+
+
+def _fleet_tracks_desc(G, V, N, see, margin, far, ego, **members):
+    """the descriptor of obca_fleet_tracks: ``fleet_tracks``' and ``FleetLoop``'s"""
+    return _lib.ObcaFleetTracks().set(G=G, V=V, N=N, see=_lib.FLEET_SEE[see], margin=float(margin), far=float(far), ego=ego, **members)
 
 
 def fleet_tracks(x0, flags, k, xopt, status, V, step, see="all", margin=0.0, far=100.0, ego=DEFAULT_EGO, out=None, device=None):
@@ -141,8 +140,7 @@ def fleet_tracks(x0, flags, k, xopt, status, V, step, see="all", margin=0.0, far
     ``select``'s stage_A, stage_b and stage_ok with stage_group = V for pools whose last V slots are the cars.  ``out``: a dict
     of such tensors to write into."""
     import torch
-    if not torch.cuda.is_available():
-        raise RuntimeError("scene.fleet_tracks needs a ROCm GPU; there is no CPU fallback on the product path")
+    _lib.require_gpu("scene.fleet_tracks")
     if see not in _lib.FLEET_SEE:
         raise ValueError("see is one of %s" % sorted(_lib.FLEET_SEE))
     dev = _dev_of(device, xopt, x0)
@@ -160,16 +158,10 @@ def fleet_tracks(x0, flags, k, xopt, status, V, step, see="all", margin=0.0, far
         out = {"track_A": torch.empty(G, V, N1, 4, 2, dtype=torch.float64, device=dev),
                "track_b": torch.empty(G, V, N1, 4, dtype=torch.float64, device=dev),
                "track_ok": torch.empty(B, V, dtype=torch.int32, device=dev)}
-    d = _lib.ObcaFleetTracks()
-    d.G, d.V, d.N, d.step, d.see, d.margin, d.far = G, V, N1 - 1, int(step), _lib.FLEET_SEE[see], float(margin), float(far)
-    d.ego = (ctypes.c_double * 4)(*[float(v) for v in ego])
-    for name, a in (("x0", x0), ("flags", flags), ("k", k), ("xopt", xopt), ("status", status), ("track_A", out["track_A"]),
-                    ("track_b", out["track_b"]), ("track_ok", out["track_ok"])):
-        setattr(d, name, a.data_ptr())
-    _lib.check(_lib.load().obca_fleet_tracks(ctypes.byref(d), _lib.device_index(dev), _lib.stream_ptr(dev)))
-    out["track_A"]._obca_keep = (x0, flags, k, xopt, status)     # the launch is asynchronous: see ``select``
-    for a in out["track_A"]._obca_keep:
-        a.record_stream(torch.cuda.current_stream(dev))
+    d = _fleet_tracks_desc(G, V, N1 - 1, see, margin, far, ego, step=int(step), x0=x0, flags=flags, k=k, xopt=xopt, status=status,
+                           track_A=out["track_A"], track_b=out["track_b"], track_ok=out["track_ok"])
+    _lib.launch(_lib.load().obca_fleet_tracks, ctypes.byref(d), dev=dev)
+    _lib.keep_alive(out["track_A"], (x0, flags, k, xopt, status), dev)     # the launch is asynchronous: see ``select``
     return out
 
 
@@ -197,6 +189,13 @@ def check_tracks(tracks, track_t, track_len, track_size):
                 raise ValueError("track %d of block %d is not usable: %s" % (j, bt, why))
 
 
+def _pool_tracks_desc(B, K, Kt, N, L, group, max_steps, n_sub, predict, clearance, margin, far, ego, **members):
+    """the descriptor of obca_pool_tracks: ``pool_tracks``' and ``TrackLoop``'s"""
+    return _lib.ObcaPoolTracks().set(B=B, K=K, Kt=Kt, N=N, L=L, group=group, max_steps=max_steps, n_sub=int(n_sub),
+                                     predict=_lib.TRACK_PREDICT[predict], clearance=NEVER_STOP if clearance is None else float(clearance),
+                                     margin=float(margin), far=float(far), ego=ego, **members)
+
+
 def pool_tracks(tracks, track_t, track_len, track_size, Ts, k, x0, pool_A, pool_b, pool_v, N, group=1, t0=None, predict="track",
                 margin=0.0, far=100.0, measure=False, step=0, x_prev=None, flags=None, max_steps=1, n_sub=8, clearance=None,
                 ego=DEFAULT_EGO, out=None, device=None):
@@ -214,8 +213,7 @@ def pool_tracks(tracks, track_t, track_len, track_size, Ts, k, x0, pool_A, pool_
     measured), flags, xref_out [B,3,N+1] and variant_out [B] (written for a rollout that measure ended).  ``out``: a dict of
     such tensors to write into."""
     import torch
-    if not torch.cuda.is_available():
-        raise RuntimeError("scene.pool_tracks needs a ROCm GPU; there is no CPU fallback on the product path")
+    _lib.require_gpu("scene.pool_tracks")
     if predict not in _lib.TRACK_PREDICT:
         raise ValueError("predict is one of %s" % sorted(_lib.TRACK_PREDICT))
     dev = _dev_of(device, pool_A, tracks, x0)
@@ -253,20 +251,12 @@ def pool_tracks(tracks, track_t, track_len, track_size, Ts, k, x0, pool_A, pool_
                "xref_out": torch.zeros(B, 3, N + 1, dtype=torch.float64, device=dev),
                "variant_out": torch.zeros(B, dtype=torch.int32, device=dev)}
     out["flags"] = flags
-    d = _lib.ObcaPoolTracks()
-    d.B, d.K, d.Kt, d.N, d.L, d.group, d.max_steps, d.step, d.n_sub = B, K, Kt, N, L, group, S, int(step), int(n_sub)
-    d.predict, d.margin, d.far = _lib.TRACK_PREDICT[predict], float(margin), float(far)
-    d.clearance = NEVER_STOP if clearance is None else float(clearance)
-    d.ego = (ctypes.c_double * 4)(*[float(v) for v in ego])
-    ins = (("track_x", tracks), ("track_t", track_t), ("track_len", track_len), ("track_size", track_size), ("t0", t0), ("Ts", Ts),
-           ("x_prev", x_prev), ("x0", x0), ("k", k))
-    for name, a in ins + (("flags", flags), ("pool_A", pool_A), ("pool_b", pool_b), ("pool_v", pool_v)) + \
-            tuple((n, out[n]) for n in ("stage_A", "stage_b", "stage_ok", "track_state", "track_clear_hist", "xref_out", "variant_out")):
-        setattr(d, name, None if a is None else a.data_ptr())
-    _lib.check(_lib.load().obca_pool_tracks(ctypes.byref(d), 1 if measure else 0, _lib.device_index(dev), _lib.stream_ptr(dev)))
-    out["stage_A"]._obca_keep = tuple(a for _, a in ins if a is not None)     # the launch is asynchronous: see ``select``
-    for a in out["stage_A"]._obca_keep:
-        a.record_stream(torch.cuda.current_stream(dev))
+    ins = dict(track_x=tracks, track_t=track_t, track_len=track_len, track_size=track_size, t0=t0, Ts=Ts, x_prev=x_prev, x0=x0, k=k)
+    d = _pool_tracks_desc(B, K, Kt, N, L, group, S, n_sub, predict, clearance, margin, far, ego, step=int(step), flags=flags,
+                          pool_A=pool_A, pool_b=pool_b, pool_v=pool_v, **ins,
+                          **{n: out[n] for n in ("stage_A", "stage_b", "stage_ok", "track_state", "track_clear_hist", "xref_out", "variant_out")})
+    _lib.launch(_lib.load().obca_pool_tracks, ctypes.byref(d), 1 if measure else 0, dev=dev)
+    _lib.keep_alive(out["stage_A"], ins.values(), dev)                    # the launch is asynchronous: see ``select``
     return out
 
 
@@ -364,8 +354,7 @@ def grid_pool(grids, K, resolution=1.0, pad=None, far=100.0, device=None):
     rectangles, also beyond K) and ok [B] int32 (0: count > K, the first K rectangles are written, the map is not covered)."""
     import numpy as np
     import torch
-    if not torch.cuda.is_available():
-        raise RuntimeError("scene.grid_pool needs a ROCm GPU; there is no CPU fallback on the product path")
+    _lib.require_gpu("scene.grid_pool")
     dev = _dev_of(device, grids)
     if isinstance(grids, torch.Tensor):
         g = grids.to(device=dev, dtype=torch.uint8).contiguous()
@@ -383,11 +372,9 @@ def grid_pool(grids, K, resolution=1.0, pad=None, far=100.0, device=None):
            "count": torch.empty(B, dtype=torch.int32, device=dev),
            "ok": torch.empty(B, dtype=torch.int32, device=dev)}
     p = _lib.ptr
-    _lib.check(_lib.load().obca_grid_pool(p(g), B, rows, cols, K, resolution, pad, float(far), p(out["pool_A"]), p(out["pool_b"]),
-                                          p(out["rect"]), p(out["count"]), p(out["ok"]), _lib.device_index(dev),
-                                          _lib.stream_ptr(dev)))
-    out["pool_A"]._obca_keep = (g,)                          # the launch is asynchronous: see planner.dilate_batch
-    g.record_stream(torch.cuda.current_stream(dev))
+    _lib.launch(_lib.load().obca_grid_pool, p(g), B, rows, cols, K, resolution, pad, float(far), p(out["pool_A"]), p(out["pool_b"]),
+                p(out["rect"]), p(out["count"]), p(out["ok"]), dev=dev)
+    _lib.keep_alive(out["pool_A"], (g,), dev)                # the launch is asynchronous: see planner.dilate_batch
     return out
 
 
@@ -430,6 +417,33 @@ def solve_maps(solver, grids, start_cells, goal_cells, start, goal, Ts, K, pad=N
 NEVER_STOP = -1e300          # obca_pool_loop.clearance must be finite: below every distance a double can hold
 
 
+def _with_spare_slots(solver, B, pool_A, pool_b, pool_v, n, far, what):
+    """the static part of every rollout's pool -- pool_A [B,Ks,4,2], pool_b [B,Ks,4] and optionally pool_v [B,Ks,2], or None for
+    Ks = 0 -- with n spare slots (``grid_pool``'s spare at ``far``) appended, which a loop's step call rewrites at every reset
+    and after every step.  Returns (full_A, full_b, full_v, Ks); ``what`` names the n slots in the error message."""
+    import torch
+    dev = solver.device
+    f64 = lambda a: torch.as_tensor(a, dtype=torch.float64, device=dev)
+    if pool_A is None or pool_b is None:
+        if pool_A is not None or pool_b is not None or pool_v is not None:
+            raise ValueError("pool_A and pool_b are given together; without them there is no pool_v")
+        sA, sb = torch.zeros(B, 0, 4, 2, dtype=torch.float64, device=dev), torch.zeros(B, 0, 4, dtype=torch.float64, device=dev)
+    else:
+        sA, sb = f64(pool_A), f64(pool_b)
+    if sA.dim() != 4 or sb.dim() != 3 or tuple(sA.shape) != tuple(sb.shape) + (2,) or sb.shape[0] != B or sb.shape[2] != 4:
+        raise ValueError("expected pool_A [B,Ks,4,2], pool_b [B,Ks,4] with B = %d" % B)
+    Ks = int(sb.shape[1])
+    if Ks + n > 64:
+        raise ValueError("Ks + %s = %d slots: a pool holds 64 at the most" % (what, Ks + n))
+    sv = torch.zeros(B, Ks, 2, dtype=torch.float64, device=dev) if pool_v is None else solver._dev(pool_v, (B, Ks, 2))
+    spare_A = f64([[0.0, 1.0], [1.0, 0.0], [0.0, -1.0], [-1.0, 0.0]])
+    spare_b = f64([-far, -far, far + 1.0, far + 1.0])
+    full_A = torch.cat([sA, spare_A.expand(B, n, 4, 2)], dim=1).contiguous()
+    full_b = torch.cat([sb, spare_b.expand(B, n, 4)], dim=1).contiguous()
+    full_v = torch.cat([sv, torch.zeros(B, n, 2, dtype=torch.float64, device=dev)], dim=1).contiguous()
+    return full_A, full_b, full_v, Ks
+
+
 class PoolLoop:
     """B closed-loop rollouts over scene pools on one GPU, the counterpart of ``rollouts.DeviceRollouts`` for worlds of up to 64
     obstacles: ``reset()`` starts them, ``step()`` enqueues one receding-horizon step of every running rollout, ``run()`` all of
@@ -451,8 +465,7 @@ class PoolLoop:
     def __init__(self, solver, pool_A, pool_b, start, goal, path, path_len, Ts, pool_v=None, variant=None, params=None,
                  max_steps=30, rounds=0, select_n_sub=1, n_sub=8, clearance=None, goal_tol2=0.1, ego=DEFAULT_EGO):
         import torch
-        if not torch.cuda.is_available():
-            raise RuntimeError("scene.PoolLoop needs a ROCm GPU; there is no CPU fallback on the product path")
+        _lib.require_gpu("scene.PoolLoop")
         self.torch, self.lib, self.solver = torch, _lib.load(), solver
         dev = self.device = solver.device
         f64 = lambda a: torch.as_tensor(a, dtype=torch.float64, device=dev).contiguous()
@@ -495,24 +508,34 @@ class PoolLoop:
         self.term = f(B, 3)
         self._held = None                                    # the solve's outputs, allocated by the first solve
         self._last = (None, None)                            # (result, selection) of the last step
-        d = self._desc = _lib.ObcaPoolLoop()
-        d.B, d.K, d.E, d.N, d.n_sel, d.path_max, d.max_steps = B, K, E, N, n_sel, int(self.path.shape[2]), S
-        d.variant, d.n_sub, d.clearance, d.goal_tol2 = self.variant, self.n_sub, self.clearance, self.goal_tol2
-        d.ego = (ctypes.c_double * 4)(*self.ego)
-        a = lambda t: None if t is None else t.data_ptr()
-        for name, t in (("pool_A", self.pool_A), ("pool_v", self.pool_v), ("goal", self.goal), ("path", self.path),
-                        ("path_len", self.path_len), ("x0", self.x0), ("u0", self.u0), ("pool_b", self.pool_b), ("k", self.k),
-                        ("flags", self.flags), ("x_closed", self.hist["x_closed"]), ("u_closed", self.hist["u_closed"]),
-                        ("T_closed", self.hist["T_closed"]), ("status_hist", self.hist["status"]), ("iters_hist", self.hist["iters"]),
-                        ("clear_hist", self.hist["clear"]), ("sel_hist", self.hist["sel"]), ("xref_out", self.xref),
-                        ("variant_out", self.variant_out)):
-            setattr(d, name, a(t))
+        self._desc = _lib.ObcaPoolLoop().set(
+            B=B, K=K, E=E, N=N, n_sel=n_sel, path_max=int(self.path.shape[2]), max_steps=S, variant=self.variant, n_sub=self.n_sub,
+            clearance=self.clearance, goal_tol2=self.goal_tol2, ego=self.ego, pool_A=self.pool_A, pool_v=self.pool_v, goal=self.goal,
+            path=self.path, path_len=self.path_len, x0=self.x0, u0=self.u0, pool_b=self.pool_b, k=self.k, flags=self.flags,
+            x_closed=self.hist["x_closed"], u_closed=self.hist["u_closed"], T_closed=self.hist["T_closed"],
+            status_hist=self.hist["status"], iters_hist=self.hist["iters"], clear_hist=self.hist["clear"], sel_hist=self.hist["sel"],
+            xref_out=self.xref, variant_out=self.variant_out)
+        self.x_prev = None                                   # a loop with an after-step hook: made by the first reset
         self.steps_enqueued = 0
         self.reset()
 
+    # ---- what a loop with a step call of its own between two solves overrides (``FleetLoop``, ``TrackLoop``)
+    def _staged(self):
+        """the stage_* keyword arguments of ``select``, or {} for obca_scene_select"""
+        return {}
+
+    def _after_reset(self):
+        """called at the end of ``reset()``, x_prev = x0; the first time, it also makes the loop's own buffers and descriptor"""
+
+    def _after_step(self, measure, step):
+        """called after obca_pool_loop_advance of every step: (1, the step's index), or (0, 0) beyond the cap, where nobody steps"""
+
+    def _hooked(self):
+        return type(self)._after_step is not PoolLoop._after_step
+
     def _tensors(self):
         own = [self.pool_A, self.pool_b0, self.pool_v, self.start, self.goal, self.path, self.path_len, self.Ts, self.x0, self.u0,
-               self.pool_b, self.k, self.flags, self.xref, self.variant_out, self.term] + list(self.hist.values())
+               self.pool_b, self.k, self.flags, self.xref, self.variant_out, self.term, self.x_prev] + list(self.hist.values())
         r, sel = self._last                                  # the last solve's outputs: the descriptor still points at them
         if r is not None:
             own += [r.xopt, r.uopt, r.ts_opt, r.status, r.iters, r.info, sel]
@@ -520,13 +543,10 @@ class PoolLoop:
 
     def _on_stream(self):
         """the launches are asynchronous: every tensor they touch is recorded on the stream they run on (see ``select``)"""
-        s = self.torch.cuda.current_stream(self.device)
-        for t in self._tensors():
-            t.record_stream(s)
+        _lib.keep_alive(self, self._tensors(), self.device)
 
     def _advance(self, solved):
-        _lib.check(self.lib.obca_pool_loop_advance(ctypes.byref(self._desc), int(solved), _lib.device_index(self.device),
-                                                   _lib.stream_ptr(self.device)))
+        _lib.launch(self.lib.obca_pool_loop_advance, ctypes.byref(self._desc), int(solved), dev=self.device)
 
     def reset(self):
         self._on_stream()
@@ -534,13 +554,23 @@ class PoolLoop:
         self.pool_b.copy_(self.pool_b0)
         self._advance(0)
         self.steps_enqueued = 0
+        if self._hooked():
+            first = self.x_prev is None                      # the reset the constructor ends with
+            if first:
+                self.x_prev = self.torch.zeros(self.B, 3, dtype=self.torch.float64, device=self.device)
+            self.x_prev.copy_(self.x0)
+            self._after_reset()
+            if first:
+                self._on_stream()
 
     def _select(self):
         return select(self.pool_A, self.pool_b, self.xref, self.n_sel, pool_v=self.pool_v, Ts=self.Ts, x0=self.x0,
-                      variant=self.variant_out, n_sub=self.select_n_sub, ego=self.ego, device=self.device)
+                      variant=self.variant_out, n_sub=self.select_n_sub, ego=self.ego, device=self.device, **self._staged())
 
     def _step(self):
         torch, solver, d = self.torch, self.solver, self._desc
+        if self._hooked():
+            self.x_prev.copy_(self.x0)
         if self.rounds == 0:
             s = self._select()
             var = torch.where(s["ok"] != 0, self.variant_out, 0).to(torch.int32)
@@ -553,11 +583,13 @@ class PoolLoop:
                                   n_sub=max(self.n_sub, 1), ego=self.ego)
             sel = info["sel"]
         self._last = (r, sel)                                # alive until the next step replaces them
-        for name, t in (("status", r.status), ("iters", r.iters), ("ts_opt", r.ts_opt), ("xopt", r.xopt), ("uopt", r.uopt),
-                        ("sel", sel)):
-            setattr(d, name, t.data_ptr())
+        d.set(status=r.status, iters=r.iters, ts_opt=r.ts_opt, xopt=r.xopt, uopt=r.uopt, sel=sel)
         self._advance(1)
         self.steps_enqueued += 1
+        if self.steps_enqueued <= self.max_steps:
+            self._after_step(1, self.steps_enqueued - 1)
+        else:                                                # beyond the cap nobody steps
+            self._after_step(0, 0)
 
     def step(self):
         self._on_stream()
@@ -615,9 +647,7 @@ class FleetLoop(PoolLoop):
                  margin=0.0, far=100.0, agent_clearance=None, agent_n_sub=8, **kw):
         import numpy as np
         import torch
-        if not torch.cuda.is_available():
-            raise RuntimeError("scene.FleetLoop needs a ROCm GPU; there is no CPU fallback on the product path")
-        dev = solver.device
+        _lib.require_gpu("scene.FleetLoop")
         V = self.V = int(V)
         if see not in _lib.FLEET_SEE or (predict not in _lib.FLEET_PREDICT and predict != "plan"):
             raise ValueError("see is one of %s and predict one of %s" % (sorted(_lib.FLEET_SEE), sorted(_lib.FLEET_PREDICT) + ["plan"]))
@@ -626,36 +656,18 @@ class FleetLoop(PoolLoop):
         if kw.get("variant") not in (None, 8):
             raise ValueError("variant %r: a fleet's time is synchronous, the loop runs obca_mpc8 (8) only" % (kw["variant"],))
         kw["variant"] = 8
-        start = torch.as_tensor(start, dtype=torch.float64, device=dev)
+        start = torch.as_tensor(start, dtype=torch.float64, device=solver.device)
         B = int(start.shape[0])
         if V < 1 or V > 16 or B % V != 0:
             raise ValueError("B = %d rollouts are no whole number of worlds of V = %d cars (1 <= V <= 16)" % (B, V))
         self.G = B // V
-        f64 = lambda a: torch.as_tensor(a, dtype=torch.float64, device=dev)
-        if pool_A is None or pool_b is None:
-            if pool_A is not None or pool_b is not None or pool_v is not None:
-                raise ValueError("pool_A and pool_b are given together; without them there is no pool_v")
-            sA, sb = torch.zeros(B, 0, 4, 2, dtype=torch.float64, device=dev), torch.zeros(B, 0, 4, dtype=torch.float64, device=dev)
-        else:
-            sA, sb = f64(pool_A), f64(pool_b)
-        if sA.dim() != 4 or sb.dim() != 3 or tuple(sA.shape) != tuple(sb.shape) + (2,) or sb.shape[0] != B or sb.shape[2] != 4:
-            raise ValueError("expected pool_A [B,Ks,4,2], pool_b [B,Ks,4] with B = %d" % B)
-        Ks = self.Ks = int(sb.shape[1])
-        if Ks + V > 64:
-            raise ValueError("Ks + V = %d slots: a pool holds 64 at the most" % (Ks + V))
-        sv = torch.zeros(B, Ks, 2, dtype=torch.float64, device=dev) if pool_v is None else solver._dev(pool_v, (B, Ks, 2))
+        # the agent slots start as spares; obca_fleet_step writes them at every reset and after every step
+        full_A, full_b, full_v, self.Ks = _with_spare_slots(solver, B, pool_A, pool_b, pool_v, V, float(far), "V")
         if not isinstance(Ts, torch.Tensor) or not Ts.is_cuda:
             t = np.asarray(Ts.cpu() if isinstance(Ts, torch.Tensor) else Ts, dtype=float)
             if t.ndim != 0 and (t.shape != (B,) or not np.all(t.reshape(self.G, V) == t.reshape(self.G, V)[:, :1])):
                 raise ValueError("Ts must be one value per world: [B] with the same word for the V cars of a world, or a float")
-        # the agent slots start as spares; obca_fleet_step writes them at every reset and after every step
-        far = float(far)
-        spare_A = torch.tensor([[0.0, 1.0], [1.0, 0.0], [0.0, -1.0], [-1.0, 0.0]], dtype=torch.float64, device=dev)
-        spare_b = torch.tensor([-far, -far, far + 1.0, far + 1.0], dtype=torch.float64, device=dev)
-        full_A = torch.cat([sA, spare_A.expand(B, V, 4, 2)], dim=1).contiguous()
-        full_b = torch.cat([sb, spare_b.expand(B, V, 4)], dim=1).contiguous()
-        full_v = torch.cat([sv, torch.zeros(B, V, 2, dtype=torch.float64, device=dev)], dim=1).contiguous()
-        self.see, self.predict, self.margin, self.far = see, predict, float(margin), far
+        self.see, self.predict, self.margin, self.far = see, predict, float(margin), float(far)
         self.agent_clearance = NEVER_STOP if agent_clearance is None else float(agent_clearance)
         self.agent_n_sub = int(agent_n_sub)
         self._fdesc = None                                   # made by the first reset, which PoolLoop's constructor ends with
@@ -663,77 +675,56 @@ class FleetLoop(PoolLoop):
 
     def _make_fleet(self):
         torch = self.torch
-        self.x_prev = torch.zeros(self.B, 3, dtype=torch.float64, device=self.device)
         self.agent_clear = torch.zeros(self.B, self.max_steps, dtype=torch.float64, device=self.device)
-        d = self._fdesc = _lib.ObcaFleet()
-        d.G, d.V, d.Ks, d.N, d.max_steps, d.n_sub = self.G, self.V, self.Ks, self.N, self.max_steps, self.agent_n_sub
         # "plan" is the loop's word: the C call writes the velocity prediction, the tracks replace it where there is a plan
-        d.see, d.predict = _lib.FLEET_SEE[self.see], _lib.FLEET_PREDICT["velocity" if self.predict == "plan" else self.predict]
-        d.clearance, d.margin, d.far = self.agent_clearance, self.margin, self.far
-        d.ego = (ctypes.c_double * 4)(*self.ego)
-        for name, t in (("x_prev", self.x_prev), ("x0", self.x0), ("u0", self.u0), ("k", self.k), ("flags", self.flags),
-                        ("pool_A", self.pool_A), ("pool_b", self.pool_b), ("pool_v", self.pool_v),
-                        ("agent_clear_hist", self.agent_clear), ("xref_out", self.xref), ("variant_out", self.variant_out)):
-            setattr(d, name, t.data_ptr())
+        self._fdesc = _lib.ObcaFleet().set(
+            G=self.G, V=self.V, Ks=self.Ks, N=self.N, max_steps=self.max_steps, n_sub=self.agent_n_sub, see=_lib.FLEET_SEE[self.see],
+            predict=_lib.FLEET_PREDICT["velocity" if self.predict == "plan" else self.predict], clearance=self.agent_clearance,
+            margin=self.margin, far=self.far, ego=self.ego, x_prev=self.x_prev, x0=self.x0, u0=self.u0, k=self.k, flags=self.flags,
+            pool_A=self.pool_A, pool_b=self.pool_b, pool_v=self.pool_v, agent_clear_hist=self.agent_clear, xref_out=self.xref,
+            variant_out=self.variant_out)
         if self.predict == "plan":
             G, V, N1 = self.G, self.V, self.N + 1
             self.track_A = torch.zeros(G, V, N1, 4, 2, dtype=torch.float64, device=self.device)
             self.track_b = torch.zeros(G, V, N1, 4, dtype=torch.float64, device=self.device)
             self.track_ok = torch.zeros(self.B, V, dtype=torch.int32, device=self.device)
-            t = self._tdesc = _lib.ObcaFleetTracks()
-            t.G, t.V, t.N, t.see, t.margin, t.far = G, V, self.N, _lib.FLEET_SEE[self.see], self.margin, self.far
-            t.ego = (ctypes.c_double * 4)(*self.ego)
-            for name, a in (("x0", self.x0), ("flags", self.flags), ("k", self.k), ("track_A", self.track_A),
-                            ("track_b", self.track_b), ("track_ok", self.track_ok)):
-                setattr(t, name, a.data_ptr())
+            self._tdesc = _fleet_tracks_desc(G, V, self.N, self.see, self.margin, self.far, self.ego, x0=self.x0, flags=self.flags,
+                                             k=self.k, track_A=self.track_A, track_b=self.track_b, track_ok=self.track_ok)
 
     def _tensors(self):
         own = super()._tensors()
         if self._fdesc is not None:
-            own += [self.x_prev, self.agent_clear]
+            own.append(self.agent_clear)
             if self.predict == "plan":
                 own += [self.track_A, self.track_b, self.track_ok]
         return own
 
-    def _select(self):
-        if self.predict != "plan":
-            return super()._select()
-        return select(self.pool_A, self.pool_b, self.xref, self.n_sel, pool_v=self.pool_v, Ts=self.Ts, x0=self.x0,
-                      variant=self.variant_out, n_sub=self.select_n_sub, ego=self.ego, device=self.device, stage_A=self.track_A,
-                      stage_b=self.track_b, stage_ok=self.track_ok, stage_group=self.V)
-
-    def _tracks(self, step):
-        """obca_fleet_tracks on the solve just applied (``self._last``), after obca_fleet_step on the same stream"""
-        r, t = self._last[0], self._tdesc
-        t.step, t.xopt, t.status = int(step), r.xopt.data_ptr(), r.status.data_ptr()
-        _lib.check(self.lib.obca_fleet_tracks(ctypes.byref(t), _lib.device_index(self.device), _lib.stream_ptr(self.device)))
+    def _staged(self):
+        plan = self.predict == "plan"
+        return dict(stage_A=self.track_A, stage_b=self.track_b, stage_ok=self.track_ok, stage_group=self.V) if plan else {}
 
     def _fleet_step(self, measure, step):
-        self._fdesc.step = int(step)
-        _lib.check(self.lib.obca_fleet_step(ctypes.byref(self._fdesc), int(measure), _lib.device_index(self.device),
-                                            _lib.stream_ptr(self.device)))
+        self._fdesc.set(step=int(step))
+        _lib.launch(self.lib.obca_fleet_step, ctypes.byref(self._fdesc), int(measure), dev=self.device)
 
-    def reset(self):
-        super().reset()
+    def _after_reset(self):
         if self._fdesc is None:
             self._make_fleet()
-            self._on_stream()
-        self.x_prev.copy_(self.x0)
         self.agent_clear.fill_(float("inf"))
         self._fleet_step(0, 0)
         if self.predict == "plan":
             self.track_ok.zero_()                            # no plan yet: the first select is the velocity loop's
 
-    def _step(self):
-        self.x_prev.copy_(self.x0)
-        super()._step()
-        idx = self.steps_enqueued - 1
-        if idx < self.max_steps:
-            self._fleet_step(1, idx)
-        else:                                                # beyond the cap nobody steps: the slots alone
-            self._fleet_step(0, 0)
+    def _tracks(self, step):
+        """obca_fleet_tracks on the solve just applied (``self._last``), after obca_fleet_step on the same stream"""
+        r = self._last[0]
+        self._tdesc.set(step=int(step), xopt=r.xopt, status=r.status)
+        _lib.launch(self.lib.obca_fleet_tracks, ctypes.byref(self._tdesc), dev=self.device)
+
+    def _after_step(self, measure, step):
+        self._fleet_step(measure, step)
         if self.predict == "plan":
-            self._tracks(idx)                                # beyond the cap k == step + 1 fails: every mask word 0
+            self._tracks(self.steps_enqueued - 1)            # beyond the cap k == step + 1 fails: every mask word 0
 
     def read(self):
         """``PoolLoop.read()``'s dict and agent_clear [B,S] (the smallest distance to another car of the world over every
@@ -772,8 +763,7 @@ class TrackLoop(PoolLoop):
                  group=1, t0=None, predict="track", margin=0.0, far=100.0, track_clearance=None, track_n_sub=8, pool_v=None, **kw):
         import numpy as np
         import torch
-        if not torch.cuda.is_available():
-            raise RuntimeError("scene.TrackLoop needs a ROCm GPU; there is no CPU fallback on the product path")
+        _lib.require_gpu("scene.TrackLoop")
         dev = solver.device
         if predict not in _lib.TRACK_PREDICT:
             raise ValueError("predict is one of %s" % sorted(_lib.TRACK_PREDICT))
@@ -799,26 +789,9 @@ class TrackLoop(PoolLoop):
         B, group = int(start.shape[0]), int(group)
         if group < 1 or Bt * group != B:
             raise ValueError("B = %d rollouts are not %d track blocks of group = %d" % (B, Bt, group))
-        if pool_A is None or pool_b is None:
-            if pool_A is not None or pool_b is not None or pool_v is not None:
-                raise ValueError("pool_A and pool_b are given together; without them there is no pool_v")
-            sA, sb = torch.zeros(B, 0, 4, 2, dtype=torch.float64, device=dev), torch.zeros(B, 0, 4, dtype=torch.float64, device=dev)
-        else:
-            sA, sb = f64(pool_A), f64(pool_b)
-        if sA.dim() != 4 or sb.dim() != 3 or tuple(sA.shape) != tuple(sb.shape) + (2,) or sb.shape[0] != B or sb.shape[2] != 4:
-            raise ValueError("expected pool_A [B,Ks,4,2], pool_b [B,Ks,4] with B = %d" % B)
-        Ks = self.Ks = int(sb.shape[1])
-        if Ks + Kt > 64:
-            raise ValueError("Ks + Kt = %d slots: a pool holds 64 at the most" % (Ks + Kt))
-        sv = torch.zeros(B, Ks, 2, dtype=torch.float64, device=dev) if pool_v is None else solver._dev(pool_v, (B, Ks, 2))
         # the tracked slots start as spares; obca_pool_tracks writes them at every reset and after every step
-        far = float(far)
-        spare_A = torch.tensor([[0.0, 1.0], [1.0, 0.0], [0.0, -1.0], [-1.0, 0.0]], dtype=torch.float64, device=dev)
-        spare_b = torch.tensor([-far, -far, far + 1.0, far + 1.0], dtype=torch.float64, device=dev)
-        full_A = torch.cat([sA, spare_A.expand(B, Kt, 4, 2)], dim=1).contiguous()
-        full_b = torch.cat([sb, spare_b.expand(B, Kt, 4)], dim=1).contiguous()
-        full_v = torch.cat([sv, torch.zeros(B, Kt, 2, dtype=torch.float64, device=dev)], dim=1).contiguous()
-        self.Kt, self.L, self.group, self.predict, self.margin, self.far = Kt, L, group, predict, float(margin), far
+        full_A, full_b, full_v, self.Ks = _with_spare_slots(solver, B, pool_A, pool_b, pool_v, Kt, float(far), "Kt")
+        self.Kt, self.L, self.group, self.predict, self.margin, self.far = Kt, L, group, predict, float(margin), float(far)
         self.tracks, self.track_t, self.track_size = f64(tracks), f64(track_t), f64(track_size)
         self.track_len = torch.as_tensor(track_len, dtype=torch.int32, device=dev).contiguous()
         self.t0 = None if t0 is None else solver._dev(torch.as_tensor(t0, dtype=torch.float64).expand(B)
@@ -830,61 +803,42 @@ class TrackLoop(PoolLoop):
 
     def _make_tracks(self):
         torch, dev, B, Kt, N1 = self.torch, self.device, self.B, self.Kt, self.N + 1
-        self.x_prev = torch.zeros(B, 3, dtype=torch.float64, device=dev)
         self.track_clear = torch.zeros(B, self.max_steps, dtype=torch.float64, device=dev)
         self.stage_A = torch.zeros(B, Kt, N1, 4, 2, dtype=torch.float64, device=dev)
         self.stage_b = torch.zeros(B, Kt, N1, 4, dtype=torch.float64, device=dev)
         self.stage_ok = torch.zeros(B, Kt, dtype=torch.int32, device=dev)
         self.track_state = torch.zeros(B, Kt, dtype=torch.int32, device=dev)
-        d = self._tdesc = _lib.ObcaPoolTracks()
-        d.B, d.K, d.Kt, d.N, d.L, d.group, d.max_steps, d.n_sub = B, self.K, Kt, self.N, self.L, self.group, self.max_steps, self.track_n_sub
-        d.predict, d.clearance, d.margin, d.far = _lib.TRACK_PREDICT[self.predict], self.track_clearance, self.margin, self.far
-        d.ego = (ctypes.c_double * 4)(*self.ego)
-        for name, t in (("track_x", self.tracks), ("track_t", self.track_t), ("track_len", self.track_len),
-                        ("track_size", self.track_size), ("t0", self.t0), ("Ts", self.Ts), ("x_prev", self.x_prev), ("x0", self.x0),
-                        ("k", self.k), ("flags", self.flags), ("pool_A", self.pool_A), ("pool_b", self.pool_b), ("pool_v", self.pool_v),
-                        ("stage_A", self.stage_A), ("stage_b", self.stage_b), ("stage_ok", self.stage_ok),
-                        ("track_state", self.track_state), ("track_clear_hist", self.track_clear), ("xref_out", self.xref),
-                        ("variant_out", self.variant_out)):
-            setattr(d, name, None if t is None else t.data_ptr())
+        self._tdesc = _pool_tracks_desc(
+            B, self.K, Kt, self.N, self.L, self.group, self.max_steps, self.track_n_sub, self.predict, self.track_clearance,
+            self.margin, self.far, self.ego, track_x=self.tracks, track_t=self.track_t, track_len=self.track_len,
+            track_size=self.track_size, t0=self.t0, Ts=self.Ts, x_prev=self.x_prev, x0=self.x0, k=self.k, flags=self.flags,
+            pool_A=self.pool_A, pool_b=self.pool_b, pool_v=self.pool_v, stage_A=self.stage_A, stage_b=self.stage_b,
+            stage_ok=self.stage_ok, track_state=self.track_state, track_clear_hist=self.track_clear, xref_out=self.xref,
+            variant_out=self.variant_out)
 
     def _tensors(self):
         own = super()._tensors() + [self.tracks, self.track_t, self.track_len, self.track_size]
         if self.t0 is not None:
             own.append(self.t0)
         if self._tdesc is not None:
-            own += [self.x_prev, self.track_clear, self.stage_A, self.stage_b, self.stage_ok, self.track_state]
+            own += [self.track_clear, self.stage_A, self.stage_b, self.stage_ok, self.track_state]
         return own
 
-    def _select(self):
-        if self.predict != "track":
-            return super()._select()
-        return select(self.pool_A, self.pool_b, self.xref, self.n_sel, pool_v=self.pool_v, Ts=self.Ts, x0=self.x0,
-                      variant=self.variant_out, n_sub=self.select_n_sub, ego=self.ego, device=self.device, stage_A=self.stage_A,
-                      stage_b=self.stage_b, stage_ok=self.stage_ok, stage_group=1)
+    def _staged(self):
+        track = self.predict == "track"
+        return dict(stage_A=self.stage_A, stage_b=self.stage_b, stage_ok=self.stage_ok, stage_group=1) if track else {}
 
     def _pool_tracks(self, measure, step):
-        self._tdesc.step = int(step)
-        _lib.check(self.lib.obca_pool_tracks(ctypes.byref(self._tdesc), int(measure), _lib.device_index(self.device),
-                                             _lib.stream_ptr(self.device)))
+        self._tdesc.set(step=int(step))
+        _lib.launch(self.lib.obca_pool_tracks, ctypes.byref(self._tdesc), int(measure), dev=self.device)
 
-    def reset(self):
-        super().reset()
+    _after_step = _pool_tracks
+
+    def _after_reset(self):
         if self._tdesc is None:
             self._make_tracks()
-            self._on_stream()
-        self.x_prev.copy_(self.x0)
         self.track_clear.fill_(float("inf"))
         self._pool_tracks(0, 0)
-
-    def _step(self):
-        self.x_prev.copy_(self.x0)
-        super()._step()
-        idx = self.steps_enqueued - 1
-        if idx < self.max_steps:
-            self._pool_tracks(1, idx)
-        else:                                                # beyond the cap nobody steps: the rows alone
-            self._pool_tracks(0, 0)
 
     def read(self):
         """``PoolLoop.read()``'s dict and track_clear [B,S] (the smallest distance to a tracked obstacle over every interval the

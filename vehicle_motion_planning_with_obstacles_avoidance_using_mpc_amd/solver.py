@@ -97,8 +97,7 @@ class BatchSolver:
     """One handle = one problem shape (N, obstacle edge counts) on one GPU."""
 
     def __init__(self, N, m, max_batch, device=None, mode=None):
-        if not torch.cuda.is_available():
-            raise RuntimeError("BatchSolver needs a ROCm GPU; there is no CPU fallback on the product path")
+        _lib.require_gpu("BatchSolver")
         self.lib = _lib.load()
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         self.N = int(N)
@@ -213,8 +212,7 @@ def moving_rows(static_A, static_b, boxes, Ts, N, half_window=0.0, margin=0.0, d
     current stream that feed ``BatchSolver.solve`` of a handle with m = static edge counts + [4] * n_box.  half_window
     (steps) / margin (metres) > 0: every stage's rectangle covers the box, inflated by the margin, over the half window on
     either side of the stage (include/obca_mpc.h: obca_rollouts_set_swept_rows); both 0: the box itself at each stage."""
-    if not torch.cuda.is_available():
-        raise RuntimeError("moving_rows needs a ROCm GPU; there is no CPU fallback on the product path")
+    _lib.require_gpu("moving_rows")
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     lib = _lib.load()
     t = lambda a: torch.as_tensor(a, dtype=torch.float64, device=dev).contiguous()
@@ -231,9 +229,8 @@ def moving_rows(static_A, static_b, boxes, Ts, N, half_window=0.0, margin=0.0, d
     A = torch.empty(B, int(N) + 1, M, 2, dtype=torch.float64, device=dev)
     b = torch.empty(B, int(N) + 1, M, dtype=torch.float64, device=dev)
     ptr = _lib.ptr
-    _lib.check(lib.obca_moving_rows_batch(B, int(N), Ms, n_box, ptr(static_A), ptr(static_b), ptr(boxes), ptr(Ts),
-                                          float(half_window), float(margin), ptr(A), ptr(b), _lib.device_index(dev),
-                                          _lib.stream_ptr(dev)))
+    _lib.launch(lib.obca_moving_rows_batch, B, int(N), Ms, n_box, ptr(static_A), ptr(static_b), ptr(boxes), ptr(Ts),
+                float(half_window), float(margin), ptr(A), ptr(b), dev=dev)
     return A, b
 
 
