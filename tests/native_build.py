@@ -5,35 +5,43 @@ import subprocess
 
 import numpy as np
 
+from __graft_entry__ import stale
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
-SRC = os.path.join(HERE, "native", "rollout_host.cpp")
-CSRC = os.path.join(ROOT, "vehicle_motion_planning_with_obstacles_avoidance_using_mpc_amd", "csrc")
-DEPS = [SRC, os.path.join(HERE, "native", "lpi_host.cpp"), os.path.join(CSRC, "obca_lpi_core.h"),
-        os.path.join(CSRC, "obca_rollout_core.h"), os.path.join(CSRC, "obca_astar_core.h"), os.path.join(CSRC, "obca_device.h"), os.path.join(CSRC, "obca_select.h"),
-        os.path.join(ROOT, "include", "obca_mpc.h")]
+NATIVE = os.path.join(HERE, "native")
+SRC = os.path.join(NATIVE, "rollout_host.cpp")
 
 _lib = None
 
 
-def build_shim(name, sources, deps, openmp=False):
-    """tests/native/_build/lib<name>.so from ``sources``, compiled when it is missing or older than a source or one of
-    ``deps`` (the headers and included sources), and loaded.  Without contraction: the host words are the ones numpy and the
-    device's unfused expressions are compared with."""
-    out = os.path.join(HERE, "native", "_build", "lib%s.so" % name)
-    if not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in list(sources) + list(deps)):
+def compile_shim(out, sources, cwd, openmp=False, defines=()):
+    """the shared library ``out`` from ``sources`` (names relative to ``cwd``, where g++ runs), compiled when
+    __graft_entry__.stale() says so: g++ itself lists what it read in <out>.d (-MMD: the sources and every header of ours
+    behind them, at any depth), and <out>.flags records the flag set.  Without contraction: the host words are the ones
+    numpy and the device's unfused expressions are compared with."""
+    flags = (["-fopenmp", "-Wno-unknown-pragmas"] if openmp else []) + ["-D" + d for d in defines]
+    if stale(out, cwd, flags=" ".join(flags)):
         os.makedirs(os.path.dirname(out), exist_ok=True)
-        omp = ["-fopenmp", "-Wno-unknown-pragmas"] if openmp else []
-        subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off"] + omp + list(sources) + ["-o", out],
-                       check=True)
-    return ctypes.CDLL(out)
+        subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off"] + flags + list(sources) +
+                       ["-o", out, "-MMD", "-MF", out + ".d"], check=True, cwd=cwd)
+        with open(out + ".flags", "w") as fh:
+            fh.write(" ".join(flags))
+    return out
+
+
+def build_shim(name, sources, openmp=False, defines=()):
+    """tests/native/_build/lib<name>.so from ``sources`` (files under tests/native), ``defines`` as NAME=VALUE, brought up
+    to date by compile_shim() and loaded"""
+    out = os.path.join(NATIVE, "_build", "lib%s.so" % name)
+    return ctypes.CDLL(compile_shim(out, [os.path.relpath(s, NATIVE) for s in sources], NATIVE, openmp, defines))
 
 
 def load():
     global _lib
     if _lib is not None:
         return _lib
-    _lib = build_shim("native_host", [SRC], DEPS, openmp=True)
+    _lib = build_shim("native_host", [SRC], openmp=True)
     _lib.lpi_host_solve_batch.restype = ctypes.c_int
     _lib.lpi_host_solve_batch_cert.restype = ctypes.c_int
     _lib.rollout_host_run.restype = ctypes.c_int

@@ -13,18 +13,14 @@ from tests import kkt_check, native_build
 from vehicle_motion_planning_with_obstacles_avoidance_using_mpc_amd.model_obstacle import obstacleModel, rectangle_vertices
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 SRC = os.path.join(HERE, "native", "audit_host.cpp")
-CSRC = os.path.join(ROOT, "vehicle_motion_planning_with_obstacles_avoidance_using_mpc_amd", "csrc")
-DEPS = [SRC, os.path.join(CSRC, "obca_plan_batch.h"), os.path.join(CSRC, "obca_audit_core.h"), os.path.join(CSRC, "obca_rollout_core.h"),
-        os.path.join(ROOT, "include", "obca_mpc.h")]
 EGO = (1.7, 0.75, 1.7, 0.75)
 MAXM = 8                    # HOST_MAXM of audit_host.cpp
 E_INVAL = -22
 
 
 def load_host():
-    lib = native_build.build_shim("audit_host", [SRC], DEPS)
+    lib = native_build.build_shim("audit_host", [SRC])
     lib.audit_host_distance.restype = ctypes.c_int
     lib.audit_host_interval.restype = ctypes.c_int
     lib.audit_host_box_next.restype = None

@@ -9,6 +9,8 @@ import numpy as np
 import pytest
 import torch
 
+from __graft_entry__ import host_cpus
+
 pytestmark = pytest.mark.gpu
 
 
@@ -149,7 +151,7 @@ def test_c3_free_time_N20_matches_oracle():
     assert np.abs(o["xopt"][ok][:, :, -1] - b["xref"][ok][:, :, -1]).max() < 1e-7      # terminal equality
     k = 16 if (os.cpu_count() or 1) >= 16 else 3                                        # dense oracle: ~15 s each, one thread per instance
     ref = c_oracle.solve_batch(4, N, b["m"], b["x0"][:k], b["u0"][:k], b["xref"][:k], b["A"][:k], b["b"][:k],
-                               b["Ts"][:k], threads=min(k, os.cpu_count() or 1))
+                               b["Ts"][:k], threads=min(k, host_cpus()))
     n_tight = 0
     for i in range(k):
         assert (ref["status"][i] in (0, 1)) == bool(ok[i])
@@ -171,7 +173,7 @@ def test_c3_gated_N20_matches_the_dense_oracle():
     k = 8 if (os.cpu_count() or 1) >= 8 else 4
     b = sc.make_batch_c3(k, N, gated=True)
     o = run(b, N)
-    ref = c_oracle.solve_batch(6, N, b["m"], b["x0"], b["u0"], b["xref"], b["A"], b["b"], b["Ts"], b["term"], threads=min(k, os.cpu_count() or 1))
+    ref = c_oracle.solve_batch(6, N, b["m"], b["x0"], b["u0"], b["xref"], b["A"], b["b"], b["Ts"], b["term"], threads=min(k, host_cpus()))
     n_tight = 0
     for i in range(k):
         f_ref, f_gpu = ref["status"][i] in (0, 1), o["status"][i] in (0, 1)
@@ -213,7 +215,7 @@ def test_c3_fixed_time_moving_obstacles():
     b2 = sc.make_batch_c3(B2, N2, gated=True)
     o2 = run(b2, N2)
     ref = c_oracle.solve_batch(6, N2, b2["m"], b2["x0"], b2["u0"], b2["xref"], b2["A"], b2["b"], b2["Ts"], b2["term"],
-                               threads=min(B2, os.cpu_count() or 1))
+                               threads=min(B2, host_cpus()))
     n_tight = 0
     for i in range(B2):
         f_ref, f_gpu = ref["status"][i] in (0, 1), o2["status"][i] in (0, 1)
@@ -271,7 +273,7 @@ def test_free_time_half_at_N20_against_the_independent_oracle():
     out = s.solve(b["variant"], b["x0"], b["u0"], b["xref"], b["A"], b["b"], b["Ts"], b["term"], SolverParams())
     torch.cuda.synchronize()
     st, xo, ts = out.status.cpu().numpy(), out.xopt.cpu().numpy(), out.ts_opt.cpu().numpy()
-    ref = ipopt_like.solve_c2_sample(B, N, idx, procs=min(cores, len(idx)), gen="c3free")
+    ref = ipopt_like.solve_c2_sample(B, N, idx, procs=min(host_cpus(), len(idx)), gen="c3free")
     n_ok = 0
     for i, (rst, rts, rf, rx, ru, nres) in zip(idx, ref):
         assert st[i] in (0, 1)
@@ -303,7 +305,7 @@ def test_gated_half_against_the_independent_oracle():
     out = s.solve(b["variant"], b["x0"], b["u0"], b["xref"], b["A"], b["b"], b["Ts"], b["term"], SolverParams())
     torch.cuda.synchronize()
     st, xo, info = out.status.cpu().numpy(), out.xopt.cpu().numpy(), out.info.cpu().numpy()
-    ref = ipopt_like.solve_c2_sample(B, N, idx, procs=min(cores, len(idx)), gen="c3gated", max_iter=400)
+    ref = ipopt_like.solve_c2_sample(B, N, idx, procs=min(host_cpus(), len(idx)), gen="c3gated", max_iter=400)
     n_ok = n_same = 0
     for i, (rst, rts, rf, rx, ru, nres) in zip(idx, ref):
         if rst not in (ipopt_like.OK, ipopt_like.ACCEPTABLE):

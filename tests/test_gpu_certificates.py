@@ -8,19 +8,19 @@ stationarity, primal feasibility, multiplier signs and complementarity, all <= 1
 any solver, an explicit geometric check (car rectangle against every obstacle polygon, Euclidean distance >= dmin - 1e-6)
 runs at the full sizes of BASELINE.json's configs: C2 8192, C3 both halves at 8192 unique seeds, C5 4096 rollouts.
 """
-import os
 
 import numpy as np
 import pytest
 import torch
 
+from __graft_entry__ import host_cpus
 from tests import kkt_check
 from tests.test_oracle_nlp import build
 
 pytestmark = pytest.mark.gpu
 
 TOL = 1e-6
-PROCS = max(1, min(32, (os.cpu_count() or 1) // 2))
+PROCS = max(1, min(32, host_cpus() // 2))
 
 
 def _solve(b, N, mode=None, cert=True):

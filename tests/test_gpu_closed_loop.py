@@ -3,6 +3,8 @@ solver behind obca(), and the batched driver."""
 import numpy as np
 import pytest
 
+from __graft_entry__ import host_cpus
+
 pytestmark = pytest.mark.gpu
 
 
@@ -119,7 +121,7 @@ def test_closed_loop_calls_against_the_independent_oracle():
         bs.close()
     jobs = [(q["variant"], 5, {k: q[k] for k in ("m", "x0", "u0", "xref", "A", "b", "Ts", "term")},
              (sp.Q_free, sp.R_free, sp.P_free) if q["variant"] == 4 else (sp.Q_fix, sp.R_fix, sp.P_fix), box, 300) for q in calls]
-    ref = ipopt_like.solve_calls(jobs, procs=min(cores, 64))
+    ref = ipopt_like.solve_calls(jobs, procs=min(host_cpus(), 64))
     n_ok = n_same = n_better = n_more = 0
     for j, (rst, rf, rx, rts, nres) in enumerate(ref):
         if rst not in (ipopt_like.OK, ipopt_like.ACCEPTABLE):

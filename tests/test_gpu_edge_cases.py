@@ -1,12 +1,12 @@
 """Edge cases of the C ABI on the device: empty and masked batches, argument errors, the compiled size limits, the
 three-box (M=12) sub-configuration of C2, instance skipping."""
 import ctypes
-import os
 
 import numpy as np
 import pytest
 import torch
 
+from __graft_entry__ import host_cpus
 from oracle import c_oracle
 
 pytestmark = pytest.mark.gpu
@@ -145,7 +145,7 @@ def test_c4_total_size_on_one_gpu():
     from vehicle_motion_planning_with_obstacles_avoidance_using_mpc_amd.sharding import shard_bounds
     from vehicle_motion_planning_with_obstacles_avoidance_using_mpc_amd.solver import BatchSolver
     B, world = 65536, 8
-    b = sc.make_batch(B, 5, procs=max(1, min(64, os.cpu_count() or 1)))
+    b = sc.make_batch(B, 5, procs=min(64, host_cpus()))
     assert len(np.unique(b["x0"], axis=0)) == B
     s = BatchSolver(5, b["m"], max_batch=B)
     d = _dev(b)

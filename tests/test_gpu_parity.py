@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 import torch
 
+from __graft_entry__ import host_cpus
 from oracle import ipm_dense
 from oracle.obca_nlp import Problem
 from tests.test_oracle_nlp import build
@@ -129,9 +130,8 @@ def test_batch_matches_oracle_and_is_permutation_invariant():
     assert np.array_equal(out2.xopt.cpu().numpy(), xo[perm])            # bit-exact: no cross-instance coupling
     assert np.array_equal(out2.status.cpu().numpy(), st[perm])
     from oracle import c_oracle
-    import os
     ref = c_oracle.solve_batch(4, N, b["m"], b["x0"], b["u0"], b["xref"], b["A"], b["b"], b["Ts"],
-                               threads=os.cpu_count() or 1)                 # the C restatement, every instance
+                               threads=host_cpus())                 # the C restatement, every instance
     it_gpu = out.iters.cpu().numpy()
     n_tight = 0
     for i in range(B):
@@ -204,7 +204,7 @@ def test_headline_batch_against_the_independent_oracle():
     out = s.solve(b["variant"], b["x0"], b["u0"], b["xref"], b["A"], b["b"], b["Ts"], b["term"], SolverParams())
     torch.cuda.synchronize()
     st, xo, uo, ts, info = (getattr(out, k).cpu().numpy() for k in ("status", "xopt", "uopt", "ts_opt", "info"))
-    ref = ipopt_like.solve_c2_sample(B, N, idx, procs=min(cores, 64))
+    ref = ipopt_like.solve_c2_sample(B, N, idx, procs=min(host_cpus(), 64))
     n_ok = 0
     for i, (rst, rts, rf, rx, ru, nres) in zip(idx, ref):
         assert st[i] in (0, 1)

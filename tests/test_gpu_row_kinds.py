@@ -30,12 +30,12 @@ it, the kernels run another pass of their solve pipeline and do, so where the it
 count minus the oracle's is the number of corrected solves -- never negative, at least one on the witness and in the batch.  And
 iteration counts equal to the oracle's on every instance (the caps are 0) mean every barrier decision, the re-checks after a
 decrease included, and every switching decision went the oracle's way."""
-import os
 
 import numpy as np
 import pytest
 import torch
 
+from __graft_entry__ import host_cpus
 from oracle import c_oracle
 from vehicle_motion_planning_with_obstacles_avoidance_using_mpc_amd import scenarios as sc
 from vehicle_motion_planning_with_obstacles_avoidance_using_mpc_amd.solver import BatchSolver, SolverParams
@@ -99,7 +99,7 @@ def oracle(name):
         b, N, variant, _, _, _ = CASES[name]()
         v = b["variant"] if variant is None else np.full(len(b["variant"]), variant, np.int32)
         ref = c_oracle.solve_batch(v, N, b["m"], b["x0"], b["u0"], b["xref"], b["A"], b["b"], b["Ts"], b["term"],
-                                   threads=min(len(v), os.cpu_count() or 1))
+                                   threads=min(len(v), host_cpus()))
         _oracle_cache[name] = (b, N, v, ref)
     return _oracle_cache[name]
 

@@ -5,6 +5,8 @@ import os
 import numpy as np
 import pytest
 
+from __graft_entry__ import host_cpus
+
 pytestmark = pytest.mark.gpu
 
 
@@ -35,7 +37,7 @@ def test_other_orders_match_the_oracle_and_the_default_optima(order, iters_vs_de
     np.testing.assert_allclose(xo, x0, rtol=0, atol=1e-5)
     # and the oracle with the same option follows the same iterates
     ref = c_oracle.solve_batch(4, N, b["m"], b["x0"], b["u0"], b["xref"], b["A"], b["b"], b["Ts"],
-                               params=c_oracle.default_params(start_order=order), threads=os.cpu_count() or 1)
+                               params=c_oracle.default_params(start_order=order), threads=host_cpus())
     assert np.array_equal(ref["status"], st)
     same = ref["iters"] == it
     assert same.mean() > 0.9

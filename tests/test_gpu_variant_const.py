@@ -26,12 +26,12 @@ What each case is there for:
                obca_mpc4 converge with elastic variables left, which is what its penalty escalation answers (the oracle: infeasible
                after ~650 iterations on each; the iteration counts differ from the kernels', the class may not).
   handle       one handle, one set of buffers: obca_mpc4, then obca_mpc8, then obca_mpc4 again gives the first call's words."""
-import os
 
 import numpy as np
 import pytest
 import torch
 
+from __graft_entry__ import host_cpus
 import test_gpu_row_kinds as g
 import test_gpu_shapes as gs
 from oracle import c_oracle
@@ -83,7 +83,7 @@ def _oracle(key, b, N, v, **prm):
     if key not in _cache:
         p = c_oracle.default_params(**prm)
         _cache[key] = c_oracle.solve_batch(v, N, b["m"], b["x0"], b["u0"], b["xref"], b["A"], b["b"], b["Ts"], b["term"], params=p,
-                                           threads=min(len(v), os.cpu_count() or 1))
+                                           threads=min(len(v), host_cpus()))
     return _cache[key]
 
 

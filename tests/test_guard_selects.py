@@ -30,7 +30,7 @@ GUARDS = ("lower slack", "upper slack", "p", "n", "zL", "zU", "zp", "zn")
 
 @functools.lru_cache(maxsize=None)
 def host():
-    lib = native_build.build_shim("step_guards_host", [SRC], native_build.DEPS + [SRC], openmp=True)
+    lib = native_build.build_shim("step_guards_host", [SRC], openmp=True)
     lib.step_guards_solve_batch.restype = ctypes.c_int
     return lib
 

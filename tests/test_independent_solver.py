@@ -7,16 +7,16 @@ image allows.  Two questions per instance:
       problems it does from every start; the fixed-time problems are non-convex enough that some starts end elsewhere --
       the shares are reported (bench.py prints them as `independent_solver`) and bounded here.
 CPU part: the structured core on the host (same code as the lane kernel).  `-m gpu` part: the HIP kernels."""
-import os
 
 import numpy as np
 import pytest
 
+from __graft_entry__ import host_cpus
 from tests import independent as ind, kkt_check, native_build
 from tests.test_oracle_nlp import build
 from vehicle_motion_planning_with_obstacles_avoidance_using_mpc_amd import scenarios as sc
 
-PROCS = max(1, min(128, (os.cpu_count() or 1)))
+PROCS = min(128, host_cpus())
 
 
 def _check(jobs_polish, jobs_starts, what, max_better=0.0, min_same=0.0):

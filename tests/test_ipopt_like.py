@@ -8,6 +8,7 @@ import warnings
 import numpy as np
 import pytest
 
+from __graft_entry__ import host_cpus
 from oracle import ipm_dense, ipopt_like
 from tests.test_oracle_ipm import KNOWN, by_name
 from tests.test_oracle_nlp import build
@@ -100,13 +101,12 @@ def test_headline_workload_agrees_with_the_independent_oracle():
     algorithm from the reference's literal zero start (hard equalities, restoration phase: 1-8 restorations per solve) and the product's
     method (structured core: l1-elastic form, window start) end at the same point -- Ts_opt to 2e-7 s, every pose to 1e-6 m.  The free-time
     problem has one optimum on this workload; neither method shares code or formulation with the other."""
-    import os
     from tests import native_build
     from vehicle_motion_planning_with_obstacles_avoidance_using_mpc_amd import scenarios as sc
     B, N, idx = 64, 5, list(range(12))
     b = sc.make_batch(B, N)
     g = native_build.lpi_solve(b["variant"], N, b["m"], b["x0"], b["u0"], b["xref"], b["A"], b["b"], b["Ts"], b["term"])
-    ref = ipopt_like.solve_c2_sample(B, N, idx, procs=min(4, os.cpu_count() or 1))
+    ref = ipopt_like.solve_c2_sample(B, N, idx, procs=min(4, host_cpus()))
     assert sum(r[5] for r in ref) >= len(idx)                        # the oracle did go through its restoration phase
     for i, (st, ts, f, xo, uo, nres) in zip(idx, ref):
         assert st == ipopt_like.OK and g["status"][i] == 0
@@ -119,13 +119,12 @@ def test_headline_workload_agrees_with_the_independent_oracle():
 def test_c3_free_time_shape_agrees_with_the_independent_oracle():
     """the C3 generator's free-time half at N = 12 (three obstacles, 430 rows), two seeded instances: the independent oracle from the
     zero start and the product's structured core end at the same optimum (N = 20 runs on the GPU box: tests/test_gpu_c3.py)"""
-    import os
     from tests import native_build
     from vehicle_motion_planning_with_obstacles_avoidance_using_mpc_amd import scenarios as sc
     B, N, idx = 8, 12, [1, 2]
     b = sc.make_batch_c3(B, N, gated=False)
     g = native_build.lpi_solve(b["variant"], N, b["m"], b["x0"], b["u0"], b["xref"], b["A"], b["b"], b["Ts"], b["term"])
-    ref = ipopt_like.solve_c2_sample(B, N, idx, procs=min(2, os.cpu_count() or 1), gen="c3free")
+    ref = ipopt_like.solve_c2_sample(B, N, idx, procs=min(2, host_cpus()), gen="c3free")
     for i, (st, ts, f, xo, uo, nres) in zip(idx, ref):
         assert st == ipopt_like.OK and g["status"][i] == 0
         assert g["ts_opt"][i] == pytest.approx(ts, abs=1e-6)

@@ -27,8 +27,6 @@ SHAPES = [(5, 2, 2), (5, 3, 6), (5, 4, 10), (5, 5, 14), (5, 6, 18), (6, 2, 2), (
 VARIANTS = (4, 6, 8)
 NT = 64
 SRC = os.path.join(native_build.HERE, "native", "mu_entry_host.cpp")
-DEPS = [SRC, os.path.join(native_build.CSRC, "obca_lpi_core.h"), os.path.join(native_build.CSRC, "obca_device.h"),
-        os.path.join(native_build.ROOT, "include", "obca_mpc.h")]
 
 # case of tests/test_gpu_row_kinds.py -> instance (found on the host with the Python oracle over the 32 instances of each case)
 WITNESS = {"s5_3_6_mpc4": 11, "s5_3_6_mpc6": 21, "s5_3_6_mpc8": 30, "s6_3_6": 4, "s5_2_2": 16, "s5_5_14_mpc6": 27}
@@ -37,7 +35,7 @@ BACKTRACKS = ("s5_3_6_mpc4", "s5_3_6_mpc6", "s5_3_6_mpc8", "s5_2_2", "s5_5_14_mp
 
 @functools.lru_cache(maxsize=None)
 def host():
-    return native_build.build_shim("mu_entry_host", [SRC], DEPS)
+    return native_build.build_shim("mu_entry_host", [SRC])
 
 
 def run_time_entries(N, nO, M, variant):

@@ -19,9 +19,7 @@ from vehicle_motion_planning_with_obstacles_avoidance_using_mpc_amd.closed_loop 
 from vehicle_motion_planning_with_obstacles_avoidance_using_mpc_amd.demo_setting import problemSetting
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 SRC = os.path.join(HERE, "native", "plan_refine_host.cpp")
-DEPS = [SRC, os.path.join(ROOT, "vehicle_motion_planning_with_obstacles_avoidance_using_mpc_amd", "csrc", "obca_refine_core.h")]
 E_INVAL = -22
 SHAPES = [(2, 2), (5, 1), (3, 4), (13, 5)]           # (N, ratio)
 FILL_X, FILL_I = -777.25, -777
@@ -32,7 +30,7 @@ def _p(a):
 
 
 def load_host():
-    lib = native_build.build_shim("plan_refine_host", [SRC], DEPS)
+    lib = native_build.build_shim("plan_refine_host", [SRC])
     lib.plan_refine_host.restype = ctypes.c_int
     return lib
 

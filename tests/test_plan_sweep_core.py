@@ -16,14 +16,13 @@ from vehicle_motion_planning_with_obstacles_avoidance_using_mpc_amd.model_obstac
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "native", "plan_sweep_host.cpp")
-DEPS = [SRC] + core.DEPS[1:]
 EGO = core.EGO
 TOL = 1e-9
 M3 = [1, 2, 4]                    # a half-plane, a wedge and a box
 
 
 def load_host():
-    lib = native_build.build_shim("plan_sweep_host", [SRC], DEPS)
+    lib = native_build.build_shim("plan_sweep_host", [SRC])
     lib.plan_sweep_host.restype = ctypes.c_int
     lib.plan_sweep_host_move.restype = ctypes.c_double
     return lib

@@ -17,14 +17,13 @@ from tests import test_plan_sweep_core as sweep_core
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "native", "plan_tighten_host.cpp")
-DEPS = [SRC] + core.DEPS[1:]
 EGO = core.EGO
 TOL = 1e-9
 _p = core._p
 
 
 def load_host():
-    lib = native_build.build_shim("plan_tighten_host", [SRC], DEPS)
+    lib = native_build.build_shim("plan_tighten_host", [SRC])
     lib.plan_tighten_host.restype = ctypes.c_int
     return lib
 

@@ -17,10 +17,7 @@ from vehicle_motion_planning_with_obstacles_avoidance_using_mpc_amd.rollouts imp
 from vehicle_motion_planning_with_obstacles_avoidance_using_mpc_amd.scenarios import make_world_c5
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 SRC = os.path.join(HERE, "native", "rollout_swept_host.cpp")
-CSRC = os.path.join(ROOT, "vehicle_motion_planning_with_obstacles_avoidance_using_mpc_amd", "csrc")
-DEPS = native_build.DEPS + [SRC, os.path.join(HERE, "native", "rollout_stop_host.cpp"), os.path.join(CSRC, "obca_audit_core.h")]
 DMIN = 0.05                       # c_oracle.default_params / SolverParams
 TAU = 1e-6 + 1e-8                 # obca_params defaults: feas_tol (elastic variables) + tol (row residuals)
 N_SUB = 16
@@ -30,7 +27,7 @@ GUARANTEE_WORLDS = 16
 @pytest.fixture(scope="module")
 def host():
     """the shim in its own library"""
-    lib = native_build.build_shim("rollout_swept_host", [SRC], DEPS, openmp=True)
+    lib = native_build.build_shim("rollout_swept_host", [SRC], openmp=True)
     for f in ("rollout_stop_host_run", "rollout_swept_host_run", "rollout_swept_host_harness", "rollout_swept_host_rows_batch"):
         getattr(lib, f).restype = ctypes.c_int
     return lib

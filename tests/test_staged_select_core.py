@@ -18,7 +18,6 @@ from tests import kkt_check, native_build, test_scene_core as tsc
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "native", "staged_select_host.cpp")
-DEPS = [SRC] + tsc.DEPS[1:]
 E_INVAL = tsc.E_INVAL
 _p = tsc._p
 words = tsc.words
@@ -26,7 +25,7 @@ OUT = ("score", "sel", "A", "b", "variant_out", "ok", "min_clear")
 
 
 def load_host():
-    lib = native_build.build_shim("staged_select_host", [SRC], DEPS)
+    lib = native_build.build_shim("staged_select_host", [SRC])
     lib.scene_select_staged_host.restype = ctypes.c_int
     return lib
 

@@ -27,15 +27,13 @@ TOL_MIRROR = 1e-9                   # tests/test_lpi_core_cpu.py: TOL_SAME_PATH 
 TOL_ON_BOUND = 1e-9                 # |ts_opt - Tmax Ts| of an answer held on the bound (the dense oracle: 2e-11)
 E_INVAL = -22
 SRC = os.path.join(native_build.HERE, "native", "time_bound_host.cpp")
-DEPS = [SRC, os.path.join(native_build.CSRC, "obca_lpi_core.h"), os.path.join(native_build.CSRC, "obca_device.h"),
-        os.path.join(native_build.ROOT, "include", "obca_mpc.h")]
 DESCENDING_SEEDS = [2, 6, 8, 9]     # loop_world(seed, 0) whose first window runs towards smaller y
 LEFT_OUT_SEEDS = [2, 6, 8, 9, 11, 12, 13, 14]     # tests/test_gpu_pool_loop.py: the seeds POOL_SEEDS leaves out
 
 
 @functools.lru_cache(maxsize=None)
 def load_host():
-    lib = native_build.build_shim("time_bound_host", [SRC], DEPS, openmp=True)
+    lib = native_build.build_shim("time_bound_host", [SRC], openmp=True)
     lib.time_bound_host_tmax.restype = ctypes.c_double
     lib.time_bound_host_tmax.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_double]
     lib.time_bound_host_resolve.restype = ctypes.c_int

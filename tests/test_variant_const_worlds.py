@@ -5,11 +5,11 @@ The stated rule: of the first worlds of the gated C3 generator (tests/test_gpu_s
 32 on which the dense C oracle and the structured host core (csrc/obca_lpi_core.h through tests/native) -- two CPU
 implementations of one rule -- both converge, take the same number of iterations and end within 1e-10 of each other.  And the
 reason for picking at all: on the worlds left out the two differ by more than the 1e-9 of the GPU test's rule."""
-import os
 
 import numpy as np
 import pytest
 
+from __graft_entry__ import host_cpus
 import test_gpu_shapes as gs
 import test_gpu_variant_const as vc
 from oracle import c_oracle
@@ -23,7 +23,7 @@ def test_the_listed_worlds_are_the_first_on_which_the_cpu_implementations_agree(
     b = gs._batch(5, nO, POOL)
     v = np.full(POOL, 4, np.int32)
     args = (5, b["m"], b["x0"], b["u0"], b["xref"], b["A"], b["b"], b["Ts"], b["term"])
-    ref = c_oracle.solve_batch(v, *args, threads=min(POOL, os.cpu_count() or 1))
+    ref = c_oracle.solve_batch(v, *args, threads=min(POOL, host_cpus()))
     host = native_build.lpi_solve(v, *args)
     ok = np.isin(ref["status"], (0, 1)) & np.isin(host["status"], (0, 1)) & (host["iters"] == ref["iters"])
     dev = np.array([max(np.abs(host["xopt"][i] - ref["xopt"][i]).max(), np.abs(host["uopt"][i] - ref["uopt"][i]).max(),

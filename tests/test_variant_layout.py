@@ -27,14 +27,12 @@ FIELDS = ("r_init", "r_dyn", "r_term", "r_xb", "r_ub", "r_acc", "r_T", "r_tx", "
 KINDS = ("init", "dyn", "term", "xb", "ub", "acc", "T", "tx", "norm", "dist", "lam", "mu")      # bit k of a kind mask
 MU = 1 << KINDS.index("mu")
 SRC = os.path.join(native_build.HERE, "native", "variant_layout_host.cpp")
-DEPS = [SRC, os.path.join(native_build.CSRC, "obca_lpi_core.h"), os.path.join(native_build.CSRC, "obca_device.h"),
-        os.path.join(native_build.ROOT, "include", "obca_mpc.h")]
 ids = lambda s: "s%d_%d_%d" % s
 
 
 @functools.lru_cache(maxsize=None)
 def host():
-    return native_build.build_shim("variant_layout_host", [SRC], DEPS)
+    return native_build.build_shim("variant_layout_host", [SRC])
 
 
 @pytest.fixture(scope="module")

@@ -11,6 +11,7 @@ import time
 import numpy as np
 
 sys.path.insert(0, ".")
+from __graft_entry__ import host_cpus  # noqa: E402
 
 
 def candidates_job(job):
@@ -44,8 +45,9 @@ if __name__ == "__main__":
     if fails:
         import multiprocessing as mp
         from tools.c5_heldout_failures import candidates_job as job          # (importable name for the spawned workers)
+        procs = min(len(fails), 64, host_cpus())                            # read before the workers' thread count caps it
         os.environ["OMP_NUM_THREADS"] = os.environ["OPENBLAS_NUM_THREADS"] = "1"
-        with mp.get_context("spawn").Pool(max(1, min(len(fails), 64, os.cpu_count() or 1))) as pool:
+        with mp.get_context("spawn").Pool(procs) as pool:
             rows = pool.map(job, [(int(f[0]), 2) for f in fails])
     print(json.dumps(dict(first=first, B=B, steps_per_s=res["value"], stopped=res["rollouts_stopped_infeasible"], split=split, further_starts=rows,
                           seconds=time.time() - t0)))

@@ -2,9 +2,7 @@
 OBCA_DODGE_LEVEL1_MU; host build of the structured core compiled with -DOBCA_DODGE_LEVEL1_MU=0.1 into a scratch library)?  The
 reference-held runs that use the rung -- demo11 (Figure 11's titles, the GIF's markers) and demo1 (Figure 12) -- replayed with it.
     python tools/dodge_mu_study.py [mu]"""
-import ctypes
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -13,12 +11,9 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from tests import native_build, reference_report  # noqa: E402
 
 mu = sys.argv[1] if len(sys.argv) > 1 else "0.1"
-out = "/tmp/libnative_host_dodgemu.so"
-subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fopenmp", "-Wno-unknown-pragmas", "-DOBCA_DODGE_LEVEL1_MU=" + mu,
-                native_build.SRC, "-o", out], check=True)
-for name, lib in (("product (mu 1)", None), ("first level at mu " + mu, out)):
-    if lib:
-        native_build._lib = ctypes.CDLL(lib)
+for name, study in (("product (mu 1)", False), ("first level at mu " + mu, True)):
+    if study:
+        native_build._lib = native_build.build_shim("native_host_dodgemu", [native_build.SRC], openmp=True, defines=["OBCA_DODGE_LEVEL1_MU=" + mu])
     fx = reference_report.fixture()
     gif = reference_report.gif_demo11()
     for which, st, key in (("demo11", reference_report.demo11_setting(), "figure11_demo11"), ("demo1", reference_report.demo1_setting(), "figure12_demo1")):

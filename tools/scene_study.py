@@ -45,7 +45,7 @@ def kernel_of(N, n, solver):
     """auto mode's kernel for the shape, by the selection header's own rule, and what the handle says about instantiations"""
     import ctypes
     from tests import native_build, test_select_core as sel
-    lib = native_build.build_shim("select_host", [sel.SRC], sel.DEPS)
+    lib = native_build.build_shim("select_host", [sel.SRC])
     lib.select_kernel_name.restype = ctypes.c_char_p
     p = sel.plan(lib, (N, n, 4 * n))
     return {"kernel_generic": p["kernel"], "specialised": bool(solver.specialised), "lds_bytes": int(solver.lds_bytes)}
