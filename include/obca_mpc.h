@@ -996,9 +996,76 @@ struct obca_pool_tracks {
 void obca_pool_tracks_init(struct obca_pool_tracks* d);
 int obca_pool_tracks(const struct obca_pool_tracks* d, int32_t measure, int32_t device, void* hip_stream);
 
+/* ------------------------------------------------------------------------------------------------------
+ * Open-loop plans among timed tracks, on the device: a batch of plans measured against the TRACKS THEMSELVES.
+ * obca_pool_tracks measures the one interval a closed loop has just driven, and obca_scene_select_staged scores a plan against
+ * rows interpolated entry by entry between two stage times -- which cannot show an obstacle whose track has knots between two
+ * stage times and moves in and out of the lane there.  This call samples the N intervals of a plan as obca_scene_select does
+ * and puts the track's own rectangle at the track's pose at every sample's time; given obca_scene_select_staged's score it
+ * folds what it measured into the running minimum that call re-ranks on (accumulate = 1), so a staged select -> solve ->
+ * measure -> re-select loop takes a tracked obstacle in on the track's word.  It has no handle;
+ * csrc/obca_plan_tracks_core.h holds the serial definition the kernel reproduces.
+ *
+ * Bt = B / group track blocks, plan b reads block b / group; track j of a block is score slot K - Kt + j.
+ *   track_state   [B,Kt], written for every plan: obca_pool_tracks' rule, word for word -- 0 where track_len == 0, 1 where the
+ *                 track is usable, -1 otherwise -- the plan's own time words being dt[b] finite and > 0 and t0[b] finite.  A
+ *                 length outside 1 .. L is never used as an index, no knot is read before the length word and the rectangle
+ *                 have passed their check, and nothing read from a track that is not in state 1 reaches an output.
+ *   times         knot kk of plan b is at t0[b] + (double)kk dt[b] (one product, one sum, each rounded on its own): the word
+ *                 obca_pool_tracks forms for stage kk with k = 0 and Ts = dt, so a plan's knot time and the time of the stage
+ *                 row it was solved against are one word.  A caller measuring an obca_mpc4 plan passes dt = Ts * ts_opt.
+ *   samples       obca_scene_select's: x0[b], where given, at knot 0's time; then for every interval s -> s + 1 the n_sub + 1
+ *                 samples j = 0 .. n_sub, the car's pose interpolated as obca_plan_sweep interpolates and the time interpolated
+ *                 alike between the two knot times.  A sample whose car pose is not finite is skipped.  The obstacle at a sample
+ *                 is the margin-free rectangle track_size (in ego's convention) at obca_pool_tracks' pose of the track at the
+ *                 sample's time: the track itself, across knots and turning.  The distance is the signed distance between the
+ *                 car's footprint (ego) and obca_fleet_step's four rows of that rectangle, as obca_pool_tracks measures.
+ *   measured      a plan with variant[b] != 0 and status[b] 0 or 1 (obca_scene_select's accumulate rule); a NULL variant or
+ *                 status: every plan.
+ *   track_clear   [B,Kt]: this call's smallest distance to track j, +inf for a slot not in state 1
+ *   track_min     [B]: the smallest word of track_clear[b,:], +inf where no track is usable
+ *   score         [B,K] or NULL: a measured plan gets score[b,K-Kt+j] = min(score[b,K-Kt+j], track_clear[b,j]) for every
+ *                 usable j (an old word that is no number is replaced, as obca_scene_select does).  Slots 0 .. K-Kt-1 are
+ *                 never touched.
+ * A plan that was not measured, has no finite sample pose, or met a distance that is no number (overflow) gets NaN in
+ * track_clear[b,:] and track_min[b], and its score row is untouched: the call never turns "unknown" into "safe".
+ * B >= 1, 1 <= Kt <= K <= 64 (K is read only for score), 1 <= N <= 127, 1 <= L <= 4096, group >= 1 and B % group == 0,
+ * 1 <= n_sub <= 256, far > 0 and ego finite, struct_size == sizeof(struct obca_plan_tracks), device >= 0, no pointer NULL but
+ * t0 (NULL: 0 for every plan), x0, variant, status and score.  Every argument is checked before the first HIP call; a refused
+ * call (OBCA_E_INVAL) has no side effect.  Asynchronous on hip_stream. */
+struct obca_plan_tracks {
+    uint32_t struct_size;              /* sizeof(struct obca_plan_tracks): set by obca_plan_tracks_init() */
+    uint32_t reserved_;
+    int32_t B, K, Kt, N, L, group, n_sub, reserved2_;
+    double far;                        /* obca_plan_tracks_init: 100 (the spares' place; no word of this call depends on it) */
+    double ego[4];                     /* the car's footprint; obca_plan_tracks_init: 1.7, 0.75, 1.7, 0.75 */
+    /* read-only, Bt = B / group */
+    const double* track_x;             /* [Bt,Kt,L,3] poses (x, y, heading) */
+    const double* track_t;             /* [Bt,Kt,L] */
+    const int32_t* track_len;          /* [Bt,Kt] */
+    const double* track_size;          /* [Bt,Kt,4] in ego's convention */
+    const double* t0;                  /* [B] or NULL */
+    const double* dt;                  /* [B] the time between two knots of the plan */
+    const double* x;                   /* [B,3,N+1] the plans */
+    const double* x0;                  /* [B,3] or NULL */
+    const int32_t* variant;            /* [B] or NULL */
+    const int32_t* status;             /* [B] or NULL */
+    /* in and out */
+    double* score;                     /* [B,K] or NULL: slots K-Kt .. K-1 folded */
+    /* written */
+    double* track_clear;               /* [B,Kt] */
+    double* track_min;                 /* [B] */
+    int32_t* track_state;              /* [B,Kt] */
+};   /* no typedef: the call has the descriptor's name, so C and C++ say `struct obca_plan_tracks` */
+
+/* zero-fills *d and sets struct_size, far and ego: the one way to start filling an obca_plan_tracks */
+void obca_plan_tracks_init(struct obca_plan_tracks* d);
+int obca_plan_tracks(const struct obca_plan_tracks* d, int32_t device, void* hip_stream);
+
 const char* obca_strerror(int code);
 /* "obca_mpc 0.18 (gfx950)" -- the string still reads 0.18: 0.19 and 0.20 add calls and change no existing word, and callers
- * detect them by the exported symbols obca_fleet_tracks / obca_scene_select_staged and obca_pool_tracks.
+ * detect them by the exported symbols obca_fleet_tracks / obca_scene_select_staged and obca_pool_tracks.  Plans measured
+ * against timed tracks (obca_plan_tracks) came after 0.20 in the same way: detect the call by its symbol.
  * 0.20 = obstacles on timed tracks (obca_pool_tracks);
  * 0.19 = fleet prediction by plans (obca_fleet_tracks, obca_scene_select_staged);
  * 0.18 = fleet closed loop (obca_fleet_step);

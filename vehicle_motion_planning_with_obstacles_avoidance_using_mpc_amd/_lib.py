@@ -144,6 +144,15 @@ class ObcaPoolTracks(Descriptor):
     DEFAULTS = ("clearance", "far", "ego")
 
 
+class ObcaPlanTracks(Descriptor):
+    """obca_plan_tracks (include/obca_mpc.h), the descriptor of the call of that name.  A new instance is what
+    obca_plan_tracks_init leaves: all zero (t0, x0, variant, status and score NULL), struct_size set, far 100, the default ego."""
+    _fields_ = Descriptor.members(("B", "K", "Kt", "N", "L", "group", "n_sub", "reserved2_"), ("far", "ego"),
+                                  ("track_x", "track_t", "track_len", "track_size", "t0", "dt", "x", "x0", "variant", "status", "score",
+                                   "track_clear", "track_min", "track_state"))
+    DEFAULTS = ("far", "ego")
+
+
 EXPORTS = ("obca_create", "obca_destroy", "obca_solve_batch", "obca_lds_bytes", "obca_strerror", "obca_version", "obca_params_init",
            "obca_set_profile_buffer", "obca_set_mode", "obca_set_two_sided_sweep", "obca_rollouts_create", "obca_rollouts_destroy", "obca_rollouts_debug_stats", "obca_rollouts_debug_harness",
            "obca_rollouts_reset", "obca_rollouts_step", "obca_rollouts_read", "obca_rollouts_run",
@@ -153,7 +162,7 @@ EXPORTS = ("obca_create", "obca_destroy", "obca_solve_batch", "obca_lds_bytes", 
            "obca_rollouts_read_clearance", "obca_rollouts_set_swept_rows", "obca_moving_rows_batch", "obca_plan_refine",
            "obca_grid_dilate_batch", "obca_route_resample", "obca_scene_select", "obca_grid_pool", "obca_pool_loop_init", "obca_pool_loop_advance",
            "obca_fleet_init", "obca_fleet_step", "obca_fleet_tracks_init", "obca_fleet_tracks", "obca_scene_select_staged",
-           "obca_pool_tracks_init", "obca_pool_tracks")
+           "obca_pool_tracks_init", "obca_pool_tracks", "obca_plan_tracks_init", "obca_plan_tracks")
 
 OBCA_MAX_DYN = 4
 RUN, DONE_GOAL, DONE_CAP, DONE_FAILED, DONE_COLLISION = 0, 1, 2, 3, 4
@@ -310,6 +319,10 @@ def load():
     lib.obca_pool_tracks_init.restype = None
     lib.obca_pool_tracks.argtypes = [ctypes.POINTER(ObcaPoolTracks), ctypes.c_int32, ctypes.c_int32, vp]
     lib.obca_pool_tracks.restype = ctypes.c_int
+    lib.obca_plan_tracks_init.argtypes = [ctypes.POINTER(ObcaPlanTracks)]
+    lib.obca_plan_tracks_init.restype = None
+    lib.obca_plan_tracks.argtypes = [ctypes.POINTER(ObcaPlanTracks), ctypes.c_int32, vp]
+    lib.obca_plan_tracks.restype = ctypes.c_int
     lib.obca_lds_bytes.argtypes = [ctypes.POINTER(ObcaDims)]
     lib.obca_lds_bytes.restype = ctypes.c_int64
     lib.obca_strerror.argtypes = [ctypes.c_int]

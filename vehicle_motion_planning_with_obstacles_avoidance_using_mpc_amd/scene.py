@@ -24,7 +24,11 @@ the other cars of the world into the last V pool slots of each car and measures 
 obca_scene_select_staged.  ``TrackLoop`` gives a world obstacles that follow timed tracks -- recorded or scripted road users
 that turn, brake, stop or set off later: after every step obca_pool_tracks (csrc/obca_pool_tracks_core.h) writes the last Kt pool
 slots from the tracks' poses now, their rows at the stage times of the next solve for obca_scene_select_staged, and measures what
-the car kept from the tracks themselves.  Not here: the reference's 4 -> 6 -> 8 dispatch, its lidar gate and its fixed-time reference preparation
+the car kept from the tracks themselves.  ``solve_tracks`` is ``solve_scene`` among such obstacles, for whole plans: ``track_rows``
+gives the stage rows of an open-loop solve, ``plan_track_clearance`` (obca_plan_tracks, csrc/obca_plan_tracks_core.h) measures a
+batch of plans against the tracks themselves -- the track's own rectangle at its own pose at every sample's time, which rows
+interpolated between two stage times cannot show -- and folds that into the running minimum the staged ``select`` re-ranks on.
+Not here: the reference's 4 -> 6 -> 8 dispatch, its lidar gate and its fixed-time reference preparation
 (``rollouts.DeviceRollouts`` has those, for at most 8 static obstacles).
 """
 import ctypes
@@ -442,6 +446,238 @@ def _with_spare_slots(solver, B, pool_A, pool_b, pool_v, n, far, what):
     full_b = torch.cat([sb, spare_b.expand(B, n, 4)], dim=1).contiguous()
     full_v = torch.cat([sv, torch.zeros(B, n, 2, dtype=torch.float64, device=dev)], dim=1).contiguous()
     return full_A, full_b, full_v, Ks
+
+
+class _OnDevice:
+    """what ``_with_spare_slots`` asks of a solver, for a caller that has none: a device and ``BatchSolver._dev``'s check"""
+
+    def __init__(self, device):
+        self.device = device
+
+    def _dev(self, t, shape, dtype=None):
+        import torch
+        t = torch.as_tensor(t, dtype=dtype or torch.float64, device=self.device).contiguous()
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError("expected shape %s, got %s" % (tuple(shape), tuple(t.shape)))
+        return t
+
+
+def _tracks_on_device(tracks, track_t, track_len, track_size, ego, dev):
+    """tracks [Bt,Kt,L,3], track_t [Bt,Kt,L], track_len [Bt,Kt] and track_size [Bt,Kt,4] (None: ``ego``'s) as contiguous device
+    tensors.  Tracks given as host arrays go through ``check_tracks`` and an unusable one raises; device tensors are taken at
+    their word."""
+    import numpy as np
+    import torch
+    on_host = lambda a: not (isinstance(a, torch.Tensor) and a.is_cuda)
+    shape = tuple(np.shape(tracks) if on_host(tracks) else tracks.shape)
+    if len(shape) != 4 or shape[3] != 3 or shape[1] < 1 or shape[2] < 1:
+        raise ValueError("expected tracks [Bt,Kt,L,3], got %s" % (shape,))
+    Bt, Kt, L = shape[:3]
+    if track_size is None:
+        track_size = np.tile(np.asarray(ego, float), (Bt, Kt, 1))
+    for a, want in ((track_t, (Bt, Kt, L)), (track_len, (Bt, Kt)), (track_size, (Bt, Kt, 4))):
+        got = tuple(np.shape(a) if on_host(a) else a.shape)
+        if got != want:
+            raise ValueError("expected shape %s next to tracks %s, got %s" % (want, shape, got))
+    if all(on_host(a) for a in (tracks, track_t, track_len, track_size)):
+        check_tracks(tracks, track_t, track_len, track_size)
+    f64 = lambda a: torch.as_tensor(a, dtype=torch.float64, device=dev).contiguous()
+    return f64(tracks), f64(track_t), torch.as_tensor(track_len, dtype=torch.int32, device=dev).contiguous(), f64(track_size)
+
+
+def plan_track_clearance(x, tracks, track_t, track_len, dt, track_size=None, t0=None, x0=None, variant=None, status=None, group=1,
+                         n_sub=16, score=None, ego=DEFAULT_EGO, device=None):
+    """obca_plan_tracks: plans x [B,3,N+1] measured against timed tracks themselves -- at every sample the track's own rectangle at
+    the track's pose at the sample's time, across knots and turning, where ``select``'s staged score rests on rows interpolated
+    between two stage times.  tracks [Bt,Kt,L,3], track_t [Bt,Kt,L], track_len [Bt,Kt], track_size [Bt,Kt,4] (None: ``ego``'s) as
+    ``TrackLoop`` takes them, plan b of B = Bt * group reading block b // group; host arrays are checked (``check_tracks``) and an
+    unusable track raises, device tensors are taken at their word (track_state -1).  dt [B] or a float is the time between two
+    knots of a plan (a plan of obca_mpc4: Ts * ts_opt), t0 [B], a float or None the time of knot 0: knot kk is at t0 + kk dt,
+    the word ``pool_tracks`` forms for stage kk with k = 0 and Ts = dt.  x0 [B,3] or None is one more pose at knot 0's time.
+    The samples are ``select``'s: n_sub + 1 per interval.  variant [B] / status [B], each or None: only plans with variant != 0
+    and status 0 / 1 are measured.
+
+    ``score``: a contiguous float64 device tensor [B,K], K >= Kt -- ``select``'s state["score"] for pools whose last Kt slots are
+    the tracks -- whose slots K - Kt .. K - 1 are folded IN PLACE to min(score, track_clear) for every measured plan and usable
+    track: the running minimum the next staged ``select(..., state=state)`` re-ranks on.
+
+    Returns a dict of device tensors on the current stream, no host synchronisation: track_clear [B,Kt] (the smallest distance to
+    every track; +inf for a slot that is no usable track), track_min [B] (their minimum), both NaN for a plan that was not
+    measured, has no finite pose or met a distance that is no number, and track_state [B,Kt] int32 (1 usable, 0 a length of 0,
+    -1 not usable)."""
+    import torch
+    _lib.require_gpu("scene.plan_track_clearance")
+    dev = _dev_of(device, x, tracks)
+    tracks, track_t, track_len, track_size = _tracks_on_device(tracks, track_t, track_len, track_size, ego, dev)
+    Bt, Kt, L = (int(v) for v in tracks.shape[:3])
+    x = torch.as_tensor(x, dtype=torch.float64, device=dev).contiguous()
+    group = int(group)
+    if x.dim() != 3 or x.shape[1] != 3 or group < 1 or int(x.shape[0]) != Bt * group:
+        raise ValueError("expected x [B,3,N+1] with B = %d track blocks * group = %d, got %s" % (Bt, group, tuple(x.shape)))
+    B, N1 = int(x.shape[0]), int(x.shape[2])
+
+    def opt(a, shape, dt_=torch.float64):
+        if a is None:
+            return None
+        a = torch.as_tensor(a, dtype=dt_, device=dev)
+        a = a.expand(shape).contiguous() if a.dim() == 0 else a.contiguous()
+        if tuple(a.shape) != shape:
+            raise ValueError("expected shape %s, got %s" % (shape, tuple(a.shape)))
+        return a
+    dt, t0, x0 = opt(dt, (B,)), opt(t0, (B,)), opt(x0, (B, 3))
+    variant, status = opt(variant, (B,), torch.int32), opt(status, (B,), torch.int32)
+    K = Kt
+    if score is not None:
+        if not (isinstance(score, torch.Tensor) and score.device == dev and score.dtype == torch.float64 and score.is_contiguous() and
+                score.dim() == 2 and score.shape[0] == B and score.shape[1] >= Kt):
+            raise ValueError("score is folded in place: a contiguous float64 tensor [B,K] on %s with K >= Kt = %d" % (dev, Kt))
+        K = int(score.shape[1])
+    out = {"track_clear": torch.empty(B, Kt, dtype=torch.float64, device=dev),
+           "track_min": torch.empty(B, dtype=torch.float64, device=dev),
+           "track_state": torch.empty(B, Kt, dtype=torch.int32, device=dev)}
+    ins = dict(track_x=tracks, track_t=track_t, track_len=track_len, track_size=track_size, t0=t0, dt=dt, x=x, x0=x0, variant=variant,
+               status=status)
+    d = _lib.ObcaPlanTracks().set(B=B, K=K, Kt=Kt, N=N1 - 1, L=L, group=group, n_sub=int(n_sub), ego=ego, score=score, **ins, **out)
+    _lib.launch(_lib.load().obca_plan_tracks, ctypes.byref(d), dev=dev)
+    _lib.keep_alive(out["track_clear"], tuple(ins.values()) + (score,), dev)       # the launch is asynchronous: see ``select``
+    return out
+
+
+def track_rows(tracks, track_t, track_len, Ts, N, pool_A=None, pool_b=None, pool_v=None, track_size=None, group=1, t0=None, margin=0.0,
+               far=100.0, solver=None):
+    """Timed tracks as the rows of an open-loop solve: ``pool_tracks`` with k = 0, measure=False and predict="track".  The
+    caller's static pool -- pool_A [B,Ks,4,2], pool_b [B,Ks,4] and optionally pool_v [B,Ks,2], or None for Ks = 0 -- gets Kt
+    slots appended, slot Ks + j being track j of block b // group at t0 (its rows grown by ``margin``, its chord velocity), and
+    every track gets its rows at the N + 1 stage times t0 + kk Ts.  Tracks as ``plan_track_clearance`` takes them; ``solver``
+    only names the device (None: the current one).
+
+    Returns a dict of device tensors on the current stream, no host synchronisation: pool_A [B,K,4,2], pool_b [B,K,4] and pool_v
+    [B,K,2] with K = Ks + Kt, stage_A [B,Kt,N+1,4,2], stage_b [B,Kt,N+1,4] and stage_ok [B,Kt] (``select``'s arguments of those
+    names with stage_group = 1), track_state [B,Kt] (a track that is not usable is a spare at ``far``) and Ks."""
+    import torch
+    _lib.require_gpu("scene.track_rows")
+    dev = solver.device if solver is not None else _dev_of(None, pool_A, tracks)
+    ego = DEFAULT_EGO
+    tracks, track_t, track_len, track_size = _tracks_on_device(tracks, track_t, track_len, track_size, ego, dev)
+    Bt, Kt = int(tracks.shape[0]), int(tracks.shape[1])
+    group = int(group)
+    if group < 1:
+        raise ValueError("group = %d: at least 1" % group)
+    B = Bt * group
+    full_A, full_b, full_v, Ks = _with_spare_slots(solver if solver is not None else _OnDevice(dev), B, pool_A, pool_b, pool_v, Kt,
+                                                   float(far), "Kt")
+    zeros = torch.zeros(B, 3, dtype=torch.float64, device=dev)
+    out = pool_tracks(tracks, track_t, track_len, track_size, Ts, torch.zeros(B, dtype=torch.int32, device=dev), zeros, full_A, full_b,
+                      full_v, int(N), group=group, t0=t0, predict="track", margin=margin, far=far, measure=False, device=dev)
+    return {"pool_A": full_A, "pool_b": full_b, "pool_v": full_v, "stage_A": out["stage_A"], "stage_b": out["stage_b"],
+            "stage_ok": out["stage_ok"], "track_state": out["track_state"], "Ks": Ks}
+
+
+def solve_tracks(solver, variant, x0, u0, xref, pool_A, pool_b, Ts, tracks, track_t, track_len, track_size=None, group=1, t0=None,
+                 margin=0.0, far=100.0, pool_v=None, term=None, params=None, rounds=2, n_sub=16, target=0.0, ego=DEFAULT_EGO):
+    """``solve_scene`` among obstacles on timed tracks: the caller's static pool (pool_A [B,Ks,4,2], pool_b [B,Ks,4], pool_v
+    [B,Ks,2] or None; None and None for Ks = 0) and Kt tracks (as ``plan_track_clearance`` takes them; a track's rectangle is
+    grown by ``margin`` in the rows and measured without it), ``solver`` with m == [4] * n_sel, n_sel <= Ks + Kt.  Variants 6
+    and 8 only: the tracks' clock needs a fixed step, stage kk being at t0 + kk Ts; obca_mpc4 reads stage 0's rows at every
+    stage and is refused (a device tensor is taken at its word but for that: an instance whose word is 4 is masked).
+
+    Round 0 is ``track_rows`` and the staged ``select`` on ``xref`` and ``x0``, then the solve.  Every solve is measured in
+    three parts: ``plan_track_clearance`` on the plans with dt = Ts, which folds the distances to the TRACKS THEMSELVES into the
+    running minimum of the tracked slots; the staged ``select`` with that state, which does the static slots and the
+    re-ranking; and ``pool_clearance`` of the plans against the caller's Ks slots alone.  The figure that decides which plan is
+    held and what ``clear`` says is min(static minimum, track_min), NaN where either is -- not the staged select's min_clear,
+    which rests on rows interpolated between two stage times for the tracked slots.  The rest is ``solve_scene``'s: every later
+    round solves only the instances whose selection changed, a later plan is held only if it is feasible and its figure larger.
+
+    Runs on the current stream without host synchronisation.  Returns (result, info) as ``solve_scene`` does -- clear,
+    min_clear, min_clear_first (round 0's true figure), rounds_used, sel (pool indices, Ks + j being track j), A_used, b_used --
+    and track_min_clear [B], track_clear [B,Kt] and track_state [B,Kt] of the held plan."""
+    import numpy as np
+    import torch
+    params = params or SolverParams()
+    dev, N, m = solver.device, solver.N, solver.m
+    n_sel = len(m)
+    x0 = torch.as_tensor(x0, dtype=torch.float64, device=dev).contiguous()
+    if x0.dim() != 2 or x0.shape[1] != 3:
+        raise ValueError("expected x0 [B,3], got %s" % (tuple(x0.shape),))
+    B = int(x0.shape[0])
+    if isinstance(variant, torch.Tensor) and variant.is_cuda:
+        variant = torch.where(variant.to(torch.int32) == 4, 0, variant.to(torch.int32)).to(torch.int32)
+    else:
+        v = np.asarray(variant.cpu() if isinstance(variant, torch.Tensor) else variant)
+        if not np.all(np.isin(v, (0, 6, 8))):
+            raise ValueError("variant %s: among tracks the solve is obca_mpc6 (6) or obca_mpc8 (8); obca_mpc4 reads stage 0's rows "
+                             "at every stage" % (v.tolist(),))
+        variant = torch.as_tensor(np.broadcast_to(v, (B,)).astype(np.int32), device=dev)
+    on_dev = lambda t, shape, dt=torch.float64: solver._dev(t, shape, dt)
+    variant = on_dev(variant, (B,), torch.int32)
+    u0, xref = on_dev(u0, (B, 2)), on_dev(xref, (B, 3, N + 1))
+    Ts = on_dev(torch.as_tensor(Ts, dtype=torch.float64).expand(B) if torch.as_tensor(Ts).dim() == 0 else Ts, (B,))
+    if t0 is not None:
+        t0 = on_dev(torch.as_tensor(t0, dtype=torch.float64).expand(B) if torch.as_tensor(t0).dim() == 0 else t0, (B,))
+    term = on_dev(torch.zeros(B, 3) if term is None else term, (B, 3))
+    tracks, track_t, track_len, track_size = _tracks_on_device(tracks, track_t, track_len, track_size, ego, dev)
+    Kt, group = int(tracks.shape[1]), int(group)
+    if group < 1 or int(tracks.shape[0]) * group != B:
+        raise ValueError("B = %d instances are not %d track blocks of group = %d" % (B, int(tracks.shape[0]), group))
+    rows = track_rows(tracks, track_t, track_len, Ts, N, pool_A, pool_b, pool_v, track_size=track_size, group=group, t0=t0,
+                      margin=margin, far=far, solver=solver)
+    full_A, full_b, full_v, Ks = rows["pool_A"], rows["pool_b"], rows["pool_v"], rows["Ks"]
+    K = Ks + Kt
+    if m != [4] * n_sel or n_sel > K:
+        raise ValueError("solver.m = %s does not fit a pool of %d obstacles of 4 rows: expected [4] * n_sel, n_sel <= %d" % (m, K, K))
+    cp = params.to_c() if isinstance(params, SolverParams) else params
+    kw = dict(pool_v=full_v, Ts=Ts, n_sub=n_sub, ego=ego, device=dev, stage_A=rows["stage_A"], stage_b=rows["stage_b"],
+              stage_ok=rows["stage_ok"], stage_group=1)
+    static = (full_A[:, :Ks].contiguous(), full_b[:, :Ks].contiguous(), full_v[:, :Ks].contiguous()) if Ks > 0 else None
+
+    state = select(full_A, full_b, xref, n_sel, x0=x0, variant=variant, **kw)
+
+    def measure(r, var):
+        """the three parts of a measurement of solve ``r``: (the staged select's dict, the tracks' dict, the true figure)"""
+        tr = plan_track_clearance(r.xopt, tracks, track_t, track_len, Ts, track_size=track_size, t0=t0, variant=var, status=r.status,
+                                  group=group, n_sub=n_sub, score=state["score"], ego=ego, device=dev)
+        t = select(full_A, full_b, r.xopt, n_sel, variant=var, status=r.status, state=state, **kw)
+        mc = tr["track_min"]
+        if static is not None:
+            _, smin = pool_clearance(r.xopt, static[0], static[1], pool_v=static[2], Ts=Ts, variant=var, n_sub=n_sub, ego=ego,
+                                     device=dev)
+            mc = torch.where(torch.isnan(smin) | torch.isnan(mc), float("nan"), torch.minimum(smin, mc))
+        return t, tr, mc
+
+    A_held, b_held, sel_held = state["A"], state["b"], state["sel"].clone()
+    held = solver.solve(variant, x0, u0, xref, A_held, b_held, Ts, term, cp)
+    t, tr, min_clear = measure(held, variant)
+    first = min_clear.clone()
+    track_min, track_clear = tr["track_min"], tr["track_clear"]
+    rounds_used = torch.zeros(B, dtype=torch.int32, device=dev)
+    iters = held.iters.clone()
+    cur, var = None, t["variant_out"]
+    for _ in range(int(rounds)):
+        A_cur, b_cur, sel_cur = t["A"], t["b"], state["sel"].clone()
+        if cur is None:
+            cur = solver.solve(var, x0, u0, xref, A_cur, b_cur, Ts, term, cp)
+        else:
+            solver.solve(var, x0, u0, xref, A_cur, b_cur, Ts, term, cp, out=cur)
+        iters += cur.iters                                       # a masked instance reports 0
+        rounds_used += (var != 0).to(torch.int32)
+        t, tr, mc = measure(cur, var)
+        better = mc > min_clear                                  # NaN (masked, infeasible) compares false
+        for name in ("xopt", "uopt", "ts_opt", "status", "info"):
+            h, c = getattr(held, name), getattr(cur, name)
+            if h is not None:
+                h.copy_(torch.where(better.reshape((B,) + (1,) * (h.dim() - 1)), c, h))
+        min_clear = torch.where(better, mc, min_clear)
+        track_min = torch.where(better, tr["track_min"], track_min)
+        track_clear = torch.where(better[:, None], tr["track_clear"], track_clear)
+        A_held = torch.where(better[:, None, None, None], A_cur, A_held)
+        b_held = torch.where(better[:, None, None], b_cur, b_held)
+        sel_held = torch.where(better[:, None], sel_cur, sel_held)
+        var = t["variant_out"]
+    held.iters.copy_(iters)
+    return held, {"clear": min_clear >= float(target), "min_clear": min_clear, "min_clear_first": first,
+                  "rounds_used": rounds_used, "sel": sel_held, "A_used": A_held, "b_used": b_held,
+                  "track_min_clear": track_min, "track_clear": track_clear, "track_state": rows["track_state"]}
 
 
 class PoolLoop:
