@@ -44,6 +44,7 @@ def load():
     _lib = build_shim("native_host", [SRC], openmp=True)
     _lib.lpi_host_solve_batch.restype = ctypes.c_int
     _lib.lpi_host_solve_batch_cert.restype = ctypes.c_int
+    _lib.lpi_host_solve_batch_warm.restype = ctypes.c_int
     _lib.rollout_host_run.restype = ctypes.c_int
     return _lib
 
@@ -52,9 +53,12 @@ def _ptr(a):
     return a.ctypes.data_as(ctypes.c_void_p)
 
 
-def lpi_solve(variant, N, m, x0, u0, xref, A, b, Ts, term=None, params=None, cert=False):
+def lpi_solve(variant, N, m, x0, u0, xref, A, b, Ts, term=None, params=None, cert=False, warm=None, cert_fill=0.0):
     """the structured solver of csrc/obca_lpi_core.h on the CPU; arrays as in include/obca_mpc.h.
-    cert=True adds the certificate buffers (final primal vector "z" and multipliers "y", include/obca_mpc.h)"""
+    cert=True adds the certificate buffers (final primal vector "z" and multipliers "y", include/obca_mpc.h), every word
+    ``cert_fill`` before the solve.
+    warm=(z, use, mu) is obca_set_warm_start on the host: ``z`` the caller's float64 [B, n_max] array, read and written in
+    place; ``use`` int32 [B] or None (every instance); ``mu`` the barrier parameter of a warm-started pass"""
     from oracle import c_oracle
     lib = load()
     x0 = np.ascontiguousarray(x0, float)
@@ -70,13 +74,21 @@ def lpi_solve(variant, N, m, x0, u0, xref, A, b, Ts, term=None, params=None, cer
     marr = (ctypes.c_int * len(m))(*[int(v) for v in m])
     extra = []
     fn = lib.lpi_host_solve_batch
+    nO = len(m)
+    n_max = (N + 1) * (3 + M + 4 * nO) + 2 * N + 1
     if cert:
-        nO = len(m)
-        n_max = (N + 1) * (3 + M + 4 * nO) + 2 * N + 1
         R_max = 3 + 3 * N + 3 + 2 * (N + 1) + 4 * N + 2 + 2 * (N + 1) * nO + (N + 1) * (M + 4 * nO)
-        out["z"], out["y"] = np.zeros((B, n_max)), np.zeros((B, R_max + 2 * (N + 1) * nO))
+        out["z"], out["y"] = np.full((B, n_max), float(cert_fill)), np.full((B, R_max + 2 * (N + 1) * nO), float(cert_fill))
         extra = [_ptr(out["z"]), _ptr(out["y"])]
         fn = lib.lpi_host_solve_batch_cert
+    if warm is not None:
+        z, use, mu = warm
+        assert isinstance(z, np.ndarray) and z.dtype == np.float64 and z.flags.c_contiguous and z.shape == (B, n_max)
+        assert float(mu) > 0.0                       # as obca_set_warm_start
+        if use is not None:
+            assert isinstance(use, np.ndarray) and use.dtype == np.int32 and use.flags.c_contiguous and use.shape == (B,)
+        extra = [_ptr(z), None if use is None else _ptr(use), ctypes.c_double(float(mu))] + (extra or [None, None])
+        fn = lib.lpi_host_solve_batch_warm
     rc = fn(N, len(m), marr, _ptr(var), B, *[_ptr(a) for a in arrs], _ptr(term),
             ctypes.byref(params), _ptr(out["xopt"]), _ptr(out["uopt"]), _ptr(out["ts_opt"]),
             _ptr(out["status"]), _ptr(out["iters"]), _ptr(out["info"]), *extra)

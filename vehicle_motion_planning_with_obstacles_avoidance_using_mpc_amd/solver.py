@@ -115,6 +115,7 @@ class BatchSolver:
         _lib.check(self.lib.obca_create(ctypes.byref(d), ctypes.byref(h)))
         self._h = h
         self.lds_bytes = int(self.lib.obca_lds_bytes(ctypes.byref(d)))
+        self.warm_z = self.warm_use = None          # enable_warm_start
         if mode is not None:
             self.set_mode(mode)
 
@@ -153,6 +154,27 @@ class BatchSolver:
         else:
             _lib.check(self.lib.obca_set_certificate_buffers(self._h, None, None))
             self.cert_z = self.cert_y = None
+
+    def enable_warm_start(self, mu_init=0.1, use=None):
+        """Optional warm start -- not reference behaviour (include/obca_mpc.h, obca_set_warm_start): while on, every solve that
+        ends converged or acceptable stores its primal vector in ``self.warm_z`` [max_batch, primal_size], and the next solve of
+        an instance b with ``use[b] != 0`` (``use`` None: every instance) starts from row b moved one horizon stage forward, with
+        barrier parameter ``mu_init``.  ``use`` is an int32 [max_batch] device tensor (anything else is copied into one) -- one
+        word per instance the handle can hold, not per instance of the next batch: another length is a ValueError; it is
+        kept in ``self.warm_use`` and read at every solve, so the caller may rewrite it between solves.  A call while on keeps
+        the stored vectors."""
+        if not float(mu_init) > 0.0:
+            raise ValueError("mu_init must be positive, got %r" % (mu_init,))
+        if self.warm_z is None:
+            nz = int(self.lib.obca_primal_size(ctypes.byref(self._dims)))
+            self.warm_z = torch.zeros(self.max_batch, nz, dtype=torch.float64, device=self.device)
+        self.warm_use = None if use is None else self._dev(use, (self.max_batch,), torch.int32)
+        _lib.check(self.lib.obca_set_warm_start(self._h, _lib.ptr(self.warm_z), _lib.ptr(self.warm_use), float(mu_init)))
+
+    def disable_warm_start(self):
+        """back to cold starts: nothing is stored and nothing read; ``self.warm_z`` stays as it is, for a later enable_warm_start"""
+        _lib.check(self.lib.obca_set_warm_start(self._h, None, None, 0.0))
+        self.warm_use = None
 
     def close(self):
         if getattr(self, "_h", None):
