@@ -6,6 +6,8 @@
 # its exports.
 #   tools/build_variant.sh prof -DOBCA_PROFILE        per-phase shader-clock counters (tools/gpu_prof.py)
 #   tools/build_variant.sh straight -DOBCA_LOOP_R4=false -DOBCA_LOOP_R56=false     form of the ladder's passes per kernel (csrc/obca_kernel.hip: solve_passes)
+#   tools/build_variant.sh cnt -DOBCA_PROFILE -DOBCA_MATH_COUNT       calls of the out-of-line math per iteration (OBCA_MATH_COUNT=1 tools/gpu_prof.py)
+#   tools/build_variant.sh liblog -DOBCA_LIBRARY_LOG / sepsc -DOBCA_SEPARATE_SINCOS     the library's log() / separate sin() and cos() back (csrc/obca_kernel.hip: dlog, dsincos)
 set -e
 NAME=$1; shift
 python "$(dirname "$0")/../__graft_entry__.py" variant "$NAME" -- "$@"

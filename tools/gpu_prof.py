@@ -31,6 +31,11 @@ elif p[:,18].max() > 0:     # library built with -DOBCA_TWO_SIDED_CHECK: slots 1
     print('two-sided vs one-sided sweep, same data: max rel. difference of the step %.2e (median of per-instance maxima %.2e), of the elastic multiplier steps %.2e (median %.2e)'
           % (p[:,18].max()/1e18, np.median(p[:,18])/1e18, p[:,19].max()/1e18, np.median(p[:,19])/1e18))
     p[:,18:] = 0
+if os.environ.get('OBCA_MATH_COUNT'):     # library built with -DOBCA_PROFILE -DOBCA_MATH_COUNT: slots 12 / 13 / 14 hold counts, not the sweep's first three clocks
+    tr, re_, pw = (p[:,i].sum()/it.sum() for i in (12, 13, 14))
+    print('per iteration: line-search trials %.4f, evaluations of phi(x_k) in rowsteps %.4f, iterations forming the two powers %.4f -> dlog calls %.3f (one per row slot, %d slots), dsincos calls %.3f, dpow calls %.3f'
+          % (tr, re_, pw, -(-rows//64)*(tr+re_), -(-rows//64), tr, 2*pw))
+    p[:,12:15] = 0
 names=["grad+err","mu","rowE+gatherB","asm_stages","local","riccati","rowsteps","linesearch","accept","reeval","prologue","loop","r:FG+term","r:phaseA","r:phaseB","r:stage0","r:forward","r:recover","rs:slotloop","rs:staging"]      # one-wavefront kernels: rowsteps' rolled staging loop (row_jdx) and unrolled slot loop; "rowsteps" is the rest of that phase
 tot=p[:,:12].sum(1)+(p[:,18]+p[:,19] if onewave else 0)
 print('mean iters %.1f nfact %.1f total cycles/solve %.3e'%(it.mean(), nf.mean(), tot.mean()))

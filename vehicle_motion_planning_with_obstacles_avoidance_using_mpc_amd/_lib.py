@@ -323,6 +323,11 @@ def load():
     lib.obca_plan_tracks_init.restype = None
     lib.obca_plan_tracks.argtypes = [ctypes.POINTER(ObcaPlanTracks), ctypes.c_int32, vp]
     lib.obca_plan_tracks.restype = ctypes.c_int
+    # test hook of csrc/obca_math_probe.hip (not in include/obca_mpc.h, not in EXPORTS): math_probe() below.  A library of an
+    # older tree loaded beside this one for an A/B (OBCA_LIB, tools/ab_run.sh) has none; math_probe() on it raises.
+    if hasattr(lib, "obca_math_probe"):
+        lib.obca_math_probe.argtypes = [ctypes.c_int32, ctypes.c_int64, vp, vp, ctypes.c_int32, vp]
+        lib.obca_math_probe.restype = ctypes.c_int
     lib.obca_lds_bytes.argtypes = [ctypes.POINTER(ObcaDims)]
     lib.obca_lds_bytes.restype = ctypes.c_int64
     lib.obca_strerror.argtypes = [ctypes.c_int]
@@ -360,6 +365,23 @@ def check(code):
 def launch(fn, *args, dev):
     """the call ``fn(*args, device, stream)`` on torch device ``dev`` and its current stream; raises on an error code"""
     check(fn(*args, device_index(dev), stream_ptr(dev)))
+
+
+MATH_PROBE_KINDS = {"obca_log": 0, "log": 1, "obca_sincos": 2, "sin_cos": 3}
+
+
+def math_probe(kind, x):
+    """tests only: the device's elementary functions on the float64 CUDA tensor ``x`` (csrc/obca_math_probe.hip).  ``kind``:
+    "obca_log" (csrc/obca_math.h) and "log" (device library) return a tensor like ``x``; "obca_sincos" (the shared reduction the
+    solver calls) and "sin_cos" (separate library calls) return [n, 2]: sine, cosine"""
+    import torch
+    require_gpu("math_probe")
+    assert x.is_cuda and x.dtype == torch.float64 and x.is_contiguous() and x.dim() == 1 and x.numel() > 0
+    k = MATH_PROBE_KINDS[kind]
+    out = torch.empty((x.numel(), 2) if k >= 2 else (x.numel(),), dtype=torch.float64, device=x.device)
+    launch(load().obca_math_probe, k, x.numel(), ptr(x), ptr(out), dev=x.device)
+    keep_alive(out, (x,), x.device)
+    return out
 
 
 def keep_alive(anchor, tensors, dev):

@@ -18,6 +18,7 @@
 #include <math.h>
 #include <type_traits>
 #include "obca_device.h"
+#include "obca_math.h"
 
 #define SYNC() __syncthreads()
 
@@ -40,6 +41,16 @@ __device__ long long* prof_dummy;
 #define PROF(i)
 #define RPROF(i)
 #endif
+// -DOBCA_PROFILE -DOBCA_MATH_COUNT: profile slots 12 / 13 / 14 (the sweep's first three clocks, outside the total) hold counts
+// instead: line-search trials (one eval_geom = one dsincos round, and one dlog per row slot), evaluations of phi(x_k) in
+// rowsteps (one dlog per row slot), and iterations that form the switching condition's two powers (two dpow).
+#if defined(OBCA_PROFILE) && defined(OBCA_MATH_COUNT)
+#define MCOUNT_DECL long long mcount[3] = {0, 0, 0};
+#define MCOUNT(i) { mcount[i] += 1; }
+#else
+#define MCOUNT_DECL
+#define MCOUNT(i)
+#endif
 
 namespace {
 
@@ -48,12 +59,36 @@ constexpr int MW = OBCA_MAX_EDGES + 6;      // local block width: lambda (<=4) +
 constexpr int NW = OBCA_MAX_EDGES + 4;      // primal part of the local block
 
 // ---------------------------------------------------------------- out-of-line math
-// fp64 log/pow/sincos expand to 150-400 instructions each; inlined at every call site they pushed the hot loop
-// past the 64 KiB instruction cache.  One shared copy each.
-__device__ __noinline__ double dlog(double x) { return log(x); }
-__device__ __noinline__ double dpow(double x, double y) { return exp(y * log(x)); }
+// fp64 log/pow/sincos expand to 80-200 instructions each; inlined at every call site they pushed the hot loop
+// past the 64 KiB instruction cache.  One shared copy each.  The logarithm is the project's own (csrc/obca_math.h: 76
+// instructions on the path taken, the device library's log() has 113), the same in every kernel family of this unit; the
+// exponential stays the library's.  Sine and cosine come from the library's sincos(): ONE argument reduction (190
+// instructions) where separate sin() and cos() ran it twice (340), the same words (tests/test_gpu_math.py).
+// Dev builds for an A/B of either item alone (tools/build_variant.sh): -DOBCA_LIBRARY_LOG puts the library's log() back,
+// -DOBCA_SEPARATE_SINCOS the separate sin() and cos().
+#ifdef OBCA_LIBRARY_LOG
+#define OBCA_LOG(x) log(x)
+#else
+#define OBCA_LOG(x) obca_log(x)
+#endif
+__device__ __noinline__ double dlog(double x) { return OBCA_LOG(x); }
+__device__ __noinline__ double dpow(double x, double y) { return exp(y * OBCA_LOG(x)); }
 struct SinCos { double s, c; };
+#ifdef OBCA_SEPARATE_SINCOS
 __device__ __noinline__ SinCos dsincos(double x) { SinCos r; r.s = sin(x); r.c = cos(x); return r; }
+#else
+// The shared reduction needs 26 vector and 6 scalar registers, the separate calls needed 32 and 22.  The compiler tells the callers
+// which registers a callee writes, and with v26-v31 and s6-s21 left alone it allocated the shape kernels' bodies (at 512 of 512
+// registers) differently: two doubles spilled in (5, 3, 6) and (6, 3, 6), 16 B more scratch in (5, 4, 10), (5, 6, 18) and
+// (6, 5, 14).  Declared written, the callers keep the allocation they had.
+__device__ __noinline__ SinCos dsincos(double x) {
+    SinCos r;
+    obca_sincos(x, &r.s, &r.c);
+    asm volatile("" ::: "v26", "v27", "v28", "v29", "v30", "v31", "s6", "s7", "s8", "s9", "s10", "s11", "s12", "s13", "s14", "s15",
+                 "s16", "s17", "s18", "s19", "s20", "s21");
+    return r;
+}
+#endif
 
 // ---------------------------------------------------------------- wave reductions (64 lanes)
 // DPP within each row of 16 lanes (no LDS crossbar: __shfl_xor lowers to ds_bpermute, ~12 dependent LDS
@@ -2330,6 +2365,7 @@ __device__ __forceinline__ void obca_ipm_body(DESC& Ain, const int inst, const b
     bool soc_pass = false, use_soc = false, first_trial = true;
     int soc_it = 0;
     PROF_DECL
+    MCOUNT_DECL
 #ifdef OBCA_PROFILE
     if (NT == 64) prof_t[10] += prof_last - prof_body_t0;
 #endif
@@ -2494,6 +2530,7 @@ __device__ __forceinline__ void obca_ipm_body(DESC& Ain, const int inst, const b
         // one log per row -- when the barrier parameter has changed since, at the first iterate, or in a corrected solve
         const double phik = GET(IV_PHIK);
         const bool phi_known = !soc_pass && isfinite(phik);
+        if (!phi_known) { MCOUNT(1) }
         const double tau = GET(IV_TAU);
         if constexpr (SHAPE::variant != 0) {
             mixed_then_mu<SHAPE, false>(lane, [&](auto km, int r) __attribute__((always_inline)) {      // (mu rounds: in the slot loop, mu_direct)
@@ -2571,6 +2608,7 @@ __device__ __forceinline__ void obca_ipm_body(DESC& Ain, const int inst, const b
             // lane: read back from lane 0 they are scalars, and no vector register carries them through the line search.
             const bool sw = dphi < 0.0 && th <= GET(IV_THMIN);
             if (sw) {
+                MCOUNT(2)
                 pw_th = lane_read(dpow(th, OBCA_S_THETA), 0);
                 pw_dphi = lane_read(dpow(-dphi, OBCA_S_PHI), 0);
             }
@@ -2593,6 +2631,7 @@ __device__ __forceinline__ void obca_ipm_body(DESC& Ain, const int inst, const b
         for (;;) {
             for (int t = lane; t < L.n; t += NT) S.xt[t] = S.x[t] + a_try * S.dx[t];
             SYNC();
+            MCOUNT(0)
             eval_geom(L, S, S.xt, S.ctt, S.stt, S.cct, lane);
             f_t = eval_objective<true>(L, S, in, S.xt, sf, lane);     // gradient too: gf of the current point is spent
             double th_t = 0.0, phi_t = 0.0;
@@ -2790,6 +2829,9 @@ __device__ __forceinline__ void obca_ipm_body(DESC& Ain, const int inst, const b
     }
 #ifdef OBCA_PROFILE
     if (A.prof && lane == 0) for (int i = 0; i < 20; ++i) A.prof[(size_t)inst * 20 + i] = (double)prof_t[i];
+#ifdef OBCA_MATH_COUNT
+    if (A.prof && lane == 0) for (int i = 0; i < 3; ++i) A.prof[(size_t)inst * 20 + 12 + i] = (double)mcount[i];
+#endif
 #endif
 
     const int l0 = __builtin_amdgcn_readfirstlane(ladder_state[0]);      // (read by every wavefront BEFORE the barrier, rewritten by thread 0 after it)
